@@ -21,12 +21,17 @@ Clock pre-conditioning: a GPU that has been idle starts a run of launches at boo
 about 5 launches in and takes ~20 launches to settle (round-1 trace: 576 -> 725 -> 571 us).  Before the W warm-up steps
 the bench therefore launches the same step until the series has settled (`settled_tail`: the mean of the last 10 launches within
 2 % of the mean of the 10 before them and no outlier among them; at most 300 launches / ~0.2 s), untimed, so that a short timed window (--steps 20) measures the steady state.  The per-launch
-distribution of the TIMED steps (min / median / p90 / max) is printed so that a transient stays visible.
+distribution of the TIMED steps (min / median / p90 / max; the last 4095 of them at most) is printed so that a transient stays visible.
 
 Prints ONE JSON line on rank 0.  `roofline.achieved` = algorithmic bytes per launch
 (hop*4 + K*8 = 9216 B/frame x frames) / mean kernel time measured with HIP events on the library's stream.
 `cpu_baseline` = the oracle's C restatement of the BinaryBackend path (oracle/bb_baseline.c) timed on this
 box's host cores on a bounded sample (rank 0, N=1 only).
+
+A plain run measures the headline alone: set-up, clock pre-conditioning, the W warm-up and K timed steps, the line.  `--full` adds
+every other block: config 2 as written (`single_stream`), `host_path`, the in-run check against the oracle (`verify`), the no-math
+ceiling (`roofline.mix_ceiling`), `yardsticks`, configs 3 / 4 / 5, the assemblies at N > 1 and `cpu_baseline`; the blocks a plain run
+leaves out are null or absent in its line.  `--dump-outputs DIR` writes a seeded sample of the timed steps' spectrum (dump_outputs).
 """
 from __future__ import annotations
 
@@ -50,6 +55,7 @@ L = SR * SECONDS                      # 2 880 000 samples
 M = (L - N_FFT) // HOP + 1            # 11 247 frames
 BYTES_PER_FRAME = HOP * 4 + N_FFT * 8  # 9 216 algorithmic bytes / frame
 HBM_PEAK_GBS = 8000.0                 # MI355X_MICROARCH.md chip table (spec); measured copy ceiling 6290
+MAX_LAPS = 4095                       # intervals of one timer_lap series (the library holds 4096 events per series)
 
 
 def synth(seed: int) -> np.ndarray:
@@ -681,6 +687,26 @@ class FileControl:
                 pass
 
 
+def dump_outputs(dirpath, ctx, lib, _lib, C, zd, B):
+    """--dump-outputs DIR: the c64 spectrum (B, M, N_FFT) the last timed step left in `zd`, as a fixed sample: in every stream its first
+    and last frame and frames drawn with a fixed seed between them (64 per stream up to 64 streams, fewer beyond, never under 2), the
+    same rows for every run with the same arguments.  Written as DIR/stft.npy, float32 (B, frames per stream, N_FFT, 2) = real and
+    imaginary parts: 16.8 MB at the default 32 streams, under 48 MB for any batch that fits the device."""
+    k = max(2, min(64, 4096 // B))
+    prng = np.random.Generator(np.random.PCG64(2718))
+    z = np.empty((B, k, N_FFT), np.complex64)
+    for b in range(B):
+        frames = [0] + sorted(int(m) for m in prng.choice(np.arange(1, M - 1), k - 2, replace=False)) + [M - 1]
+        for i, m in enumerate(frames):
+            _lib.check(lib.nxsig_download(ctx.handle, z[b, i].ctypes.data_as(C.c_void_p), C.c_void_p(zd.ptr + (b * M + m) * N_FFT * 8),
+                                          N_FFT * 8))
+    os.makedirs(dirpath, exist_ok=True)
+    a = z.view(np.float32).reshape(B, k, N_FFT, 2)
+    np.save(os.path.join(dirpath, "stft.npy"), a)
+    return {"dir": dirpath, "files": {"stft.npy": list(a.shape)},
+            "what": f"spectrum of the last timed step, {k} seeded frames per stream (first and last included), real / imaginary parts"}
+
+
 def self_spawn(args) -> int:
     """`python bench.py --gpus N` with no RANK / WORLD_SIZE in the environment: start N copies of this script, one per GPU, with the
     variables a launcher sets (RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR = 127.0.0.1, a free MASTER_PORT).  Rank 0 inherits stdout
@@ -740,8 +766,8 @@ def main():
     ap.add_argument("--no-yardsticks", action="store_true", help="skip the plain copy / read / fill / mix bandwidth yardsticks")
     ap.add_argument("--dry", action="store_true",
                     help="PREFLIGHT (first contact with an N-GPU node): allocate exactly what the run allocates, create the group, run ONE launch of every "
-                         "block and of both assemblies, and print one JSON line with `dry: true`, the per-rank memory high-water marks and the RCCL "
-                         "library actually loaded — no settling, no timing claims, no CPU baseline")
+                         "block (with --full: of every block and of both assemblies), and print one JSON line with `dry: true`, the per-rank memory "
+                         "high-water marks and the RCCL library actually loaded — no settling, no timing claims, no CPU baseline")
     ap.add_argument("--share-gpu", action="store_true",
                     help="TEST MODE for one-GPU boxes: every rank uses device LOCAL_RANK %% device_count and claims its own "
                          "NCCL_HOSTID, so several ranks can form an RCCL communicator on ONE GPU (socket transport over lo); "
@@ -754,7 +780,19 @@ def main():
                          "--share-gpu: 1, because N ranks x N shards must fit ONE device there)")
     ap.add_argument("--precondition", type=int, default=300,
                     help="max untimed launches spent settling the clocks before the warm-up steps (0 = none)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: config 2 as written, the host path, the in-run check against the oracle, the no-math "
+                         "ceiling, the bandwidth yardsticks, configs 3 / 4 / 5, the assemblies (N > 1) and cpu_baseline.  Without it a run "
+                         "sets up, settles the clocks, warms up, times the steps and prints the line; --no-verify / --no-secondary / "
+                         "--no-yardsticks / --cpu-seconds only act with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the spectrum their last step computed to DIR/stft.npy "
+                         "(float32, see dump_outputs; rank 0's shard at N > 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run measures the headline alone
+        args.no_verify, args.no_secondary, args.no_yardsticks, args.cpu_seconds = True, True, True, 0.0
     if args.dry:
         args.steps, args.warmup, args.precondition, args.cpu_seconds, args.no_yardsticks = 1, 0, 0, 0.0, True
 
@@ -886,17 +924,23 @@ def main():
     import gc
     gc.collect()
     gc.disable()   # no collector pause between two launches of the timed window
+    # a lap series holds at most 4096 events (nxsig_timer_lap): one interval per step for the last `first_lap` .. K-1 steps, and the
+    # kernel time of ALL K steps from one start / stop pair of events, so that no read-out of a series interrupts the timed window
+    first_lap = max(0, args.steps - MAX_LAPS)
     barrier()
     t0 = time.perf_counter()
-    ctx.timer_lap()
-    for _ in range(args.steps):
+    ctx.timer_start()
+    for i in range(args.steps):
+        if i == first_lap:
+            ctx.timer_lap()
         step()
-        ctx.timer_lap()
-    laps = ctx.timer_laps()  # HIP events on the stream the kernels run on, one interval per step (synchronises)
+        if i >= first_lap:
+            ctx.timer_lap()
+    kernel_ms_total = ctx.timer_stop()  # HIP events on the stream the kernels run on, first step to last (synchronises)
+    laps = ctx.timer_laps()
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
-    kernel_ms_total = float(sum(laps))
     if group is not None:
         elapsed, kernel_ms_total = group.allreduce([elapsed, kernel_ms_total], "max")
     elif filectl is not None:
@@ -908,21 +952,26 @@ def main():
     kernel_ms = kernel_ms_total / args.steps
     achieved = (B * M * BYTES_PER_FRAME) / (kernel_ms * 1e-3) / 1e9  # GB/s per GPU, algorithmic bytes
 
+    # the timed steps' result, before any later block reuses the spectrum buffer
+    outputs = dump_outputs(args.dump_outputs, ctx, lib, _lib, C, zd, B) if args.dump_outputs and rank == 0 else None
+
     # config 2 exactly as written: ONE 60 s stream per launch, back-to-back launches (L3-resident; one round of workgroups: start-up latencies dominate)
-    for _ in range(1 if args.dry else 20):
-        step(1)
-    ctx.sync()
-    ctx.timer_start()
-    reps = 1 if args.dry else 200
-    for _ in range(reps):
-        step(1)
-    single_ms = ctx.timer_stop() / reps
-    single = {
-        "workload": "1 x 60 s mono (config 2 as written, 103.7 MB: Infinity-Cache resident; the one-round geometry of round 6: 176 twelve-wave workgroups, one per CU; start-up and the XCDs' dispatch stagger are ~3.5 of its ~18.5 us, profiles/r06/one_round_phase_trace.txt)",
-        "ms_per_launch": single_ms,
-        "frames_per_s": M / (single_ms * 1e-3),
-        "algorithmic_GBps": M * BYTES_PER_FRAME / (single_ms * 1e-3) / 1e9,
-    }
+    single = None
+    if args.full:
+        for _ in range(1 if args.dry else 20):
+            step(1)
+        ctx.sync()
+        ctx.timer_start()
+        reps = 1 if args.dry else 200
+        for _ in range(reps):
+            step(1)
+        single_ms = ctx.timer_stop() / reps
+        single = {
+            "workload": "1 x 60 s mono (config 2 as written, 103.7 MB: Infinity-Cache resident; the one-round geometry of round 6: 176 twelve-wave workgroups, one per CU; start-up and the XCDs' dispatch stagger are ~3.5 of its ~18.5 us, profiles/r06/one_round_phase_trace.txt)",
+            "ms_per_launch": single_ms,
+            "frames_per_s": M / (single_ms * 1e-3),
+            "algorithmic_GBps": M * BYTES_PER_FRAME / (single_ms * 1e-3) / 1e9,
+        }
 
     # ---- the path a drop-in caller takes by default: HOST tensors in, HOST tensors out (NXSIG_HOST: what NxSignalAMD.stft(%Nx.Tensor{}) and
     # the Python mirror on numpy arrays call).  8 x config 2 per call = 92 MB up, 737 MB down over PCIe: chunked pageable copies with the
@@ -930,7 +979,7 @@ def main():
     # hipMemcpy into / out of pinned memory: nothing faster can cross it) and the pinned-slot pipeline built in round 6 (NXSIG_HOST_PIPE=1,
     # not faster: profiles/r06/host_path.txt).  Never part of `value`.
     host_path = None
-    if rank == 0 and not args.dry:
+    if args.full and rank == 0 and not args.dry:
         try:
             HB = 8
             xh = np.stack([synth(1234 + b) for b in range(HB)])   # (stream 0 = the headline's stream 0 on rank 0)
@@ -984,7 +1033,8 @@ def main():
     # optional final assembly, timed SEPARATELY from frames/s: RCCL all-gather of one 60 s stream's
     # spectrum per rank (92 MB each).  Outputs otherwise stay sharded and device-resident.
     assembly = None
-    if group is not None:
+    assemble = args.full and group is not None
+    if assemble:
         zt, local_err = None, None
         try:  # this rank's part: buffer + own shard
             if os.environ.get("NXSIG_BENCH_FAIL_ASSEMBLY_RANK") == str(rank):   # failure injection (tests/test_bench_multi.py)
@@ -999,11 +1049,11 @@ def main():
         # the ranks AGREE before the first collective is queued: a rank whose part failed must not leave its peers inside an all-gather
         # (round 6: a stale HIP error on rank 0 did exactly that to the one-device test mode)
         any_bad = group.allreduce([1.0 if local_err else 0.0], "max")[0] != 0.0
-    if group is not None and any_bad:
+    if assemble and any_bad:
         assembly = {"error": local_err or "another rank could not prepare its shard; the collective was skipped on every rank"}
         if zt is not None:
             zt.free()
-    elif group is not None:
+    elif assemble:
         try:  # the optional assembly must never take the measurement down with it
             counts = [M * N_FFT * 8] * world
             for _ in range(0 if args.dry else 2):
@@ -1065,7 +1115,7 @@ def main():
     # frame pair, 2 pairs per wave, short-lived 4-wave workgroups, 12 KB of tables per workgroup) with no arithmetic, same buffers
     # (the spectrum buffer is scratch from here on: the verification above has read it), same stream, right after the timed steps
     headline_ceiling = None
-    diag = load_diag()
+    diag = load_diag() if args.full else None
     if diag is not None and rank == 0:
         try:
             tabd = ctx.empty((3072,), np.float32)
@@ -1198,6 +1248,8 @@ def main():
             "value_cold_note": "frames/s of the first 20 launches (after the one table-building call) following the idle period of the input upload, before any pre-conditioning "
                                "(what a caller that issues a handful of calls from idle sees); `value` is the settled rate",
             "precondition": precondition,
+            "full": bool(args.full),
+            "outputs": outputs,
             "dry": bool(args.dry),
             "preflight": {"memory_rank0": memrep, "high_water_GiB_per_rank": per_rank_hw, "rccl": rccl_info(lib, C) if ("RANK" in os.environ or args.dry) else None,
                           "note": "dry run: one launch of every block, no settling — the figures above are NOT measurements" if args.dry else None},

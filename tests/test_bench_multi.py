@@ -9,7 +9,7 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "3", "--warmup", "1", "--streams", "2", "--cpu-seconds", "0", "--precondition", "0", "--no-verify",
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--streams", "2", "--cpu-seconds", "0", "--precondition", "0", "--no-verify",
          "--secondary-seconds", "20", "--secondary-channels", "2", "--istft-seconds", "10"]
 
 

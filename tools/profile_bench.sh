@@ -6,7 +6,7 @@
 # PMC passes never combine with sys/runtime traces (gpurun refuses that combination).
 set -u
 TAG=${1:-r01}
-ARGS=${2:-"--steps 20 --warmup 5 --cpu-seconds 0 --no-verify"}
+ARGS=${2:-"--full --steps 20 --warmup 5 --cpu-seconds 0 --no-verify"}
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
