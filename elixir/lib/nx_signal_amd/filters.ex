@@ -1,6 +1,7 @@
 defmodule NxSignalAMD.Filters do
   @moduledoc """
-  `NxSignal.Filters.firwin/3` (lib/nx_signal/filters.ex:147-279) and the streaming `fir/3` the reference lacks:
+  `NxSignal.Filters.median/2`, `wiener/2` (lib/nx_signal/filters.ex:17-110, :281-303) on the GPU kernels of DESIGN.md section 3.9,
+  `firwin/3` (:147-279) and the streaming `fir/3` the reference lacks:
   `fir(x, taps, mode: :same)` == `NxSignal.Convolution.convolve(x, taps, method: :fft, mode: :same)` to fp32
   rounding, computed by overlap-save block FFT convolution on the GPU.
   """
@@ -80,6 +81,74 @@ defmodule NxSignalAMD.Filters do
     {:ok, y} = nif.(NxSignalAMD.context(), xb, length, Tuple.product(batch_shape), hb, @modes[opts[:mode]]) |> NxSignalAMD.unwrap!()
     n_out = div(byte_size(y), es * max(Tuple.product(batch_shape), 1))
     Nx.from_binary(y, type) |> Nx.reshape(Tuple.insert_at(batch_shape, r - 1, n_out))
+  end
+
+  @doc """
+  Sliding-window median: every output is the median of the `:kernel_shape` window that starts at `min(i, n - k)` on every axis
+  (no padding).  The result is f32 of the input's shape; integer tensors are computed like f64.
+  """
+  def median(t, opts) do
+    opts = Keyword.validate!(opts, [:kernel_shape])
+    ks = opts[:kernel_shape]
+
+    if not is_tuple(ks) or Nx.rank(t) != tuple_size(ks) do
+      raise ArgumentError, message: "kernel shape must be of the same rank as the tensor"
+    end
+
+    {type, is_f64} =
+      case Nx.type(t) do
+        {:c, _} -> raise ArgumentError, "median: complex tensors have no order"
+        {:f, 32} -> {:f32, 0}
+        _ -> {:f64, 1}
+      end
+
+    shape = Tuple.to_list(Nx.shape(t))
+    kl = Tuple.to_list(ks)
+
+    Enum.zip(shape, kl)
+    |> Enum.each(fn {n, k} ->
+      if not (is_integer(k) and k >= 1 and k <= n), do: raise(ArgumentError, "median: kernel_shape #{inspect(ks)} does not fit #{inspect(Nx.shape(t))}")
+    end)
+
+    xb = t |> Nx.as_type(type) |> Nx.to_binary()
+    {:ok, y} = NIF.median(NxSignalAMD.context(), xb, is_f64, shape, kl) |> NxSignalAMD.unwrap!()
+    Nx.from_binary(y, :f32) |> Nx.reshape(Nx.shape(t))
+  end
+
+  @doc """
+  Wiener filter: local mean and variance over the `:kernel_size` window (mode :same) in f64, `:noise` (nil: the mean local
+  variance), the result cast back to the input's type (f32 or f64).
+  """
+  def wiener(t, opts \\ []) do
+    opts = Keyword.validate!(opts, noise: nil, kernel_size: 3)
+    rank = Nx.rank(t)
+
+    ks =
+      cond do
+        is_integer(opts[:kernel_size]) -> Tuple.duplicate(opts[:kernel_size], rank)
+        is_tuple(opts[:kernel_size]) -> opts[:kernel_size]
+        true -> raise ArgumentError, "kernel_size must be an integer or tuple"
+      end
+
+    if tuple_size(ks) != rank do
+      raise ArgumentError, "wiener: kernel_size #{inspect(ks)} must have one length per axis of the rank-#{rank} tensor"
+    end
+
+    {type, is_f64} =
+      case Nx.type(t) do
+        {:f, 32} -> {:f32, 0}
+        {:f, 64} -> {:f64, 1}
+        other -> raise ArgumentError, "wiener: f32 and f64 tensors are built, got: #{inspect(other)}"
+      end
+
+    {has_noise, noise} = if is_nil(opts[:noise]), do: {0, 0.0}, else: {1, opts[:noise] * 1.0}
+    xb = t |> Nx.to_binary()
+
+    {:ok, y} =
+      NIF.wiener(NxSignalAMD.context(), xb, is_f64, Tuple.to_list(Nx.shape(t)), Tuple.to_list(ks), has_noise, noise)
+      |> NxSignalAMD.unwrap!()
+
+    Nx.from_binary(y, type) |> Nx.reshape(Nx.shape(t))
   end
 
   defp b(true), do: 1

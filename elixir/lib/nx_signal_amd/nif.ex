@@ -45,6 +45,8 @@ defmodule NxSignalAMD.NIF do
   def fftconvolve_nd(_ctx, _a, _a_is_real, _a_shape, _b, _b_is_real, _b_shape, _mode),
   def convolve_direct(_ctx, _a, _a_is_real, _a_shape, _b, _b_is_real, _b_shape, _mode),
     do: :erlang.nif_error(:nif_not_loaded)
+  def median(_ctx, _x, _is_f64, _shape, _kernel_shape), do: :erlang.nif_error(:nif_not_loaded)
+  def wiener(_ctx, _x, _is_f64, _shape, _kernel_size, _has_noise, _noise), do: :erlang.nif_error(:nif_not_loaded)
   def stft_to_mel(_ctx, _z, _rows, _fft_length, _mel_bins, _filters), do: :erlang.nif_error(:nif_not_loaded)
 
   def stft_mel(_ctx, _x, _length, _batch, _window, _params, _mel_bins, _filters),

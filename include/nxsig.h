@@ -240,6 +240,28 @@ int nxsig_convolve_direct(nxsig_ctx* ctx, const void* a, int32_t a_is_real, cons
                           const int64_t* b_shape, int32_t rank, int32_t mode, void* out, int64_t* out_shape, int32_t mem);
 
 /*
+ * Filters.median/2 — lib/nx_signal/filters.ex:17-55: every output is the median of the window of kernel_shape that starts at
+ * min(i_d, n_d - k_d) on every axis (Nx.slice clamps its start indices: no padding, outputs near the high edge reuse the last full
+ * window).  x: f32, or f64 when is_f64 (integer tensors are converted to f64 by the caller); rank <= 8; 1 <= k_d <= n_d.  Values are
+ * ordered like np.sort (NaN above +Inf, -0.0 == +0.0, a zero median comes out +0.0).  Odd windows: the middle value; even windows:
+ * (a + b) / 2 of the two middle values in the input's type.  out: f32, the input's shape.  Dispatch: median.rows (window on the last
+ * axis, k <= 31), median.plane (last two axes, k_h, k_w <= 7), median.generic (any window) — the same bits from every tier.
+ */
+int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_shape,
+                        float* out, int32_t mem);
+
+/*
+ * Filters.wiener/2 — lib/nx_signal/filters.ex:81-110, :281-303, computed in f64: S1 / S2 = correlate(t, ones(kernel_size)) and
+ * correlate(t^2, ...) with mode :same (zero padding (k-1) - div(k-1, 2) low, div(k-1, 2) high), each accumulated from 0.0 over the window
+ * in row-major order; l_mean = S1 / size, l_var = S2 / size - l_mean^2; noise = has_noise ? noise : mean(l_var);
+ * out = l_var < noise ? l_mean : (t - l_mean) * (1 - noise / l_var) + l_mean, rounded to the input's type.  x, out: f32, or f64 when
+ * is_f64; rank <= 8; kernel_size[rank] >= 1.  noise_used (may be NULL): the noise the formula used (the estimate when !has_noise; the
+ * call then waits for the device).  The estimate's sum runs in a fixed order: the result is the same from run to run.
+ */
+int nxsig_wiener(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_size, int32_t has_noise,
+                 double noise, void* out, double* noise_used, int32_t mem);
+
+/*
  * FIR filtering: y = Convolution.convolve(x, h, method: :fft, mode:) for real 1-D x (per batch row) and
  * real taps h — lib/nx_signal/convolution.ex:252-329 as used by guides/filtering.livemd:126-128 —
  * computed by overlap-save block FFT convolution (the `Filters.fir` of BASELINE config 5; the reference

@@ -748,6 +748,52 @@ static ERL_NIF_TERM nif_convolve_direct(ErlNifEnv* env, int argc, const ERL_NIF_
                         "NxSignal.convolve/3 requires both inputs to have the same rank or one of them to be a scalar");  /* :112-115 */
 }
 
+/* filter inputs: binary of prod(shape) f32 / f64 elements, shape and window lists of one length <= 8 */
+static int filter_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], ctx_res_t** c, ErlNifBinary* in, int* is_f64, int64_t* shape, int64_t* ks,
+                       unsigned* rank, size_t* n) {
+  unsigned r2;
+  if (!get_ctx(env, argv[0], c) || !enif_inspect_binary(env, argv[1], in) || !enif_get_int(env, argv[2], is_f64) ||
+      !get_i64_list(env, argv[3], shape, 8, rank) || !get_i64_list(env, argv[4], ks, 8, &r2) || *rank < 1 || r2 != *rank)
+    return 0;
+  *n = 1;
+  for (unsigned d = 0; d < *rank; ++d)
+    if (shape[d] < 1 || !mul_size(n, (uint64_t)shape[d])) return 0;
+  return in->size % (*is_f64 ? 8 : 4) == 0 && in->size / (*is_f64 ? 8 : 4) == *n;
+}
+
+/* median(ctx, x_bin, is_f64, shape, kernel_shape) -> {:ok, f32 binary}   (Filters.median/2, lib/nx_signal/filters.ex:17-55) */
+static ERL_NIF_TERM nif_median(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, ob;
+  int is_f64;
+  int64_t shape[8], ks[8];
+  unsigned rank;
+  size_t n;
+  if (argc != 5 || !filter_args(env, argv, &c, &in, &is_f64, shape, ks, &rank, &n)) return enif_make_badarg(env);
+  if (!out_bin(&ob, n, 1, 1, 4)) return mk_oom(env);
+  int rc = nxsig_median_filter(c->ctx, in.data, is_f64, shape, (int32_t)rank, ks, (float*)ob.data, NXSIG_HOST);
+  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
+  return mk_ok(env, enif_make_binary(env, &ob));
+}
+
+/* wiener(ctx, x_bin, is_f64, shape, kernel_size, has_noise, noise) -> {:ok, binary of x's type}   (Filters.wiener/2, filters.ex:81-110) */
+static ERL_NIF_TERM nif_wiener(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, ob;
+  int is_f64, has_noise;
+  double noise;
+  int64_t shape[8], ks[8];
+  unsigned rank;
+  size_t n;
+  if (argc != 7 || !filter_args(env, argv, &c, &in, &is_f64, shape, ks, &rank, &n) || !enif_get_int(env, argv[5], &has_noise) ||
+      !get_number(env, argv[6], &noise))
+    return enif_make_badarg(env);
+  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
+  int rc = nxsig_wiener(c->ctx, in.data, is_f64, shape, (int32_t)rank, ks, has_noise, noise, ob.data, NULL, NXSIG_HOST);
+  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
+  return mk_ok(env, enif_make_binary(env, &ob));
+}
+
 /* stft_to_mel(ctx, z_bin, rows, fft_length, mel_bins, filters_bin) -> {:ok, f32[rows][mel_bins]}   (lib/nx_signal.ex:486-513) */
 static ERL_NIF_TERM nif_stft_to_mel(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
@@ -1507,6 +1553,8 @@ static ErlNifFunc funcs[] = {
     {"fft_nd", 7, nif_fft_nd, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"fftconvolve_nd", 8, nif_fftconvolve_nd, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"convolve_direct", 8, nif_convolve_direct, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"median", 5, nif_median, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"wiener", 7, nif_wiener, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_to_mel", 6, nif_stft_to_mel, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_mel", 8, nif_stft_mel, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_magnitude", 7, nif_stft_magnitude, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -107,6 +107,8 @@ SIGNATURES = {
     "nxsig_fftconvolve_nd": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _p, _i32, C.POINTER(_i64), _i32, _i32, _p, C.POINTER(_i64), _i32]),
     "nxsig_convolve_direct": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _p, _i32, C.POINTER(_i64), _i32, _i32, _p, C.POINTER(_i64), _i32]),
     "nxsig_fir_slice_f32": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _p, _i32]),
+    "nxsig_median_filter": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _p, _i32]),
+    "nxsig_wiener": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _i32, _f64, _p, C.POINTER(_f64), _i32]),
     # f64 / c128 tier
     "nxsig_window_f64": (C.c_int, [_i32, _i32, _i32, _f64, _f64, _p]),
     "nxsig_sinc_f64": (C.c_int, [_p, _i64, _p]),

@@ -48,6 +48,7 @@ UNITS = [
     ("kernels_wave_firlong.hip", []),  # 1 026 ... 32 769 taps: uniformly partitioned frequency-domain delay line (round 6)
     ("kernels_wave_packed.hip", []),
     ("kernels_f64.hip", []),  # the f64 / c128 tier (workgroup-per-frame kernels in double)
+    ("kernels_filters.hip", []),  # Filters.median / wiener (no FMA contraction: the file says so itself)
 ]
 
 

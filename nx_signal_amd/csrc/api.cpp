@@ -1402,6 +1402,79 @@ int nxsig_convolve_direct(nxsig_ctx* ctx, const void* a, int32_t a_is_real, cons
   NXSIG_API_END
 }
 
+// Filters.median / wiener: the shape checks of filters.ex (and of the Nx.slice / Nx.conv they compose), host staging as in
+// nxsig_convolve_direct
+static int filter_shape(const char* fn, const int64_t* shape, int32_t rank, const int64_t* ks, int64_t* n) {
+  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": rank must be in [1, 8]");
+  *n = 1;
+  for (int d = 0; d < rank; ++d) {
+    if (shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": empty dimension");
+    if (ks[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": window lengths must be >= 1");
+    *n *= shape[d];
+  }
+  return NXSIG_OK;
+}
+
+int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_shape,
+                        float* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!x || !out || !shape || !kernel_shape) return set_error(NXSIG_ERR_INVALID_ARG, "median: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  int64_t n = 0;
+  if ((rc = filter_shape("median", shape, rank, kernel_shape, &n))) return rc;
+  for (int d = 0; d < rank; ++d)   // Nx.slice: a window longer than its axis
+    if (kernel_shape[d] > shape[d])
+      return set_error(NXSIG_ERR_INVALID_ARG, "median: kernel_shape " + std::to_string(kernel_shape[d]) + " exceeds dimension " +
+                                                  std::to_string(shape[d]) + " of axis " + std::to_string(d));
+  if (mem == NXSIG_DEVICE) return launch_median(c, x, is_f64 != 0, shape, rank, kernel_shape, out);
+  Staged st(c);
+  const void* dx = nullptr;
+  void* dout = nullptr;
+  if ((rc = st.in(17, x, (size_t)n * (is_f64 ? 8 : 4), &dx))) return rc;
+  if ((rc = st.out_alloc(19, (size_t)n * 4, &dout))) return rc;
+  if ((rc = launch_median(c, dx, is_f64 != 0, shape, rank, kernel_shape, static_cast<float*>(dout)))) return rc;
+  return st.out_copy(out, dout, (size_t)n * 4);
+  NXSIG_API_END
+}
+
+int nxsig_wiener(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_size, int32_t has_noise,
+                 double noise, void* out, double* noise_used, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!x || !out || !shape || !kernel_size) return set_error(NXSIG_ERR_INVALID_ARG, "wiener: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  int64_t n = 0;
+  if ((rc = filter_shape("wiener", shape, rank, kernel_size, &n))) return rc;
+  const size_t bytes = (size_t)n * (is_f64 ? 8 : 4);
+  const double* noise_dev = nullptr;
+  if (mem == NXSIG_DEVICE) {
+    if ((rc = launch_wiener(c, x, is_f64 != 0, shape, rank, kernel_size, has_noise != 0, noise, out, &noise_dev))) return rc;
+  } else {
+    Staged st(c);
+    const void* dx = nullptr;
+    void* dout = nullptr;
+    if ((rc = st.in(17, x, bytes, &dx))) return rc;
+    if ((rc = st.out_alloc(19, bytes, &dout))) return rc;
+    if ((rc = launch_wiener(c, dx, is_f64 != 0, shape, rank, kernel_size, has_noise != 0, noise, dout, &noise_dev))) return rc;
+    if ((rc = st.out_copy(out, dout, bytes))) return rc;
+  }
+  if (noise_used) {
+    if (noise_dev) {
+      NXSIG_HIP_TRY(hipMemcpyAsync(noise_used, noise_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      NXSIG_HIP_TRY(hipStreamSynchronize(c->stream));
+    } else {
+      *noise_used = noise;
+    }
+  }
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
 int nxsig_fftconvolve_c64(nxsig_ctx* ctx, const nxsig_c64* a, int64_t n1, const nxsig_c64* b, int64_t n2, int32_t mode,
                           nxsig_c64* out, int32_t mem) {
   NXSIG_API_BEGIN

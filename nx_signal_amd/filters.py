@@ -1,4 +1,5 @@
-"""NxSignal.Filters.firwin/3 (lib/nx_signal/filters.ex:147-279) and the new `fir` (BASELINE config 5)."""
+"""NxSignal.Filters: median/2, wiener/2 (lib/nx_signal/filters.ex:17-110, :281-303), firwin/3 (:147-279) and the new `fir`
+(BASELINE config 5)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -6,7 +7,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, convolution
-from ._lib import ArgumentError
+from ._lib import ArgumentError, NxSignalUnsupported
+from .device import DeviceBuffer, default_context, device_view, is_device
 
 _WINDOWS = {
     "hamming": _lib.WIN_HAMMING, "hann": _lib.WIN_HANN, "blackman": _lib.WIN_BLACKMAN,
@@ -51,3 +53,103 @@ def fir(x, taps, mode="same", ctx=None):
     convolution on the GPU.  Equals Convolution.convolve(x, taps, method: :fft, mode:) of the reference
     (guides/filtering.livemd:126-128) to fp32 rounding; the reference has no streaming form."""
     return convolution.convolve(x, taps, mode=mode, method="fft", ctx=ctx)
+
+
+def _tensor(t):
+    """(host array or None, device (ptr, shape, dtype) or None) of a filter input"""
+    if is_device(t):
+        return None, device_view(t)
+    return np.asarray(t), None
+
+
+def _unknown(opts, allowed, fn):
+    unknown = [k for k in opts if k not in allowed]
+    if unknown:   # Keyword.validate!
+        raise ArgumentError(f"unknown keys {unknown} in {fn} options, the allowed keys are: {list(allowed)}")
+
+
+def median(t, ctx=None, **opts):
+    """Filters.median/2 — lib/nx_signal/filters.ex:17-55.  median(t, kernel_shape=(k_0, ..., k_{r-1})): the median of the window of
+    kernel_shape that starts at min(i_d, n_d - k_d) on every axis (no padding), as f32 of t's shape.  Host arrays of any real type
+    (integers are computed like f64) or a device tensor of f32 / f64, which gives a device tensor back.  Order like np.sort: NaN
+    above +Inf, -0.0 == +0.0; even windows average the two middle values in the input's type."""
+    _unknown(opts, ("kernel_shape",), "median")
+    ks = opts.get("kernel_shape")
+    host, dev = _tensor(t)
+    shape = tuple(host.shape) if dev is None else tuple(dev[1])
+    dtype = host.dtype if dev is None else np.dtype(dev[2])
+    if not isinstance(ks, tuple) or len(ks) != len(shape):   # filters.ex:38-40
+        raise ArgumentError("kernel shape must be of the same rank as the tensor")
+    if dtype.kind == "c":
+        raise ArgumentError("median: complex tensors have no order")
+    if dtype.kind not in "fiub":
+        raise ArgumentError(f"median: unsupported type {dtype}")
+    if not 1 <= len(shape) <= 8:
+        raise ArgumentError("median: rank must be in [1, 8]")
+    ks = tuple(int(k) for k in ks)
+    for d, (k, n) in enumerate(zip(ks, shape)):   # Nx.slice: the window must fit its axis
+        if not 1 <= k <= n:
+            raise ArgumentError(f"median: kernel_shape {k} is outside 1..{n} on axis {d}")
+    is_f64 = dtype != np.float32
+    sh = (C.c_int64 * len(shape))(*shape)
+    kc = (C.c_int64 * len(shape))(*ks)
+    lib = _lib.load()
+    if dev is not None:
+        if dtype not in (np.float32, np.float64):
+            raise ArgumentError(f"median: device tensors must be f32 or f64, got {dtype}")
+        c = t.ctx if isinstance(t, DeviceBuffer) else (ctx or default_context())
+        out = DeviceBuffer.empty(c, shape, np.float32)
+        _lib.check(lib.nxsig_median_filter(c.handle, C.c_void_p(dev[0]), int(is_f64), sh, len(shape), kc, C.c_void_p(out.ptr), _lib.DEVICE))
+        return out
+    x = np.ascontiguousarray(host, dtype=np.float64 if is_f64 else np.float32)
+    out = np.empty(shape, np.float32)
+    c = ctx or default_context()
+    _lib.check(lib.nxsig_median_filter(c.handle, x.ctypes.data_as(C.c_void_p), int(is_f64), sh, len(shape), kc,
+                                       out.ctypes.data_as(C.c_void_p), _lib.HOST))
+    return out
+
+
+def wiener(t, ctx=None, return_noise=False, **opts):
+    """Filters.wiener/2 — lib/nx_signal/filters.ex:81-110, :281-303.  wiener(t, kernel_size=3, noise=None): local mean and variance
+    over the :same-padded window in f64, then the Wiener formula; the result has t's type (f32 or f64, host or device).  noise=None
+    estimates it as the mean local variance.  return_noise=True also returns the noise the formula used."""
+    _unknown(opts, ("noise", "kernel_size"), "wiener")
+    ks = opts.get("kernel_size", 3)
+    noise = opts.get("noise")
+    host, dev = _tensor(t)
+    shape = tuple(host.shape) if dev is None else tuple(dev[1])
+    dtype = host.dtype if dev is None else np.dtype(dev[2])
+    rank = len(shape)
+    if isinstance(ks, (int, np.integer)) and not isinstance(ks, bool):
+        ks = (int(ks),) * rank
+    elif not isinstance(ks, tuple):
+        raise ArgumentError("kernel_size must be an integer or tuple")
+    if len(ks) != rank:   # Nx.conv in the reference
+        raise ArgumentError(f"wiener: kernel_size {ks} must have one length per axis of the rank-{rank} tensor")
+    ks = tuple(int(k) for k in ks)
+    if any(k < 1 for k in ks):
+        raise ArgumentError(f"wiener: kernel_size {ks} must be >= 1 on every axis")
+    if noise is not None and (isinstance(noise, bool) or not isinstance(noise, (int, float, np.integer, np.floating))):
+        raise ArgumentError(f"wiener: noise must be a number or nil, got: {noise!r}")
+    if dtype not in (np.float32, np.float64):
+        raise NxSignalUnsupported(f"wiener: f32 and f64 tensors are built, got {dtype}")
+    if not 1 <= rank <= 8:
+        raise ArgumentError("wiener: rank must be in [1, 8]")
+    is_f64 = dtype == np.float64
+    sh = (C.c_int64 * rank)(*shape)
+    kc = (C.c_int64 * rank)(*ks)
+    used = C.c_double(0.0)
+    args = (int(noise is not None), float(noise) if noise is not None else 0.0)
+    lib = _lib.load()
+    if dev is not None:
+        c = t.ctx if isinstance(t, DeviceBuffer) else (ctx or default_context())
+        out = DeviceBuffer.empty(c, shape, dtype)
+        _lib.check(lib.nxsig_wiener(c.handle, C.c_void_p(dev[0]), int(is_f64), sh, rank, kc, *args, C.c_void_p(out.ptr),
+                                    C.byref(used) if return_noise else None, _lib.DEVICE))
+    else:
+        x = np.ascontiguousarray(host)
+        out = np.empty(shape, dtype)
+        c = ctx or default_context()
+        _lib.check(lib.nxsig_wiener(c.handle, x.ctypes.data_as(C.c_void_p), int(is_f64), sh, rank, kc, *args, out.ctypes.data_as(C.c_void_p),
+                                    C.byref(used) if return_noise else None, _lib.HOST))
+    return (out, used.value) if return_noise else out
