@@ -47,6 +47,8 @@ defmodule NxSignalAMD.NIF do
     do: :erlang.nif_error(:nif_not_loaded)
   def median(_ctx, _x, _is_f64, _shape, _kernel_shape), do: :erlang.nif_error(:nif_not_loaded)
   def wiener(_ctx, _x, _is_f64, _shape, _kernel_size, _has_noise, _noise), do: :erlang.nif_error(:nif_not_loaded)
+  def argrelextrema(_ctx, _x, _dtype, _shape, _axis, _shifts, _comparator), do: :erlang.nif_error(:nif_not_loaded)
+  def nonzero(_ctx, _mask, _shape), do: :erlang.nif_error(:nif_not_loaded)
   def stft_to_mel(_ctx, _z, _rows, _fft_length, _mel_bins, _filters), do: :erlang.nif_error(:nif_not_loaded)
 
   def stft_mel(_ctx, _x, _length, _batch, _window, _params, _mel_bins, _filters),

@@ -261,6 +261,36 @@ int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int
 int nxsig_wiener(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_size, int32_t has_noise,
                  double noise, void* out, double* noise_used, int32_t mem);
 
+/* element types of nxsig_argrelextrema (narrower integers and bool are widened to s32, f16 to f32, by the caller) */
+typedef enum nxsig_dtype {
+  NXSIG_DT_F32 = 0, NXSIG_DT_F64 = 1, NXSIG_DT_S32 = 2, NXSIG_DT_S64 = 3, NXSIG_DT_U32 = 4, NXSIG_DT_U64 = 5
+} nxsig_dtype;
+
+/* the comparators of PeakFinding.argrelextrema/3 that run fused: Nx.less/2, greater/2, less_equal/2, greater_equal/2 */
+typedef enum nxsig_comparator {
+  NXSIG_CMP_LESS = 0, NXSIG_CMP_GREATER = 1, NXSIG_CMP_LESS_EQUAL = 2, NXSIG_CMP_GREATER_EQUAL = 3
+} nxsig_comparator;
+
+/*
+ * PeakFinding.argrelextrema/3 — lib/nx_signal/peak_finding.ex (argrelmin/2 = NXSIG_CMP_LESS, argrelmax/2 = NXSIG_CMP_GREATER):
+ * x[i] is marked when cmp(x[i], x[clip(i + s, 0, n - 1)]) and cmp(x[i], x[clip(i - s, 0, n - 1)]) hold for s = 1 .. shifts along
+ * `axis` (n its length; shifts = max(0, ceil(order)), so 0 marks every element).  Plain IEEE compares in the input's type: NaN
+ * compares false, -0.0 == +0.0, integers exactly.  x: dtype (nxsig_dtype) of prod(shape) elements; rank 1 .. 8, no empty dimension,
+ * fewer than 2^32 elements, every dimension below 2^31.  indices: s32 [size][rank], the coordinates of the marked elements in
+ * row-major order of their flat index (np.argwhere's order), then -1 rows; *valid: their count (u32; on the device when mem is
+ * NXSIG_DEVICE, and the call then returns without waiting).  The same bits from run to run and from every dispatch family:
+ * peaks.rows (axis is the last one), peaks.strided (any other axis), peaks.generic (NXSIG_DISABLE_PEAK_TILES).
+ */
+int nxsig_argrelextrema(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t* shape, int32_t rank, int32_t axis, int64_t shifts,
+                        int32_t comparator, int32_t* indices, uint32_t* valid, int32_t mem);
+
+/*
+ * The nonzero step of PeakFinding.argrelextrema/3 for a mask built elsewhere (a custom comparator): the coordinates of the
+ * non-zero bytes of mask (u8, prod(shape) elements) in row-major order, then -1 rows, as nxsig_argrelextrema writes them
+ * (dispatch family nonzero).  The same limits on shape and rank.
+ */
+int nxsig_nonzero(nxsig_ctx* ctx, const uint8_t* mask, const int64_t* shape, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem);
+
 /*
  * FIR filtering: y = Convolution.convolve(x, h, method: :fft, mode:) for real 1-D x (per batch row) and
  * real taps h — lib/nx_signal/convolution.ex:252-329 as used by guides/filtering.livemd:126-128 —

@@ -794,6 +794,58 @@ static ERL_NIF_TERM nif_wiener(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
   return mk_ok(env, enif_make_binary(env, &ob));
 }
 
+/* peak-finding shapes: rank 1 .. 8, no empty dimension, fewer than 2^32 elements (the library checks the rest) */
+static int peaks_shape(ErlNifEnv* env, ERL_NIF_TERM list, int64_t* shape, unsigned* rank, size_t* n) {
+  if (!get_i64_list(env, list, shape, 8, rank) || *rank < 1) return 0;
+  *n = 1;
+  for (unsigned d = 0; d < *rank; ++d)
+    if (shape[d] < 1 || !mul_size(n, (uint64_t)shape[d])) return 0;
+  return *n < ((size_t)1 << 32);
+}
+
+static ERL_NIF_TERM peaks_result(ErlNifEnv* env, int rc, ErlNifBinary* ob, uint32_t valid) {
+  if (rc) { enif_release_binary(ob); return mk_error(env, rc); }
+  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, ob), enif_make_int64(env, (int64_t)valid));
+}
+
+/* argrelextrema(ctx, x_bin, dtype, shape, axis, shifts, comparator) -> {:ok, s32 [size][rank] binary, valid}
+   (PeakFinding.argrelextrema/3, lib/nx_signal/peak_finding.ex; dtype nxsig_dtype, comparator nxsig_comparator) */
+static ERL_NIF_TERM nif_argrelextrema(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, ob;
+  int dtype, axis, comparator;
+  int64_t shape[8], shifts;
+  unsigned rank;
+  size_t n;
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !enif_get_int(env, argv[2], &dtype) ||
+      !peaks_shape(env, argv[3], shape, &rank, &n) || !enif_get_int(env, argv[4], &axis) || !enif_get_int64(env, argv[5], &shifts) ||
+      !enif_get_int(env, argv[6], &comparator) || dtype < 0 || dtype > 5)
+    return enif_make_badarg(env);
+  const size_t es = dtype == 1 || dtype == 3 || dtype == 5 ? 8 : 4;
+  if (in.size != n * es) return enif_make_badarg(env);
+  if (!out_bin(&ob, n, rank, 1, 4)) return mk_oom(env);
+  uint32_t valid = 0;
+  int rc = nxsig_argrelextrema(c->ctx, in.data, dtype, shape, (int32_t)rank, axis, shifts, comparator, (int32_t*)ob.data, &valid, NXSIG_HOST);
+  return peaks_result(env, rc, &ob, valid);
+}
+
+/* nonzero(ctx, mask_bin, shape) -> {:ok, s32 [size][rank] binary, valid}   (the compaction of argrelextrema/3 for a custom comparator's
+   u8 mask) */
+static ERL_NIF_TERM nif_nonzero(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, ob;
+  int64_t shape[8];
+  unsigned rank;
+  size_t n;
+  if (argc != 3 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !peaks_shape(env, argv[2], shape, &rank, &n) ||
+      in.size != n)
+    return enif_make_badarg(env);
+  if (!out_bin(&ob, n, rank, 1, 4)) return mk_oom(env);
+  uint32_t valid = 0;
+  int rc = nxsig_nonzero(c->ctx, in.data, shape, (int32_t)rank, (int32_t*)ob.data, &valid, NXSIG_HOST);
+  return peaks_result(env, rc, &ob, valid);
+}
+
 /* stft_to_mel(ctx, z_bin, rows, fft_length, mel_bins, filters_bin) -> {:ok, f32[rows][mel_bins]}   (lib/nx_signal.ex:486-513) */
 static ERL_NIF_TERM nif_stft_to_mel(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
@@ -1555,6 +1607,8 @@ static ErlNifFunc funcs[] = {
     {"convolve_direct", 8, nif_convolve_direct, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"median", 5, nif_median, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"wiener", 7, nif_wiener, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"argrelextrema", 7, nif_argrelextrema, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"nonzero", 3, nif_nonzero, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_to_mel", 6, nif_stft_to_mel, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_mel", 8, nif_stft_mel, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_magnitude", 7, nif_stft_magnitude, ERL_NIF_DIRTY_JOB_IO_BOUND},

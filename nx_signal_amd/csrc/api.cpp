@@ -1475,6 +1475,87 @@ int nxsig_wiener(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* s
   NXSIG_API_END
 }
 
+// PeakFinding.argrelextrema / nonzero: the port's limits, host staging as in nxsig_median_filter
+static int peaks_shape(const char* fn, const int64_t* shape, int32_t rank, int64_t* n) {
+  if (!shape) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": rank must be in [1, 8]");
+  *n = 1;
+  for (int d = 0; d < rank; ++d) {
+    if (shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": empty dimension");
+    if (shape[d] >= ((int64_t)1 << 31)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": a dimension of 2^31 or more");
+    *n *= shape[d];
+    if (*n >= ((int64_t)1 << 32)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": 2^32 or more elements");
+  }
+  return NXSIG_OK;
+}
+
+static int peaks_out(int64_t n, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem, Staged* st, int32_t** di, uint32_t** dv) {
+  if (mem == NXSIG_DEVICE) {
+    *di = indices;
+    *dv = valid;
+    return NXSIG_OK;
+  }
+  void *a = nullptr, *b = nullptr;
+  int rc = st->out_alloc(19, (size_t)n * rank * 4, &a);
+  if (rc || (rc = st->out_alloc(18, 4, &b))) return rc;
+  *di = static_cast<int32_t*>(a);
+  *dv = static_cast<uint32_t*>(b);
+  return NXSIG_OK;
+}
+
+static int peaks_copy(int64_t n, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem, Staged* st, int32_t* di, uint32_t* dv) {
+  if (mem == NXSIG_DEVICE) return NXSIG_OK;
+  int rc = st->out_copy(valid, dv, 4);
+  return rc ? rc : st->out_copy(indices, di, (size_t)n * rank * 4);
+}
+
+int nxsig_argrelextrema(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t* shape, int32_t rank, int32_t axis, int64_t shifts,
+                        int32_t comparator, int32_t* indices, uint32_t* valid, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!x || !indices || !valid) return set_error(NXSIG_ERR_INVALID_ARG, "argrelextrema: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  int64_t n = 0;
+  if ((rc = peaks_shape("argrelextrema", shape, rank, &n))) return rc;
+  if (axis < 0 || axis >= rank)
+    return set_error(NXSIG_ERR_INVALID_ARG, "argrelextrema: axis " + std::to_string(axis) + " is out of range for rank " + std::to_string(rank));
+  if (dtype < NXSIG_DT_F32 || dtype > NXSIG_DT_U64) return set_error(NXSIG_ERR_INVALID_ARG, "argrelextrema: unknown dtype");
+  if (comparator < NXSIG_CMP_LESS || comparator > NXSIG_CMP_GREATER_EQUAL) return set_error(NXSIG_ERR_INVALID_ARG, "argrelextrema: unknown comparator");
+  if (shifts < 0) shifts = 0;
+  const size_t es = dtype == NXSIG_DT_F64 || dtype == NXSIG_DT_S64 || dtype == NXSIG_DT_U64 ? 8 : 4;
+  Staged st(c);
+  const void* dx = x;
+  if (mem == NXSIG_HOST && (rc = st.in(17, x, (size_t)n * es, &dx))) return rc;
+  int32_t* di = nullptr;
+  uint32_t* dv = nullptr;
+  if ((rc = peaks_out(n, rank, indices, valid, mem, &st, &di, &dv))) return rc;
+  if ((rc = launch_argrelextrema(c, dx, dtype, shape, rank, axis, shifts, comparator, di, dv))) return rc;
+  return peaks_copy(n, rank, indices, valid, mem, &st, di, dv);
+  NXSIG_API_END
+}
+
+int nxsig_nonzero(nxsig_ctx* ctx, const uint8_t* mask, const int64_t* shape, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!mask || !indices || !valid) return set_error(NXSIG_ERR_INVALID_ARG, "nonzero: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  int64_t n = 0;
+  if ((rc = peaks_shape("nonzero", shape, rank, &n))) return rc;
+  Staged st(c);
+  const void* dm = mask;
+  if (mem == NXSIG_HOST && (rc = st.in(17, mask, (size_t)n, &dm))) return rc;
+  int32_t* di = nullptr;
+  uint32_t* dv = nullptr;
+  if ((rc = peaks_out(n, rank, indices, valid, mem, &st, &di, &dv))) return rc;
+  if ((rc = launch_nonzero(c, static_cast<const uint8_t*>(dm), shape, rank, di, dv))) return rc;
+  return peaks_copy(n, rank, indices, valid, mem, &st, di, dv);
+  NXSIG_API_END
+}
+
 int nxsig_fftconvolve_c64(nxsig_ctx* ctx, const nxsig_c64* a, int64_t n1, const nxsig_c64* b, int64_t n2, int32_t mode,
                           nxsig_c64* out, int32_t mem) {
   NXSIG_API_BEGIN

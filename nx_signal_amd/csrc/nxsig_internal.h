@@ -80,7 +80,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(STORE_POLICY) X(WAVE_NO_SPLIT) X(NO_AL8) X(NO_STAGE) X(WAVE_UNITS_PER_WAVE) X(STAGE_PAD) X(WAVE_SMALL_W) X(WAVE_SMALL_CHUNK) \
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
-  X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES)
+  X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -124,7 +124,8 @@ struct Ctx {
   // slots: 0 multi-stage temporaries, 1/2 host staging in/out, 3 wave-kernel dummy sink, 4 fused-path spectrum, 5 reduction cells,
   // 6-9 four-step / Bluestein rows, 10-12 fft_nd ping-pong, 13-15 n-D fftconvolve, 16 long-transform stft frames, 17-19 host staging of n-D calls
   // 20 istft filter fallback, 21 long FIR, 22 FIR row flags, 23 istft non-finite unit list, 24/25 packed istft fallback,
-  // 27 frames of the f64 istft, 28 wiener noise cell + per-workgroup partial sums
+  // 27 frames of the f64 istft, 28 wiener noise cell + per-workgroup partial sums, 29 peak-finding mask words + tile counts / offsets,
+  // 30 peaks.strided window extremes
   void* scratch[32] = {};
   size_t scratch_bytes[32] = {};
   // per-K tables of the tuned wave kernels (pass-B / pass-C twiddles), built once
@@ -292,6 +293,11 @@ int launch_stft_big(Ctx* c, const StftLaunch& s);
 int launch_median(Ctx* c, const void* x, bool f64, const int64_t* shape, int rank, const int64_t* ks, float* out);
 int launch_wiener(Ctx* c, const void* x, bool f64, const int64_t* shape, int rank, const int64_t* ks, bool has_noise, double noise, void* out,
                   const double** noise_dev);
+// kernels_peaks.hip: PeakFinding.argrelextrema over a device tensor (dtype: nxsig_dtype; the shape checks are the caller's) and the
+// nonzero compaction of a u8 mask; indices [size][rank] and *valid on the device, nothing waits
+int launch_argrelextrema(Ctx* c, const void* x, int dtype, const int64_t* shape, int rank, int axis, int64_t shifts, int comparator,
+                         int32_t* indices, uint32_t* valid);
+int launch_nonzero(Ctx* c, const uint8_t* mask, const int64_t* shape, int rank, int32_t* indices, uint32_t* valid);
 
 // ---- f64 / c128 tier (kernels_f64.hip) ----
 struct StftLaunchD {
