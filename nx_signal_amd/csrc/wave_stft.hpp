@@ -461,7 +461,10 @@ struct MelWaveArgs {
 // ... nt (__builtin_nontemporal_store), 2 = buffer_store ... nt.  Measured on the headline launch, interleaved in one process
 // (tools/sweep_stft.py NXSIG_STORE_POLICY 0 1 2): 5.71 / 6.00 / 5.69 TB/s — the sc1 bit (system-scope write-through) is worth
 // +5 %, the buffer addressing itself nothing.
-template <int K, int MODE, bool GENERAL, bool SCALE, int W, int J, bool NPRED, int SINK, int STG = 0, int ST = 1>
+// HOP4 (pair front-end, spectrum sink, streaming kernel): hop == fft_length / 4 is known at compile time.  Sample lane + 64 s of frame B
+// is then sample lane + 64 (s + 4) of frame A — the same address in the same lane — so frame B loads only its last four points and takes
+// the other twelve from frame A's registers: 20 loads per frame pair instead of 32.  The launcher selects it when 4 * hop == fft_length.
+template <int K, int MODE, bool GENERAL, bool SCALE, int W, int J, bool NPRED, int SINK, int STG = 0, int ST = 1, bool HOP4 = false>
 __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveArgs* mp) {
   // STG > 0 (quad streaming kernels): the unit's contiguous input span travels as STG 16-byte loads per lane and is
   // re-distributed through the wave's exchange buffer instead of 32 strided 4-byte loads per lane (see issue_loads)
@@ -488,6 +491,11 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
   constexpr int TWQ = (J - 1) * (K / J);  // quad-mode separation twiddles conj(w_K^(j k0)), j = 1..J-1
   constexpr int kWavesPerBlock = W;
   constexpr int kWaveThreads = 64 * W;
+  // the headline launch (pair front-end, spectrum sink, streaming kernel, hop = fft_length / 4, four waves per workgroup) has a loop and a
+  // start-up of its own, see below.  Only that family has been timed against the loop every other instantiation keeps (the one-round
+  // 12-wave geometry, other hops, the plain-nt store policy): they stay on it until they have been.
+  constexpr bool PAIRLOOP = MODE == kModePair && SINK == kSinkSpectrum && !GENERAL && HOP4;
+  static_assert(!HOP4 || (PAIRLOOP && !NPRED && K == 1024 && W == 4), "HOP4 is an instantiation of the pair streaming kernel");
 
   // ---- LDS carve: [window KOUT f32][twB 256 c64][twC R3*256 c64][twR K c64 (real-2x)][W x exchange]
   float* s_w = reinterpret_cast<float*>(g_wave_smem);
@@ -503,8 +511,9 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
 #else
   auto stamp = [] {};
 #endif
-  // the tables are staged (and the workgroup's only barrier passed) AFTER the first unit's sample loads have been issued, see
-  // below: the two memory round trips of a workgroup's start-up overlap (a short launch is mostly start-up: config 2 as written)
+  // PAIRLOOP: the tables are staged (and the workgroup's only barrier passed) AFTER the first unit's sample loads have been issued, see
+  // tables_issue / tables_commit: the memory round trips of a workgroup's start-up overlap (a short launch is mostly start-up:
+  // config 2 as written)
   float* s_csr = reinterpret_cast<float*>(s_x + W * XCH);
   int* s_off = reinterpret_cast<int*>(s_csr + (MEL ? mp->nnz : 0));
   int* s_lo = s_off + (MEL ? mp->mel_bins + 1 : 0);
@@ -528,6 +537,33 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
       for (int i = tid; i < mp->mel_bins; i += kWaveThreads) s_lo[i] = mp->csr_lo[i];
     }
     __syncthreads();  // the only workgroup barrier: tables are read-only afterwards
+  };
+  // PAIRLOOP: window, twB and twC lie back to back in LDS (14 KB at K = 1024) and each source is a hipMalloc'ed table of its own, so the
+  // preload is a copy of NT4 16-byte pieces.  Every piece of a thread is in flight before the first wait (the loops above are one
+  // memory round trip per trip: nine in a row for 256 threads), and the first unit's sample loads are issued behind them, before that
+  // wait: a workgroup's start-up is one round trip deep.  No branch anywhere in it (threads past the last piece copy the last piece
+  // once more): at a join the wait-count pass forgets how many younger loads are behind the table loads and drains them all.
+  // (what the copy relies on: the three sources are 16-byte aligned — each is a device allocation of its own, ensure_wave_tables /
+  // ctx_window — and the carve above keeps window, twB, twC adjacent in this order with the pair front-end's s_twR empty behind them)
+  constexpr int NW4 = KOUT / 4, NB4 = 128, NT4 = NW4 + NB4 + R3 * 128;
+  static_assert(!PAIRLOOP || (KOUT % 4 == 0 && (size_t)NT4 * 16 == (size_t)KOUT * sizeof(float) + (256 + R3 * 256) * sizeof(v2f)),
+                "table preload: the 16-byte pieces must cover exactly [window KOUT f32][twB 256 c64][twC R3*256 c64] of the LDS carve");
+  constexpr int TPT = PAIRLOOP ? (NT4 + kWaveThreads - 1) / kWaveThreads : 1;
+  v4f tq[TPT];
+  auto table_piece = [&](int j) { const int i = tid + j * kWaveThreads; return i < NT4 ? i : NT4 - 1; };
+  auto tables_issue = [&]() {
+#pragma unroll
+    for (int j = 0; j < TPT; ++j) {
+      const int i = table_piece(j);
+      const v4f* src = i < NW4 ? reinterpret_cast<const v4f*>(a.wtab) + i
+                               : (i < NW4 + NB4 ? reinterpret_cast<const v4f*>(a.twB) + (i - NW4) : reinterpret_cast<const v4f*>(a.twC) + (i - NW4 - NB4));
+      tq[j] = *src;
+    }
+  };
+  auto tables_commit = [&]() {
+#pragma unroll
+    for (int j = 0; j < TPT; ++j) reinterpret_cast<v4f*>(g_wave_smem)[table_piece(j)] = tq[j];
+    __syncthreads();  // the only workgroup barrier
   };
   v2f* xb = s_x + wave * XCH;
   // MEL: after the core the exchange buffer is idle: |X|^2 of frame f of the unit at mags[f * KOUT/2 + k], k < KOUT/2
@@ -586,9 +622,13 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
 
   // Streaming kernels are software-pipelined one pair deep.  Iteration i: issue the raw loads of pair i+1 ->
   // FFT passes of pair i -> multiply the (long since landed) samples of pair i+1 by the window -> untangle and
-  // store pair i.  The loads are consumed BEFORE this pair's stores are issued, so the only VMEM ops ahead of
-  // them in gfx9's in-order queue are the previous iteration's stores (a whole iteration old): no wait ever
-  // drains fresh stores, and HBM latency hides under the butterflies.
+  // store pair i.  As written the loads are consumed BEFORE this pair's stores are issued; the compiler sinks the
+  // window products of the pair kernel behind the stores (the products are not needed before the next trip), and
+  // the waits in front of them then count the 16 fresh stores in: they end at vmcnt(16) — every load landed, every
+  // store of the pair still in flight.  What must not happen is a wait BELOW the stores of the pair: it drains
+  // them and leaves the wave with nothing in flight across the next pair's butterflies.  The wait-count pass
+  // inserts exactly that at the joins of any cold route with loads or stores of its own inside the loop, see
+  // PAIRLOOP below (tests/test_stft_pair_loop_isa.py reads it off the assembly).
   float ra[STAGED ? 1 : P], rb[STAGED ? 1 : P];
   v4f rs[STAGED ? NST : 1];
   constexpr int FPU_IN = MODE == kModeQuad ? 2 * J : 2;  // frames per unit
@@ -597,6 +637,7 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
   // back to strided 4-byte gathers, 0.49 against 0.61-0.68 of the roofline for N = 512 / 256 / 128)
   const int span4 = STAGED ? ((((FPU_IN - 1) * a.hop + KOUT + 3) & ~3) + (HQP ? 0 : 4)) : 0;
   int mis = 0;
+  uint32_t ld_bmask = ~0u;  // HOP4: all ones when the unit in ra[] / rb[] has a real frame B, 0 for the phantom B of an odd tail (wave-uniform)
   auto issue_loads = [&](int64_t row, int64_t pin) {
     if (STAGED) {
       // the unit's frames 2J pin .. 2J pin + 2J - 1 read x[unit start .. + span): one contiguous run
@@ -610,8 +651,16 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
       const int64_t mA = pin * 2;
       const float* pa = a.x + (size_t)row * a.batch_stride + (mA * a.hop - a.lo) + lane;
       const float* pb = pa + ((mA + 1 < a.M) ? a.hop : 0);  // phantom frame B of an odd tail: reload A, never stored
+      if constexpr (HOP4) {
+        ld_bmask = (mA + 1 < a.M) ? ~0u : 0u;   // window_mul picks frame B's first P - 4 points out of ra[] (the phantom B stays a copy of A: same bits)
 #pragma unroll
-      for (int s = 0; s < P; ++s) { ra[s] = pa[64 * s]; rb[s] = pb[64 * s]; }
+        for (int s = 0; s < P; ++s) ra[s] = pa[64 * s];
+#pragma unroll
+        for (int s = P - 4; s < P; ++s) rb[s] = pb[64 * s];
+      } else {
+#pragma unroll
+        for (int s = 0; s < P; ++s) { ra[s] = pa[64 * s]; rb[s] = pb[64 * s]; }
+      }
     } else if (MODE == kModeReal2x) {  // complex point n = (x[2n], x[2n+1])
       const float* pa = a.x + (size_t)row * a.batch_stride + (pin * a.hop - a.lo) + 2 * lane;
       if (STG == 2) {  // every frame starts on an 8-byte boundary (checked by the launcher): one 8-byte load per point
@@ -676,7 +725,9 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
       // reach the transform even as 0 * x, which would turn an Inf / NaN outside the frame into NaN
       if (MODE == kModePair) {
         const float w = s_w[lane + 64 * s];
-        d[s] = v2f{ra[s] * w, rb[s] * w};
+        // (a bit-select with a wave-uniform mask, one v_bfi_b32: a ?: on two array elements becomes an indexed read of a scratch copy)
+        const float vb = (HOP4 && s + 4 < P) ? __uint_as_float((__float_as_uint(ra[(s + 4) % P]) & ld_bmask) | (__float_as_uint(ra[s]) & ~ld_bmask)) : rb[s];
+        d[s] = v2f{ra[s] * w, vb * w};
         if (NPRED && lane + 64 * s >= a.N) d[s] = v2f{0.f, 0.f};
       } else if (MODE == kModeReal2x) {
         const v2f w = *reinterpret_cast<const v2f*>(&s_w[2 * (lane + 64 * s)]);
@@ -694,8 +745,10 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
   // A launch covers units_per_row of each row's pairs_per_row units: the interior ones (every sample of every frame
   // inside the signal: the streaming kernels) or the few edge ones (GENERAL).  unit index u -> unit-in-row:
   auto pinof = [&](int64_t u) { return u + (u < a.u_split ? a.u_add0 : a.u_add1); };
-  int64_t row = (p_begin + wave) / a.units_per_row;
-  int64_t uin = (p_begin + wave) - row * a.units_per_row;
+  // (PAIRLOOP: a wave of the last workgroup that has no unit loads the launch's last one all the same and never uses it, see the start-up)
+  const int64_t u_first = (PAIRLOOP && p_begin + wave >= a.total_pairs) ? a.total_pairs - 1 : p_begin + wave;
+  int64_t row = u_first / a.units_per_row;
+  int64_t uin = u_first - row * a.units_per_row;
   int64_t nrow = row, nuin = uin;
   auto advance = [&](int64_t& r, int64_t& q) {
     q += kWavesPerBlock;
@@ -705,9 +758,16 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
   v2f d[P];  // windowed samples of the current pair: re = frame A, im = frame B (exact f32 products, :101)
   const bool have_first = !GENERAL && p_begin + wave < p_end;
   stamp();
-  stage_tables();
-  stamp();
-  if (have_first) issue_loads(row, pinof(uin));
+  if constexpr (PAIRLOOP) {
+    tables_issue();
+    issue_loads(row, pinof(uin));
+    __builtin_amdgcn_sched_barrier(0);
+    tables_commit();
+  } else {
+    stage_tables();
+    stamp();
+    if (have_first) issue_loads(row, pinof(uin));
+  }
   if (have_first) window_mul(d);
   stamp();
 
@@ -875,7 +935,9 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
       const int64_t m0 = SOLO ? mS : mA;
       v2f* zA = a.z + ((size_t)crow * a.M + m0) * KOUT + 2 * lane;
       v2f* zB = (GENERAL || haveB) ? zA + K : a.dummy + 2 * lane;  // pair: frame B; real-2x: bins K..2K-1
-      constexpr bool BUFST = ST > 0 && (MODE == kModePair || MODE == kModeReal2x) && !GENERAL && SINK == kSinkSpectrum && !SOLO;
+      // (PAIRLOOP: the solo route re-stores frames the paired route has stored already, see the loop: the same kind of store, so that
+      // the wave's stores to one address stay in one queue)
+      constexpr bool BUFST = ST > 0 && (MODE == kModePair || MODE == kModeReal2x) && !GENERAL && SINK == kSinkSpectrum && (!SOLO || PAIRLOOP);
       __amdgpu_buffer_rsrc_t rsA, rsB;
       if (BUFST) {  // wave-uniform row descriptors (the row base depends on the wave index: make it an SGPR pair explicitly)
         auto uni = [](const v2f* p) -> void* {
@@ -946,7 +1008,7 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
           typedef int v4i __attribute__((ext_vector_type(4)));
           constexpr int AUX = ST == 1 ? 18 : 2;  // gfx940+ cache policy bits: 1 = sc0, 2 = nt, 16 = sc1
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, xa), rsA, lane * 16 + 1024 * q, 0, AUX);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, xbv), rsB, lane * 16 + 1024 * q, 0, AUX);
+          if (!SOLO) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i, xbv), rsB, lane * 16 + 1024 * q, 0, AUX);
         } else {
           __builtin_nontemporal_store(xa, (gv4f*)(zA + 128 * q));
           if (!SOLO && (!GENERAL || haveB)) __builtin_nontemporal_store(xbv, (gv4f*)(zB + 128 * q));
@@ -956,6 +1018,73 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
     return SPEC && __builtin_amdgcn_ballot_w64(amin <= kFftEps) != 0;
   };
 
+  if constexpr (PAIRLOOP) {
+    // ---- the headline loop.  Nothing of a cold path lives in its control flow: a load or a store on a rarely taken route makes the
+    // compiler's wait-count pass merge conservatively at the joins, and the loop then DRAINED every unit's 16 fresh stores before the
+    // next unit's loads were issued (s_waitcnt vmcnt(1) behind the stores, vmcnt(0) at the latch).  So
+    //  - the paired route always runs.  A wave-uniform mask records which of the wave's units held a non-finite sample, and those
+    //    units are redone frame by frame AFTER the loop (load_solo + drain(SOLO)): the wave's own later stores to the same addresses
+    //    land after the earlier ones, as the eps re-drain's do.  A non-finite sample still reaches exactly the frames that contain it;
+    //  - the wave's last unit is peeled: it prefetches nothing and multiplies nothing by the window.  (One body with two wave-uniform
+    //    branches instead keeps the consumed d[] live across window_mul on the other path: 172 VGPRs, two waves per SIMD.  Peeled:
+    //    160 VGPRs, 27.4 KB of code against 17.6 KB, well inside the instruction cache.)
+    // What is in flight across a unit's butterflies: its predecessor's 16 stores and its successor's loads.
+    // nfmask bit min(k, 63) = the wave's k-th unit.  Bit 63 SATURATES: with more than 64 units per wave (NXSIG_WAVE_UNITS_PER_WAVE or a
+    // forced one-round chunk allow it; no default geometry comes near) one non-finite unit from the 63rd on sends every later unit of
+    // the wave through the solo route as well.  That is correct — the solo route computes any frame — but a finite unit redone alone
+    // differs from the paired result by fp32 round-off (tests/test_gpu_reference_numerics.py, solo_route_equals_the_paired_route).
+    unsigned long long nfmask = 0;
+    int k = 0;
+    auto transform = [&](v2f (*zz)[NQ]) {
+      if (unit_nonfinite(d)) nfmask |= 1ull << (k < 63 ? k : 63);
+      wave_fft_core<K>(d, zz, xb, s_twB, s_twC, lane);
+    };
+    auto drain_unit = [&](v2f (*zz)[NQ]) {
+      const int64_t mA = pinof(uin) * 2;
+      const bool haveB = mA + 1 < a.M;
+      if (drain(std::false_type{}, std::true_type{}, zz, row, mA, haveB, mA))
+        drain(std::false_type{}, std::false_type{}, zz, row, mA, haveB, mA);   // cold: the unit again, with the clean-up
+    };
+    int64_t pr = p_begin + wave;
+    for (; pr + kWavesPerBlock < p_end; pr += kWavesPerBlock, ++k) {   // every unit of the wave but its last
+      v2f zz[2][NQ];
+      issue_loads(nrow, pinof(nuin));
+      __builtin_amdgcn_sched_barrier(0);
+      transform(zz);
+      __builtin_amdgcn_sched_barrier(0);
+      window_mul(d);
+      __builtin_amdgcn_sched_barrier(0);
+      drain_unit(zz);
+      row = nrow; uin = nuin;
+      advance(nrow, nuin);
+      stamp();
+    }
+    if (pr < p_end) {
+      v2f zz[2][NQ];
+      transform(zz);
+      drain_unit(zz);
+      stamp();
+    }
+    if (nfmask != 0) {  // cold: the non-finite units again, every frame alone through the core
+      row = (p_begin + wave) / a.units_per_row;
+      uin = (p_begin + wave) - row * a.units_per_row;
+      k = 0;
+      for (int64_t pr = p_begin + wave; pr < p_end; pr += kWavesPerBlock, ++k) {
+        if ((nfmask >> (k < 63 ? k : 63)) & 1) {
+          const int64_t mA = pinof(uin) * 2;
+#pragma nounroll
+          for (int f = 0; f < 2 && mA + f < a.M; ++f) {
+            v2f ds[P], zz[2][NQ];
+            load_solo(ds, row, mA + f);
+            wave_fft_core<K>(ds, zz, xb, s_twB, s_twC, lane);
+            drain(std::true_type{}, std::false_type{}, zz, row, mA, true, mA + f);
+          }
+        }
+        advance(row, uin);
+      }
+    }
+    return;
+  }
   for (int64_t pr = p_begin + wave; pr < p_end; pr += kWavesPerBlock) {
     const int64_t pin = pinof(uin);
     const int64_t mA = MODE == kModePair ? pin * 2 : (MODE == kModeQuad ? pin * (2 * J) : pin), mB = mA + 1;
@@ -1020,9 +1149,9 @@ __device__ __forceinline__ void stft_wave_body(const WaveArgs& a, const MelWaveA
   }
 }
 
-template <int K, int MODE, bool GENERAL, bool SCALE, int W, int J = 2, bool NPRED = false, int STG = 0, int ST = 1>
+template <int K, int MODE, bool GENERAL, bool SCALE, int W, int J = 2, bool NPRED = false, int STG = 0, int ST = 1, bool HOP4 = false>
 __global__ __launch_bounds__(64 * W) void k_stft_wave(WaveArgs a) {
-  stft_wave_body<K, MODE, GENERAL, SCALE, W, J, NPRED, kSinkSpectrum, STG, ST>(a, nullptr);
+  stft_wave_body<K, MODE, GENERAL, SCALE, W, J, NPRED, kSinkSpectrum, STG, ST, HOP4>(a, nullptr);
 }
 template <int K, int MODE, bool GENERAL, bool SCALE, int W, int J = 2, bool NPRED = false, int STG = 0>
 __global__ __launch_bounds__(64 * W) void k_stft_mel_wave(MelWaveArgs m) {
@@ -1534,6 +1663,7 @@ static int launch_wave(Ctx* c, const StftLaunch& s, const MelLaunch* mel = nullp
     return launch_mel_finish(c, mel->out, (int64_t)s.batch * s.fr.M * mel->mel_bins, m.gmax);
   }
   if constexpr (SINK == kSinkSpectrum) {
+  bool took_hop4 = false;
   {  // interior units u_lo .. u_hi-1
     const int64_t upr = u_hi - u_lo, big = (int64_t)1 << 62;
     bool done = false;
@@ -1573,6 +1703,18 @@ static int launch_wave(Ctx* c, const StftLaunch& s, const MelLaunch* mel = nullp
       // NXSIG_STORE_POLICY forces one (0 / 1 / 2).
       const int64_t out_bytes = (int64_t)s.batch * s.fr.M * KOUT * 8;
       const int stp = tune(c, kT_STORE_POLICY, (out_bytes > ((int64_t)150 << 20) && out_bytes <= ((int64_t)2200 << 20)) ? 0 : 1);
+      // hop == fft_length / 4 (the default 75 % overlap): the instantiation whose frame B reuses frame A's registers (HOP4, 20 loads per
+      // frame pair instead of 32).  NXSIG_NO_HOP4=1 keeps such a call on the kernel every other hop takes (A/B, bit-equality test).
+      // Taken by the four-wave geometry with the "sc1 nt" store policy only: what has been measured (profiles/r07/stft_pair_loop/).
+      if constexpr (W == 4) {
+        const bool hop4 = 4 * s.fr.hop == KOUT && !tune(c, kT_NO_HOP4, 0);
+        if (!done && !npred && hop4 && stp == 1) {
+          done = true;
+          took_hop4 = upr > 0;
+          rc = scale ? go(k_stft_wave<C, MODE, false, true, W, J, false, 0, 1, true>, upr, big, u_lo, u_lo)
+                     : go(k_stft_wave<C, MODE, false, false, W, J, false, 0, 1, true>, upr, big, u_lo, u_lo);
+        }
+      }
       if (!done && !npred && (stp == 0 || stp == 2)) {
         done = true;
         if (stp == 0) rc = scale ? go(k_stft_wave<C, MODE, false, true, W, J, false, 0, 0>, upr, big, u_lo, u_lo)
@@ -1594,6 +1736,8 @@ static int launch_wave(Ctx* c, const StftLaunch& s, const MelLaunch* mel = nullp
     rc = scale ? go(k_stft_wave<C, MODE, true, true, W, J>, upr, u_lo, 0, u_hi - u_lo)
                : go(k_stft_wave<C, MODE, true, false, W, J>, upr, u_lo, 0, u_hi - u_lo);
   }
+  // trails the families of the call (a record's named families lead it): the interior units ran the hop-specialised instantiation
+  if (!rc && took_hop4) dispatch_note("stft.pair.h4");
   return rc;
   }
   return NXSIG_OK;
