@@ -49,6 +49,12 @@ defmodule NxSignalAMD.NIF do
   def wiener(_ctx, _x, _is_f64, _shape, _kernel_size, _has_noise, _noise), do: :erlang.nif_error(:nif_not_loaded)
   def argrelextrema(_ctx, _x, _dtype, _shape, _axis, _shifts, _comparator), do: :erlang.nif_error(:nif_not_loaded)
   def nonzero(_ctx, _mask, _shape), do: :erlang.nif_error(:nif_not_loaded)
+  def sawtooth(_ctx, _t, _is_f64, _width), do: :erlang.nif_error(:nif_not_loaded)
+  def square(_ctx, _t, _is_f64, _duty, _duty_tensor), do: :erlang.nif_error(:nif_not_loaded)
+  def gaussian_pulse(_ctx, _t, _is_f64, _center_frequency, _bandwidth, _reference_level), do: :erlang.nif_error(:nif_not_loaded)
+  def chirp(_ctx, _t, _is_f64, _f0_t1_f1, _method, _vertex_zero, _phi), do: :erlang.nif_error(:nif_not_loaded)
+  def polynomial_sweep(_ctx, _t, _is_f64, _coefs, _phi, _phi_degrees), do: :erlang.nif_error(:nif_not_loaded)
+  def unit_impulse(_ctx, _dtype, _shape, _index), do: :erlang.nif_error(:nif_not_loaded)
   def stft_to_mel(_ctx, _z, _rows, _fft_length, _mel_bins, _filters), do: :erlang.nif_error(:nif_not_loaded)
 
   def stft_mel(_ctx, _x, _length, _batch, _window, _params, _mel_bins, _filters),

@@ -292,6 +292,50 @@ int nxsig_argrelextrema(nxsig_ctx* ctx, const void* x, int32_t dtype, const int6
 int nxsig_nonzero(nxsig_ctx* ctx, const uint8_t* mask, const int64_t* shape, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem);
 
 /*
+ * NxSignal.Waveforms — lib/nx_signal/waveforms.ex.  t: n elements, f32, or f64 when is_f64; the results have
+ * t's type unless stated.  f32: every Nx op is evaluated in double on f32 operands and rounded to f32 (the reference's literals come
+ * out bit for bit); f64: the same expressions unrounded.  pi() is the f32 constant in both.  mem: NXSIG_HOST or NXSIG_DEVICE for every
+ * tensor pointer; device calls return without waiting; n == 0 returns NXSIG_OK and launches nothing.  A device pointer needs only the
+ * alignment of its element type.  Dispatch families: waveform.<function> (waveform.chirp.<method>).
+ */
+
+/* sawtooth/2 — waveforms.ex:29-54: tmod = fmod(t, 2 pi()); width == 1: tmod / (pi() width) - 1; width == 0: the falling ramp;
+ * otherwise a select on tmod < 2 pi() width.  width outside [0, 1] (or NaN): NXSIG_ERR_INVALID_ARG (:34-36). */
+int nxsig_sawtooth(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double width, void* out, int32_t mem);
+
+/* square/2 — waveforms.ex:96-104: fmod(t, 2 pi()) < duty * 2 * pi() ? 1 : -1 as s32.  duty_tensor (n elements of t's type, same mem)
+ * replaces the scalar duty when it is not NULL. */
+int nxsig_square(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double duty, const void* duty_tensor, int32_t* out, int32_t mem);
+
+/* gaussian_pulse/2 — waveforms.ex:161-198: envelope = exp(-a t^2), in_phase = envelope cos(2 pi() fc t), quadrature = envelope
+ * sin(2 pi() fc t), a = -(pi fc bw)^2 / (4 log(10^(bwr / 20))); one pass writes the three outputs, which must not overlap.
+ * fc < 0, bw <= 0, bwr >= 0: NXSIG_ERR_INVALID_ARG (:173-186). */
+int nxsig_gaussian_pulse(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double center_frequency, double bandwidth,
+                         double bandwidth_reference_level, void* envelope, void* in_phase, void* quadrature, int32_t mem);
+
+/* the :method of chirp/5 */
+typedef enum nxsig_chirp_method {
+  NXSIG_CHIRP_LINEAR = 0, NXSIG_CHIRP_QUADRATIC = 1, NXSIG_CHIRP_LOGARITHMIC = 2, NXSIG_CHIRP_HYPERBOLIC = 3
+} nxsig_chirp_method;
+
+/* chirp/5 — waveforms.ex:249-289: cos(phase + phi), phase by method (:254-285; vertex_zero only matters to NXSIG_CHIRP_QUADRATIC).
+ * :logarithmic with f0 f1 <= 0 gives NaN everywhere, f0 == f1 of :logarithmic / :hyperbolic is 2 pi() f0 t.  An unknown method:
+ * NXSIG_ERR_INVALID_ARG (:291-300). */
+int nxsig_chirp(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double f0, double t1, double f1, int32_t method, int32_t vertex_zero,
+                double phi, void* out, int32_t mem);
+
+#define NXSIG_SWEEP_MAX_COEFS 32
+/* polynomial_sweep/3 — waveforms.ex:343-361: cos(2 pi() sum_k (coefs[k] / (n - k)) t^(n - k) + phi), coefs (host, ncoefs in
+ * [1, NXSIG_SWEEP_MAX_COEFS]) from the highest power down, the sum in f64 rounded once; phi in degrees when phi_degrees (:354-358). */
+int nxsig_polynomial_sweep(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, const double* coefs, int32_t ncoefs, double phi,
+                           int32_t phi_degrees, void* out, int32_t mem);
+
+/* unit_impulse/2 — waveforms.ex:406-437: prod(shape) zeros of dtype (nxsig_dtype) and a single one at index (rank entries, host; the
+ * caller resolves :midpoint and a scalar index); rank 0 .. 8.  An empty dimension gives NXSIG_OK and writes nothing.  An index
+ * outside the shape is NXSIG_ERR_INVALID_ARG (a deliberate deviation: what Nx.indexed_put does with it is not specified here). */
+int nxsig_unit_impulse(nxsig_ctx* ctx, int32_t dtype, const int64_t* shape, int32_t rank, const int64_t* index, void* out, int32_t mem);
+
+/*
  * FIR filtering: y = Convolution.convolve(x, h, method: :fft, mode:) for real 1-D x (per batch row) and
  * real taps h — lib/nx_signal/convolution.ex:252-329 as used by guides/filtering.livemd:126-128 —
  * computed by overlap-save block FFT convolution (the `Filters.fir` of BASELINE config 5; the reference

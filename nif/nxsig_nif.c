@@ -846,6 +846,119 @@ static ERL_NIF_TERM nif_nonzero(ErlNifEnv* env, int argc, const ERL_NIF_TERM arg
   return peaks_result(env, rc, &ob, valid);
 }
 
+/* NxSignal.Waveforms (lib/nx_signal/waveforms.ex): t_bin holds f32 elements, or f64 when is_f64; results are binaries of t's type */
+static int wave_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], ctx_res_t** c, ErlNifBinary* in, int* is_f64, size_t* n) {
+  if (!get_ctx(env, argv[0], c) || !enif_inspect_binary(env, argv[1], in) || !enif_get_int(env, argv[2], is_f64)) return 0;
+  const size_t es = *is_f64 ? 8 : 4;
+  *n = in->size / es;
+  return in->size % es == 0;
+}
+
+static ERL_NIF_TERM wave_result(ErlNifEnv* env, int rc, ErlNifBinary* ob) {
+  if (rc) { enif_release_binary(ob); return mk_error(env, rc); }
+  return mk_ok(env, enif_make_binary(env, ob));
+}
+
+/* sawtooth(ctx, t_bin, is_f64, width) -> {:ok, binary}   (Waveforms.sawtooth/2, waveforms.ex:29-54) */
+static ERL_NIF_TERM nif_sawtooth(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, ob;
+  int is_f64;
+  size_t n;
+  double width;
+  if (argc != 4 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !get_number(env, argv[3], &width)) return enif_make_badarg(env);
+  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
+  return wave_result(env, nxsig_sawtooth(c->ctx, in.data, is_f64, (int64_t)n, width, ob.data, NXSIG_HOST), &ob);
+}
+
+/* square(ctx, t_bin, is_f64, duty, duty_bin) -> {:ok, s32 binary}   (Waveforms.square/2, waveforms.ex:96-104; a duty_bin of t's size
+   replaces the number, an empty one means the number) */
+static ERL_NIF_TERM nif_square(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, duty, ob;
+  int is_f64;
+  size_t n;
+  double d;
+  if (argc != 5 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !get_number(env, argv[3], &d) || !enif_inspect_binary(env, argv[4], &duty) ||
+      (duty.size != 0 && duty.size != in.size))
+    return enif_make_badarg(env);
+  if (!out_bin(&ob, n, 1, 1, 4)) return mk_oom(env);
+  return wave_result(env, nxsig_square(c->ctx, in.data, is_f64, (int64_t)n, d, duty.size ? duty.data : NULL, (int32_t*)ob.data, NXSIG_HOST), &ob);
+}
+
+/* gaussian_pulse(ctx, t_bin, is_f64, center_frequency, bandwidth, bandwidth_reference_level) -> {:ok, envelope, in_phase, quadrature}
+   (Waveforms.gaussian_pulse/2, waveforms.ex:161-198) */
+static ERL_NIF_TERM nif_gaussian_pulse(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, b0, b1, b2;
+  int is_f64;
+  size_t n;
+  double fc, bw, bwr;
+  if (argc != 6 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !get_number(env, argv[3], &fc) || !get_number(env, argv[4], &bw) ||
+      !get_number(env, argv[5], &bwr))
+    return enif_make_badarg(env);
+  const size_t es = is_f64 ? 8 : 4;
+  if (!out_bin(&b0, n, 1, 1, es)) return mk_oom(env);
+  if (!out_bin(&b1, n, 1, 1, es)) { enif_release_binary(&b0); return mk_oom(env); }
+  if (!out_bin(&b2, n, 1, 1, es)) { enif_release_binary(&b0); enif_release_binary(&b1); return mk_oom(env); }
+  int rc = nxsig_gaussian_pulse(c->ctx, in.data, is_f64, (int64_t)n, fc, bw, bwr, b0.data, b1.data, b2.data, NXSIG_HOST);
+  if (rc) { enif_release_binary(&b0); enif_release_binary(&b1); enif_release_binary(&b2); return mk_error(env, rc); }
+  return enif_make_tuple4(env, mk_atom(env, "ok"), enif_make_binary(env, &b0), enif_make_binary(env, &b1), enif_make_binary(env, &b2));
+}
+
+/* chirp(ctx, t_bin, is_f64, {f0, t1, f1}, method, vertex_zero, phi) -> {:ok, binary}   (Waveforms.chirp/5, waveforms.ex:249-300;
+   method nxsig_chirp_method) */
+static ERL_NIF_TERM nif_chirp(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, ob;
+  int is_f64, method, vertex_zero, arity;
+  size_t n;
+  const ERL_NIF_TERM* e;
+  double f0, t1, f1, phi;
+  if (argc != 7 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !enif_get_tuple(env, argv[3], &arity, &e) || arity != 3 ||
+      !get_number(env, e[0], &f0) || !get_number(env, e[1], &t1) || !get_number(env, e[2], &f1) || !enif_get_int(env, argv[4], &method) ||
+      !enif_get_int(env, argv[5], &vertex_zero) || !get_number(env, argv[6], &phi))
+    return enif_make_badarg(env);
+  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
+  return wave_result(env, nxsig_chirp(c->ctx, in.data, is_f64, (int64_t)n, f0, t1, f1, method, vertex_zero, phi, ob.data, NXSIG_HOST), &ob);
+}
+
+/* polynomial_sweep(ctx, t_bin, is_f64, coefs_f64_bin, phi, phi_degrees) -> {:ok, binary}   (Waveforms.polynomial_sweep/3,
+   waveforms.ex:343-361) */
+static ERL_NIF_TERM nif_polynomial_sweep(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary in, cf, ob;
+  int is_f64, degrees;
+  size_t n;
+  double phi, coefs[NXSIG_SWEEP_MAX_COEFS];
+  if (argc != 6 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !enif_inspect_binary(env, argv[3], &cf) || cf.size % 8 != 0 ||
+      !get_number(env, argv[4], &phi) || !enif_get_int(env, argv[5], &degrees))
+    return enif_make_badarg(env);
+  const size_t nc = cf.size / 8;
+  if (nc <= NXSIG_SWEEP_MAX_COEFS) memcpy(coefs, cf.data, cf.size);   /* a sub-binary need not be 8-byte aligned */
+  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
+  return wave_result(env, nxsig_polynomial_sweep(c->ctx, in.data, is_f64, (int64_t)n, coefs, nc > NXSIG_SWEEP_MAX_COEFS ? -1 : (int32_t)nc, phi,
+                                                 degrees, ob.data, NXSIG_HOST), &ob);
+}
+
+/* unit_impulse(ctx, dtype, shape, index) -> {:ok, binary}   (Waveforms.unit_impulse/2, waveforms.ex:406-437; dtype nxsig_dtype, index
+   one entry per axis) */
+static ERL_NIF_TERM nif_unit_impulse(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary ob;
+  int dtype;
+  int64_t shape[8], index[8];
+  unsigned rank, r2;
+  size_t n = 1;
+  if (argc != 4 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[1], &dtype) || dtype < 0 || dtype > 5 ||
+      !get_i64_list(env, argv[2], shape, 8, &rank) || !get_i64_list(env, argv[3], index, 8, &r2) || r2 != rank)
+    return enif_make_badarg(env);
+  for (unsigned d = 0; d < rank; ++d)
+    if (shape[d] < 0 || !mul_size(&n, (uint64_t)shape[d])) return enif_make_badarg(env);
+  if (!out_bin(&ob, n, 1, 1, dtype == 1 || dtype == 3 || dtype == 5 ? 8 : 4)) return mk_oom(env);
+  return wave_result(env, nxsig_unit_impulse(c->ctx, dtype, shape, (int32_t)rank, index, ob.data, NXSIG_HOST), &ob);
+}
+
 /* stft_to_mel(ctx, z_bin, rows, fft_length, mel_bins, filters_bin) -> {:ok, f32[rows][mel_bins]}   (lib/nx_signal.ex:486-513) */
 static ERL_NIF_TERM nif_stft_to_mel(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
@@ -1609,6 +1722,12 @@ static ErlNifFunc funcs[] = {
     {"wiener", 7, nif_wiener, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"argrelextrema", 7, nif_argrelextrema, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"nonzero", 3, nif_nonzero, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"sawtooth", 4, nif_sawtooth, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"square", 5, nif_square, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"gaussian_pulse", 6, nif_gaussian_pulse, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"chirp", 7, nif_chirp, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"polynomial_sweep", 6, nif_polynomial_sweep, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"unit_impulse", 4, nif_unit_impulse, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_to_mel", 6, nif_stft_to_mel, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_mel", 8, nif_stft_mel, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"stft_magnitude", 7, nif_stft_magnitude, ERL_NIF_DIRTY_JOB_IO_BOUND},

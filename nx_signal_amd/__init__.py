@@ -7,7 +7,7 @@ Python host mirror of the reference's function-level interface (elixir-nx/nx_sig
     NxSignal.Filters.firwin/3, median/2, wiener/2 -> nx_signal_amd.filters  (+ the new `fir`)
     NxSignal.PeakFinding.*        -> nx_signal_amd.peak_finding
     NxSignal.Convolution.*        -> nx_signal_amd.convolution (FFT method, 1-D)
-    NxSignal.Waveforms.sinc/1     -> nx_signal_amd.waveforms
+    NxSignal.Waveforms.*          -> nx_signal_amd.waveforms (sinc/1 on the host)
     NxSignal.Transforms.fft_nd    -> nx_signal_amd.transforms (last axis)
 
 Same option names, defaults, return shapes and failure cases (ArgumentError) as the reference; atoms

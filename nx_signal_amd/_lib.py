@@ -21,6 +21,8 @@ WIN_RECTANGULAR, WIN_BARTLETT, WIN_TRIANGULAR, WIN_BLACKMAN, WIN_HAMMING, WIN_HA
 CONV_FULL, CONV_SAME, CONV_VALID = 0, 1, 2
 DT_F32, DT_F64, DT_S32, DT_S64, DT_U32, DT_U64 = range(6)
 CMP_LESS, CMP_GREATER, CMP_LESS_EQUAL, CMP_GREATER_EQUAL = range(4)
+CHIRP_LINEAR, CHIRP_QUADRATIC, CHIRP_LOGARITHMIC, CHIRP_HYPERBOLIC = range(4)
+SWEEP_MAX_COEFS = 32
 SHARD_CHANNELS, SHARD_FRAMES = 0, 1
 
 
@@ -113,6 +115,12 @@ SIGNATURES = {
     "nxsig_wiener": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _i32, _f64, _p, C.POINTER(_f64), _i32]),
     "nxsig_argrelextrema": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, _i32, _i64, _i32, _p, _p, _i32]),
     "nxsig_nonzero": (C.c_int, [_p, _p, C.POINTER(_i64), _i32, _p, _p, _i32]),
+    "nxsig_sawtooth": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _i32]),
+    "nxsig_square": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _p, _i32]),
+    "nxsig_gaussian_pulse": (C.c_int, [_p, _p, _i32, _i64, _f64, _f64, _f64, _p, _p, _p, _i32]),
+    "nxsig_chirp": (C.c_int, [_p, _p, _i32, _i64, _f64, _f64, _f64, _i32, _i32, _f64, _p, _i32]),
+    "nxsig_polynomial_sweep": (C.c_int, [_p, _p, _i32, _i64, C.POINTER(_f64), _i32, _f64, _i32, _p, _i32]),
+    "nxsig_unit_impulse": (C.c_int, [_p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _p, _i32]),
     # f64 / c128 tier
     "nxsig_window_f64": (C.c_int, [_i32, _i32, _i32, _f64, _f64, _p]),
     "nxsig_sinc_f64": (C.c_int, [_p, _i64, _p]),

@@ -50,6 +50,7 @@ UNITS = [
     ("kernels_f64.hip", []),  # the f64 / c128 tier (workgroup-per-frame kernels in double)
     ("kernels_filters.hip", []),  # Filters.median / wiener (no FMA contraction: the file says so itself)
     ("kernels_peaks.hip", []),  # PeakFinding.argrelextrema / nonzero: mark, scan, compact
+    ("kernels_waveforms.hip", []),  # Waveforms.* elementwise (no FMA contraction: the file says so itself)
 ]
 
 

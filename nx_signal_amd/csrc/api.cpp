@@ -1556,6 +1556,262 @@ int nxsig_nonzero(nxsig_ctx* ctx, const uint8_t* mask, const int64_t* shape, int
   NXSIG_API_END
 }
 
+// NxSignal.Waveforms (lib/nx_signal/waveforms.ex): the reference's ArgumentErrors, the scalars that do not
+// depend on t computed once under the tier's rounding (f32: every op in double on f32 operands, rounded to f32; f64: no rounding;
+// pi() the f32 constant in both), host staging as in nxsig_median_filter.
+extern "C++" {
+namespace {
+constexpr double kWavePi = 3.1415927410125732;   // Nx.Constants.pi() as f32
+constexpr double kWaveTwoPi = 2.0 * kWavePi;     // 2 * pi(): exact
+
+struct WaveRound {
+  bool f64;
+  double operator()(double x) const { return f64 ? x : (double)(float)x; }
+};
+
+std::string wave_num(double v) {
+  char buf[40];
+  std::snprintf(buf, sizeof buf, "%.17g", v);
+  return buf;
+}
+
+// t (and a second stream) in, `nout` outputs of out_es-byte elements out: device pointers are used as they are, host ones are staged
+struct WaveIo {
+  Staged st;
+  const void *dt = nullptr, *d2 = nullptr;
+  void* dout[3] = {};
+  void* hout[3] = {};
+  size_t out_bytes = 0;
+  bool host = false;
+  explicit WaveIo(Ctx* c) : st(c) {}
+  int open(int32_t mem, const void* t, const void* second, size_t in_es, int64_t n, void* const* outs, int nout, size_t out_es) {
+    host = mem == NXSIG_HOST;
+    out_bytes = (size_t)n * out_es;
+    dt = t;
+    d2 = second;
+    for (int j = 0; j < nout; ++j) dout[j] = hout[j] = outs[j];
+    if (!host) return NXSIG_OK;
+    int rc = st.in(17, t, (size_t)n * in_es, &dt);
+    if (rc) return rc;
+    if (second && (rc = st.in(18, second, (size_t)n * in_es, &d2))) return rc;
+    const size_t stride = (out_bytes + 255) & ~(size_t)255;
+    void* base = nullptr;
+    if ((rc = st.out_alloc(19, stride * nout, &base))) return rc;
+    for (int j = 0; j < nout; ++j) dout[j] = static_cast<char*>(base) + stride * j;
+    return NXSIG_OK;
+  }
+  int close(int nout) {
+    if (!host) return NXSIG_OK;
+    for (int j = 0; j < nout; ++j) {
+      const int rc = st.out_copy(hout[j], dout[j], out_bytes);
+      if (rc) return rc;
+    }
+    return NXSIG_OK;
+  }
+};
+
+int wave_args(const char* fn, const void* t, const void* out, int64_t n, int32_t mem) {
+  if (n < 0) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": n must be >= 0");
+  if (n > 0 && (!t || !out)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  return check_mem(mem);
+}
+}  // namespace
+}  // extern "C++"
+
+int nxsig_sawtooth(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double width, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!(width >= 0.0 && width <= 1.0))   // waveforms.ex:34-36
+    return set_error(NXSIG_ERR_INVALID_ARG, "width must be between 0 and 1, inclusive. Got: " + wave_num(width));
+  int rc = wave_args("sawtooth", t, out, n, mem);
+  if (rc || n == 0) return rc;
+  const WaveRound R{is_f64 != 0};
+  WaveSaw p;
+  // width is an Elixir number: width + 1 and 1 - width are double arithmetic and the number meets pi() unrounded
+  p.two_pi = kWaveTwoPi;
+  p.thr = R(kWaveTwoPi * width);
+  p.d_rise = R(kWavePi * width);
+  p.c_fall = R(kWavePi * (width + 1.0));
+  p.d_fall = R(kWavePi * (1.0 - width));
+  p.mode = width == 1.0 ? 1 : width == 0.0 ? 0 : 2;
+  WaveIo io(c);
+  const size_t es = is_f64 ? 8 : 4;
+  if ((rc = io.open(mem, t, nullptr, es, n, &out, 1, es))) return rc;
+  if ((rc = launch_sawtooth(c, io.dt, is_f64 != 0, n, p, io.dout[0]))) return rc;
+  return io.close(1);
+  NXSIG_API_END
+}
+
+int nxsig_square(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double duty, const void* duty_tensor, int32_t* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  int rc = wave_args("square", t, out, n, mem);
+  if (rc || n == 0) return rc;
+  const WaveRound R{is_f64 != 0};
+  WaveSquare p;
+  p.two_pi = kWaveTwoPi;
+  p.pi = kWavePi;
+  p.thr = R(R(R(duty) * 2.0) * kWavePi);   // duty * 2 * pi(), duty a tensor argument of square_n
+  WaveIo io(c);
+  void* o = out;
+  if ((rc = io.open(mem, t, duty_tensor, is_f64 ? 8 : 4, n, &o, 1, 4))) return rc;
+  if ((rc = launch_square(c, io.dt, is_f64 != 0, n, p, io.d2, static_cast<int32_t*>(io.dout[0])))) return rc;
+  return io.close(1);
+  NXSIG_API_END
+}
+
+int nxsig_gaussian_pulse(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double center_frequency, double bandwidth,
+                         double bandwidth_reference_level, void* envelope, void* in_phase, void* quadrature, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  const double fc = center_frequency, bw = bandwidth, bwr = bandwidth_reference_level;
+  if (!(fc >= 0.0))   // waveforms.ex:173-186
+    return set_error(NXSIG_ERR_INVALID_ARG, "Center frequency must be greater than or equal to 0, got: " + wave_num(fc));
+  if (!(bw > 0.0)) return set_error(NXSIG_ERR_INVALID_ARG, "Bandwidth must be greater than 0, got: " + wave_num(bw));
+  if (!(bwr < 0.0)) return set_error(NXSIG_ERR_INVALID_ARG, "Bandwidth reference level must be less than 0, got: " + wave_num(bwr));
+  int rc = wave_args("gaussian_pulse", t, envelope, n, mem);
+  if (rc || n == 0) return rc;
+  if (!in_phase || !quadrature) return set_error(NXSIG_ERR_INVALID_ARG, "gaussian_pulse: null pointer argument");
+  const WaveRound R{is_f64 != 0};
+  // constants fold in double before they meet a tensor: ref = f32(10^(bwr / 20)), a = -f32((pi fc bw)^2) / (4 log(ref))
+  const double ref = R(std::pow(10.0, bwr / 20.0));
+  const double pfb = 3.141592653589793 * fc * bw;
+  const double a = R(-R(pfb * pfb) / R(4.0 * R(std::log(ref))));
+  WaveGauss p;
+  p.neg_a = R(-a);
+  p.w = R(kWaveTwoPi * R(fc));
+  WaveIo io(c);
+  const size_t es = is_f64 ? 8 : 4;
+  void* outs[3] = {envelope, in_phase, quadrature};
+  if ((rc = io.open(mem, t, nullptr, es, n, outs, 3, es))) return rc;
+  if ((rc = launch_gaussian_pulse(c, io.dt, is_f64 != 0, n, p, io.dout[0], io.dout[1], io.dout[2]))) return rc;
+  return io.close(3);
+  NXSIG_API_END
+}
+
+int nxsig_chirp(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double f0, double t1, double f1, int32_t method, int32_t vertex_zero,
+                double phi, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (method < NXSIG_CHIRP_LINEAR || method > NXSIG_CHIRP_HYPERBOLIC)   // waveforms.ex:291-300
+    return set_error(NXSIG_ERR_INVALID_ARG, "invalid method, must be one of [:linear, :quadratic, :logarithmic, :hyperbolic], got: " + std::to_string(method));
+  int rc = wave_args("chirp", t, out, n, mem);
+  if (rc || n == 0) return rc;
+  const WaveRound R{is_f64 != 0};
+  f0 = R(f0), t1 = R(t1), f1 = R(f1);   // tensor arguments of the defn
+  WaveChirp p{};
+  p.two_pi = kWaveTwoPi;
+  p.phi = R(phi);
+  const char* family = "waveform.chirp.linear";
+  if (method == NXSIG_CHIRP_LINEAR) {
+    p.kind = kChirpLinear;
+    p.a = f0;
+    p.b = R(0.5 * R(R(f1 - f0) / t1));
+  } else if (method == NXSIG_CHIRP_QUADRATIC) {
+    family = "waveform.chirp.quadratic";
+    const double beta = R(R(f1 - f0) / R(t1 * t1));
+    p.kind = vertex_zero ? kChirpQuadratic : kChirpQuadraticT1;
+    p.a = vertex_zero ? f0 : f1;
+    p.b = beta;
+    p.c = t1;
+    p.d = R(std::pow(t1, 3.0));
+  } else if (method == NXSIG_CHIRP_LOGARITHMIC) {
+    family = "waveform.chirp.logarithmic";
+    if (f0 * f1 <= 0.0) {
+      p.kind = kChirpNan;
+    } else if (f0 == f1) {
+      p.kind = kChirpConstant;
+      p.a = R(kWaveTwoPi * f0);
+    } else {
+      const double ratio = R(f1 / f0), beta = R(t1 / R(std::log(ratio)));
+      p.kind = kChirpLogarithmic;
+      p.a = R(beta * f0);
+      p.b = ratio;
+      p.c = t1;
+    }
+  } else {
+    family = "waveform.chirp.hyperbolic";
+    if (f0 == f1) {
+      p.kind = kChirpConstant;
+      p.a = R(kWaveTwoPi * f0);
+    } else {
+      const double sp = R(R(R(-f1) * t1) / R(f0 - f1));
+      p.kind = kChirpHyperbolic;
+      p.a = R(R(-sp) * f0);
+      p.b = sp;
+    }
+  }
+  WaveIo io(c);
+  const size_t es = is_f64 ? 8 : 4;
+  if ((rc = io.open(mem, t, nullptr, es, n, &out, 1, es))) return rc;
+  if ((rc = launch_chirp(c, io.dt, is_f64 != 0, n, p, family, io.dout[0]))) return rc;
+  return io.close(1);
+  NXSIG_API_END
+}
+
+int nxsig_polynomial_sweep(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, const double* coefs, int32_t ncoefs, double phi,
+                           int32_t phi_degrees, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (ncoefs < 1 || ncoefs > NXSIG_SWEEP_MAX_COEFS)
+    return set_error(NXSIG_ERR_INVALID_ARG, "polynomial_sweep: coefs must have 1 to " + std::to_string(NXSIG_SWEEP_MAX_COEFS) + " entries, got " +
+                                                std::to_string(ncoefs));
+  if (!coefs) return set_error(NXSIG_ERR_INVALID_ARG, "polynomial_sweep: null pointer argument");
+  int rc = wave_args("polynomial_sweep", t, out, n, mem);
+  if (rc || n == 0) return rc;
+  const WaveRound R{is_f64 != 0};
+  WaveSweep p{};
+  p.n = ncoefs;
+  p.two_pi = kWaveTwoPi;
+  p.phi = phi_degrees ? R(phi * kWavePi / 180.0) : R(phi);   // phi * pi() / 180: constants, folded in double
+  for (int k = 0; k < ncoefs; ++k) p.coef[k] = R(R(coefs[k]) / (double)(ncoefs - k));
+  WaveIo io(c);
+  const size_t es = is_f64 ? 8 : 4;
+  if ((rc = io.open(mem, t, nullptr, es, n, &out, 1, es))) return rc;
+  if ((rc = launch_polynomial_sweep(c, io.dt, is_f64 != 0, n, p, io.dout[0]))) return rc;
+  return io.close(1);
+  NXSIG_API_END
+}
+
+int nxsig_unit_impulse(nxsig_ctx* ctx, int32_t dtype, const int64_t* shape, int32_t rank, const int64_t* index, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (dtype < NXSIG_DT_F32 || dtype > NXSIG_DT_U64) return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: unknown dtype");
+  if (rank < 0 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: rank must be in [0, 8]");
+  if (rank > 0 && (!shape || !index)) return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: null pointer argument");
+  int64_t n = 1;
+  for (int d = 0; d < rank; ++d) {
+    if (shape[d] < 0) return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: negative dimension");
+    if (shape[d] && n > (((int64_t)1 << 60) / shape[d])) return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: shape too large");
+    n *= shape[d];
+  }
+  if (n == 0) return NXSIG_OK;   // an empty dimension: an empty tensor, nothing to put
+  if (!out) return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: null pointer argument");
+  int64_t at = 0;
+  for (int d = 0; d < rank; ++d) {
+    if (index[d] < 0 || index[d] >= shape[d])
+      return set_error(NXSIG_ERR_INVALID_ARG, "unit_impulse: index " + std::to_string(index[d]) + " is out of range for axis " + std::to_string(d) +
+                                                  " of size " + std::to_string(shape[d]));
+    at = at * shape[d] + index[d];
+  }
+  const size_t bytes = (size_t)n * (dtype == NXSIG_DT_F64 || dtype == NXSIG_DT_S64 || dtype == NXSIG_DT_U64 ? 8 : 4);
+  if (mem == NXSIG_DEVICE) return launch_unit_impulse(c, out, dtype, n, at);
+  Staged st(c);
+  void* dout = nullptr;
+  if ((rc = st.out_alloc(19, bytes, &dout))) return rc;
+  if ((rc = launch_unit_impulse(c, dout, dtype, n, at))) return rc;
+  return st.out_copy(out, dout, bytes);
+  NXSIG_API_END
+}
+
 int nxsig_fftconvolve_c64(nxsig_ctx* ctx, const nxsig_c64* a, int64_t n1, const nxsig_c64* b, int64_t n2, int32_t mode,
                           nxsig_c64* out, int32_t mem) {
   NXSIG_API_BEGIN

@@ -298,6 +298,35 @@ int launch_wiener(Ctx* c, const void* x, bool f64, const int64_t* shape, int ran
 int launch_argrelextrema(Ctx* c, const void* x, int dtype, const int64_t* shape, int rank, int axis, int64_t shifts, int comparator,
                          int32_t* indices, uint32_t* valid);
 int launch_nonzero(Ctx* c, const uint8_t* mask, const int64_t* shape, int rank, int32_t* indices, uint32_t* valid);
+// kernels_waveforms.hip: NxSignal.Waveforms over n device elements (f32, or f64 when f64).  The scalars are computed by the caller
+// under the tier's rounding and passed by value; n == 0 launches nothing; nothing waits
+struct WaveSaw {
+  double two_pi, thr, d_rise, c_fall, d_fall;   // 2 pi(), 2 pi() width, pi() width, pi() (width + 1), pi() (1 - width)
+  int32_t mode;                                 // 1: width == 1 (rise only), 0: width == 0 (fall only), 2: select on tmod < thr
+};
+struct WaveSquare {
+  double two_pi, pi, thr;   // thr = duty * 2 * pi() of a scalar duty
+};
+struct WaveGauss {
+  double neg_a, w;   // -a, 2 pi() fc
+};
+enum WaveChirpKind { kChirpLinear = 0, kChirpQuadratic, kChirpQuadraticT1, kChirpLogarithmic, kChirpHyperbolic, kChirpConstant, kChirpNan };
+struct WaveChirp {
+  int32_t kind;
+  double two_pi, a, b, c, d, phi;   // per kind: see ChirpOp
+};
+constexpr int kWaveSweepMaxCoefs = 32;
+struct WaveSweep {
+  int32_t n;
+  double two_pi, phi;
+  double coef[kWaveSweepMaxCoefs];   // coefs[k] / (n - k)
+};
+int launch_sawtooth(Ctx* c, const void* t, bool f64, int64_t n, const WaveSaw& p, void* out);
+int launch_square(Ctx* c, const void* t, bool f64, int64_t n, const WaveSquare& p, const void* duty, int32_t* out);
+int launch_gaussian_pulse(Ctx* c, const void* t, bool f64, int64_t n, const WaveGauss& p, void* envelope, void* in_phase, void* quadrature);
+int launch_chirp(Ctx* c, const void* t, bool f64, int64_t n, const WaveChirp& p, const char* family, void* out);
+int launch_polynomial_sweep(Ctx* c, const void* t, bool f64, int64_t n, const WaveSweep& p, void* out);
+int launch_unit_impulse(Ctx* c, void* out, int dtype, int64_t n, int64_t at);
 
 // ---- f64 / c128 tier (kernels_f64.hip) ----
 struct StftLaunchD {
