@@ -273,6 +273,96 @@ defmodule NxSignalAMD do
     h |> Nx.as_type(:c64) |> Nx.to_binary()
   end
 
+  @doc """
+  `istft(Nx.multiply(z, mask), window, opts)` in one library call: the time-frequency masking step of denoising, source
+  separation and spectral gating. `mask` is `f32[..., M, K]`, `c64[..., M, K]` or the one-sided real `f32[..., M, K/2 + 1]`
+  (bin `k > K/2` takes `mask[K - k]`; `K` even). The flattened leading axes of `z` and `mask` are equal, or one of them is 1
+  and that operand is broadcast (one mixture, S masks); the result takes the leading shape of the operand that carries the
+  rows. Both operands are `Nx.Tensor`s or both are `DeviceTensor`s of one context. Options, defaults and errors are those of
+  `istft/3`. Bit-identical to `istft(spectrum_mask(z, mask), window, opts)`; for 1024-point frames at hop 128 / 256 / 512 /
+  1024 the mask rows stream into the inverse-STFT kernel and the masked spectrogram is never written to HBM.
+  """
+  def istft_masked(z, mask, window, opts \\ []) do
+    {dev, zarg, marg, m, k, kind, bz, bm, lead, ctx} = mask_operands!(z, mask, "istft_masked")
+
+    if Nx.type(window) == {:f, 64},
+      do: raise(ArgumentError, "istft_masked is an f32 extension: an f64 window is not taken")
+
+    {params, _overlap, ^m, _} = istft_params!({m, k}, window, opts)
+    w = window |> Nx.as_type(:f32) |> Nx.to_binary()
+    {:ok, y} = NIF.istft_masked(ctx, zarg, bz, m, w, params, marg, kind, bm) |> unwrap!()
+    out_shape = append(lead, [m * elem(params, 1) + (elem(params, 0) - elem(params, 1))])
+    mask_result(dev, y, ctx, out_shape)
+  end
+
+  @doc """
+  `Nx.multiply(z, mask)` for a time-frequency mask, kept where the operands are (see `istft_masked/4` for the operands). A
+  complex mask multiplies like `Nx.multiply/2` on c64; a real gain multiplies each component on its own, in double with one
+  rounding. Returns `c64[..., M, K]`.
+  """
+  def spectrum_mask(z, mask) do
+    {dev, zarg, marg, m, k, kind, bz, bm, lead, ctx} = mask_operands!(z, mask, "spectrum_mask")
+    {:ok, out} = NIF.spectrum_mask(ctx, zarg, bz, marg, kind, bm, m, k) |> unwrap!()
+    mask_result(dev, out, ctx, append(lead, [m, k]))
+  end
+
+  defp mask_result(true, ref, ctx, shape), do: %DeviceTensor{ref: ref, ctx: ctx, shape: shape, type: {:c, 64}}
+  defp mask_result(false, bin, _ctx, shape), do: Nx.from_binary(bin, :c64) |> Nx.reshape(shape)
+
+  # shape / type / placement checks of the two mask entry points -> {dev?, z, mask, M, K, kind, Bz, Bm, lead, ctx}
+  defp mask_operands!(%DeviceTensor{} = z, %DeviceTensor{} = mask, fun) do
+    if z.ctx != mask.ctx, do: raise(ArgumentError, "#{fun}: z and mask live on different contexts")
+    if z.type != {:c, 64}, do: raise(ArgumentError, "#{fun}: the spectrum must be c64, got: #{inspect(z.type)}")
+
+    if mask.type not in [{:f, 32}, {:c, 64}],
+      do: raise(ArgumentError, "#{fun}: a device mask must be f32 or c64, got: #{inspect(mask.type)}")
+
+    {m, k, kind, bz, bm, lead} = mask_geometry!(z.shape, mask.shape, mask.type, fun)
+    {true, z.ref, mask.ref, m, k, kind, bz, bm, lead, z.ctx}
+  end
+
+  defp mask_operands!(%Nx.Tensor{} = z, %Nx.Tensor{} = mask, fun) do
+    if Nx.type(z) in [{:c, 128}, {:f, 64}] or Nx.type(mask) in [{:c, 128}, {:f, 64}],
+      do: raise(ArgumentError, "#{fun} is an f32 extension: f64 / c128 operands are not taken")
+
+    mtype = if match?({:c, _}, Nx.type(mask)), do: {:c, 64}, else: {:f, 32}
+    {m, k, kind, bz, bm, lead} = mask_geometry!(Nx.shape(z), Nx.shape(mask), mtype, fun)
+    zb = z |> Nx.as_type(:c64) |> Nx.to_binary()
+    mb = mask |> Nx.as_type(mtype) |> Nx.to_binary()
+    {false, zb, mb, m, k, kind, bz, bm, lead, context()}
+  end
+
+  defp mask_operands!(_z, _mask, fun),
+    do: raise(ArgumentError, "#{fun}: z and mask must both be Nx tensors or both be DeviceTensors")
+
+  defp mask_geometry!(zshape, mshape, mtype, fun) do
+    if tuple_size(zshape) < 2 or tuple_size(mshape) < 2,
+      do: raise(ArgumentError, "#{fun} expects tensors of shape {..., frames, frequencies}")
+
+    {zlead, [m, k]} = zshape |> Tuple.to_list() |> Enum.split(-2)
+    {mlead, [mm, km]} = mshape |> Tuple.to_list() |> Enum.split(-2)
+    if mm != m, do: raise(ArgumentError, "#{fun}: mask has #{mm} frames, the spectrum #{m}")
+
+    kind =
+      cond do
+        km == k and mtype == {:c, 64} -> 2
+        km == k -> 0
+        km == div(k, 2) + 1 and rem(k, 2) == 1 -> raise ArgumentError, "#{fun}: a one-sided mask needs an even fft_length, got #{k}"
+        km == div(k, 2) + 1 and mtype == {:c, 64} -> raise ArgumentError, "#{fun}: a one-sided mask must be real"
+        km == div(k, 2) + 1 -> 1
+        true -> raise ArgumentError, "#{fun}: the mask's last axis must be fft_length (#{k}) or fft_length / 2 + 1, got #{km}"
+      end
+
+    bz = Enum.product(zlead)
+    bm = Enum.product(mlead)
+
+    if bz != bm and bz != 1 and bm != 1,
+      do: raise(ArgumentError, "#{fun}: z has #{bz} rows and mask #{bm}: they must be equal, or one of them 1")
+
+    lead = if bz >= bm and (bz > 1 or length(zlead) >= length(mlead)), do: zlead, else: mlead
+    {m, k, kind, bz, bm, List.to_tuple(lead)}
+  end
+
   @doc "See `NxSignal.as_windowed/2` (lib/nx_signal.ex:249-364): `{..., L}` -> `{..., M, window_length}`, bit-exact gather."
   def as_windowed(%Nx.Tensor{} = tensor, opts \\ []) do
     opts = Keyword.validate!(opts, [:window_length, padding: :valid, stride: 1])

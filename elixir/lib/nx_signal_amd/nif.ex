@@ -73,6 +73,12 @@ defmodule NxSignalAMD.NIF do
   def istft_filtered_dev(_ctx, _z, _frames, _batch, _window, _params, _h), do: :erlang.nif_error(:nif_not_loaded)
   def fir_dev(_ctx, _x, _length, _batch, _taps, _mode), do: :erlang.nif_error(:nif_not_loaded)
   def spectrum_mul_dev(_ctx, _z, _rows, _fft_length, _h), do: :erlang.nif_error(:nif_not_loaded)
+
+  def spectrum_mask(_ctx, _z, _z_rows, _mask, _mask_kind, _mask_rows, _frames, _fft_length),
+    do: :erlang.nif_error(:nif_not_loaded)
+
+  def istft_masked(_ctx, _z, _z_rows, _frames, _window, _params, _mask, _mask_kind, _mask_rows),
+    do: :erlang.nif_error(:nif_not_loaded)
   def group_create(_devices), do: :erlang.nif_error(:nif_not_loaded)
   def group_info(_group), do: :erlang.nif_error(:nif_not_loaded)
 

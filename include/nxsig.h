@@ -447,6 +447,36 @@ int nxsig_istft_filtered_c64(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_fra
                              const nxsig_stft_params* params, const nxsig_c64* h, nxsig_c64* y, int32_t mem);
 
 /*
+ * Time-frequency masks (denoising, source separation, spectral gating): a mask that differs from frame to frame, unlike the
+ * filter `h` above.  The layout of one mask row (one frame):
+ *   NXSIG_MASK_REAL      f32[K]        real gain per bin
+ *   NXSIG_MASK_ONESIDED  f32[K/2 + 1]  real gain of bins 0 .. K/2; bin k > K/2 takes mask[K - k] (K even)
+ *   NXSIG_MASK_COMPLEX   c64[K]
+ * A real gain multiplies each component on its own, (float)((double)z.c * (double)m); a complex one is the product of
+ * nxsig_spectrum_mul_c64.  z has z_rows rows of [num_frames][K], the mask mask_rows rows of [num_frames][row length]: the two
+ * counts are equal, or one of them is 1 and that operand is read again for every row of the other (one mixture and S masks:
+ * z_rows == 1, mask_rows == S).  The result has max(z_rows, mask_rows) rows, at most 65 535 (the limit of the filtered form).
+ * `mem` covers z, the mask and the result alike.
+ */
+typedef enum nxsig_mask_kind { NXSIG_MASK_REAL = 0, NXSIG_MASK_ONESIDED = 1, NXSIG_MASK_COMPLEX = 2 } nxsig_mask_kind;
+
+/* out[r][m][k] = z[r or 0][m][k] * mask[r or 0][m][k]: c64[max(z_rows, mask_rows)][num_frames][fft_length].  out must not
+ * alias z or the mask when one of them is broadcast. */
+int nxsig_spectrum_mask_c64(nxsig_ctx* ctx, const nxsig_c64* z, int32_t z_rows, const void* mask, int32_t mask_kind,
+                            int32_t mask_rows, int64_t num_frames, int32_t fft_length, nxsig_c64* out, int32_t mem);
+
+/*
+ * NxSignal.istft(Nx.multiply(z, mask), window, opts) in one call: the same bits as nxsig_spectrum_mask_c64 followed by
+ * nxsig_istft_c64.  For N = fft_length = 1024 and hop 128 / 256 / 512 / 1024 every frame's mask row streams into the inverse
+ * kernel next to its spectrum and the masked spectrogram never exists in HBM (30 KB of traffic per frame -> 14 with a full real
+ * mask, 12 with a one-sided one, at hop 256); other geometries run the two steps behind this entry.  z and the mask are not
+ * modified.  y c64[max(z_rows, mask_rows)][M*hop + N-hop].
+ */
+int nxsig_istft_masked_c64(nxsig_ctx* ctx, const nxsig_c64* z, int32_t z_rows, int64_t num_frames, const float* window,
+                           const nxsig_stft_params* params, const void* mask, int32_t mask_kind, int32_t mask_rows,
+                           nxsig_c64* y, int32_t mem);
+
+/*
  * 1-D complex case of Convolution.fftconvolve/3 — lib/nx_signal/convolution.ex:252-329 (tests: "FFT complex",
  * test/nx_signal/convolutions_test.exs:473-487): out = ifft(fft(a, P) * fft(b, P)) sliced per mode, with
  * P = next power of two >= n1 + n2 - 1 (same linear convolution as the reference's length n1 + n2 - 1).

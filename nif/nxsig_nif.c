@@ -1234,6 +1234,105 @@ static ERL_NIF_TERM nif_spectrum_mul_dev(ErlNifEnv* env, int argc, const ERL_NIF
   return rc ? mk_error(env, rc) : mk_ok(env, argv[1]);
 }
 
+/* ---- time-frequency masks (nxsig_spectrum_mask_c64 / nxsig_istft_masked_c64).  z and mask are BOTH binaries (host result: a binary)
+ * or BOTH device buffers of this context (result: a new buffer; the call is asynchronous).  mask_kind: 0 real f32[K], 1 one-sided
+ * real f32[K/2 + 1], 2 c64[K] per frame; z_rows / mask_rows are equal or one of them is 1 (that operand is broadcast). */
+typedef struct {
+  const void *z, *mask;
+  size_t zbytes, mbytes;
+  int dev;
+} mask_operands_t;
+static int get_mask_operands(ErlNifEnv* env, ctx_res_t* c, ERL_NIF_TERM zt, ERL_NIF_TERM mt, mask_operands_t* o) {
+  ErlNifBinary zb, mb;
+  buf_res_t *zr, *mr;
+  if (enif_inspect_binary(env, zt, &zb) && enif_inspect_binary(env, mt, &mb)) {
+    o->z = zb.data; o->zbytes = zb.size; o->mask = mb.data; o->mbytes = mb.size; o->dev = 0;
+    return 1;
+  }
+  if (get_buf(env, zt, &zr) && get_buf(env, mt, &mr) && zr->owner == c && mr->owner == c) {
+    o->z = zr->dptr; o->zbytes = zr->bytes; o->mask = mr->dptr; o->mbytes = mr->bytes; o->dev = 1;
+    return 1;
+  }
+  return 0;
+}
+/* the sizes the two operands must have (binaries: exactly; buffers: at least); *rows = rows of the result */
+static int mask_sizes_ok(const mask_operands_t* o, int z_rows, int mask_kind, int mask_rows, ErlNifSInt64 m, int k, int* rows) {
+  if (z_rows < 1 || mask_rows < 1 || m < 1 || k < 1 || mask_kind < 0 || mask_kind > 2) return 0;
+  if (z_rows != mask_rows && z_rows != 1 && mask_rows != 1) return 0;
+  if (mask_kind == 1 && (k & 1)) return 0;
+  size_t zneed = 8, mneed = mask_kind == 2 ? 8 : 4;
+  if (!mul_size(&zneed, (uint64_t)z_rows) || !mul_size(&zneed, (uint64_t)m) || !mul_size(&zneed, (uint64_t)k)) return 0;
+  if (!mul_size(&mneed, (uint64_t)mask_rows) || !mul_size(&mneed, (uint64_t)m) ||
+      !mul_size(&mneed, (uint64_t)(mask_kind == 1 ? k / 2 + 1 : k)))
+    return 0;
+  if (o->dev ? (o->zbytes < zneed || o->mbytes < mneed) : (o->zbytes != zneed || o->mbytes != mneed)) return 0;
+  *rows = z_rows > mask_rows ? z_rows : mask_rows;
+  return 1;
+}
+
+/* spectrum_mask(ctx, z, z_rows, mask, mask_kind, mask_rows, num_frames, fft_length) -> {:ok, out}   (Nx.multiply(z, mask)) */
+static ERL_NIF_TERM nif_spectrum_mask(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  mask_operands_t o;
+  ErlNifSInt64 m;
+  int z_rows, kind, mask_rows, k, rows;
+  if (argc != 8 || !get_ctx(env, argv[0], &c) || !get_mask_operands(env, c, argv[1], argv[3], &o) || !enif_get_int(env, argv[2], &z_rows) ||
+      !enif_get_int(env, argv[4], &kind) || !enif_get_int(env, argv[5], &mask_rows) || !enif_get_int64(env, argv[6], &m) ||
+      !enif_get_int(env, argv[7], &k))
+    return enif_make_badarg(env);
+  if (!mask_sizes_ok(&o, z_rows, kind, mask_rows, m, k, &rows)) return enif_make_badarg(env);
+  if (!o.dev) {
+    ErlNifBinary ob;
+    if (!out_bin(&ob, (uint64_t)rows, (uint64_t)m, (uint64_t)k, 8)) return mk_oom(env);
+    int rc = nxsig_spectrum_mask_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, o.mask, kind, mask_rows, m, k, (nxsig_c64*)ob.data, NXSIG_HOST);
+    if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
+    return mk_ok(env, enif_make_binary(env, &ob));
+  }
+  size_t obytes = 8;
+  if (!mul_size(&obytes, (uint64_t)rows) || !mul_size(&obytes, (uint64_t)m) || !mul_size(&obytes, (uint64_t)k)) return mk_oom(env);
+  void* out = NULL;
+  int rc = nxsig_alloc(c->ctx, obytes, &out);
+  if (rc) return mk_error(env, rc);
+  rc = nxsig_spectrum_mask_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, o.mask, kind, mask_rows, m, k, (nxsig_c64*)out, NXSIG_DEVICE);
+  if (rc) { nxsig_free(c->ctx, out); return mk_error(env, rc); }
+  return mk_ok(env, make_buf(env, c, out, obytes));
+}
+
+/* istft_masked(ctx, z, z_rows, num_frames, window_bin, params, mask, mask_kind, mask_rows) -> {:ok, y}
+ * NxSignal.istft(Nx.multiply(z, mask), window, opts) in one library call; z and mask are left untouched */
+static ERL_NIF_TERM nif_istft_masked(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  mask_operands_t o;
+  ErlNifBinary w;
+  ErlNifSInt64 m;
+  int z_rows, kind, mask_rows, rows;
+  nxsig_stft_params p;
+  if (argc != 9 || !get_ctx(env, argv[0], &c) || !get_mask_operands(env, c, argv[1], argv[6], &o) || !enif_get_int(env, argv[2], &z_rows) ||
+      !enif_get_int64(env, argv[3], &m) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
+      !enif_get_int(env, argv[7], &kind) || !enif_get_int(env, argv[8], &mask_rows))
+    return enif_make_badarg(env);
+  if (!mask_sizes_ok(&o, z_rows, kind, mask_rows, m, p.fft_length, &rows) || w.size != (size_t)p.frame_length * 4) return enif_make_badarg(env);
+  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
+  if (n < 0) return mk_error(env, (int)n);
+  if (!o.dev) {
+    ErlNifBinary yb;
+    if (!out_bin(&yb, (uint64_t)rows, (uint64_t)n, 1, 8)) return mk_oom(env);
+    int rc = nxsig_istft_masked_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, m, (const float*)w.data, &p, o.mask, kind, mask_rows,
+                                    (nxsig_c64*)yb.data, NXSIG_HOST);
+    if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
+    return mk_ok(env, enif_make_binary(env, &yb));
+  }
+  size_t ybytes = 8;
+  if (!mul_size(&ybytes, (uint64_t)rows) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
+  void* y = NULL;
+  int rc = nxsig_alloc(c->ctx, ybytes, &y);
+  if (rc) return mk_error(env, rc);
+  rc = nxsig_istft_masked_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, m, (const float*)w.data, &p, o.mask, kind, mask_rows, (nxsig_c64*)y,
+                              NXSIG_DEVICE);
+  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
+  return mk_ok(env, make_buf(env, c, y, ybytes));
+}
+
 /* ------------------------------------------------------------------------------------------------ multi-GPU groups
  * One BEAM process drives every GPU of the node: a LOCAL group (ncclCommInitAll).  The vectorized (multichannel) axis of the
  * reference (lib/nx_signal.ex:358-363) is what `axis = 0` shards. */
@@ -1743,6 +1842,8 @@ static ErlNifFunc funcs[] = {
     {"istft_filtered_dev", 7, nif_istft_filtered_dev, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"fir_dev", 6, nif_fir_dev, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"spectrum_mul_dev", 5, nif_spectrum_mul_dev, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"spectrum_mask", 8, nif_spectrum_mask, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"istft_masked", 9, nif_istft_masked, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"group_create", 1, nif_group_create, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"group_info", 1, nif_group_info, 0},
     {"stft_sharded", 8, nif_stft_sharded, ERL_NIF_DIRTY_JOB_IO_BOUND},

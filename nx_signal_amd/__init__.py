@@ -28,7 +28,7 @@ from .device import Context, DeviceBuffer, default_context, device_view, is_devi
 
 __all__ = [
     "stft", "istft", "as_windowed", "overlap_and_add", "fft_frequencies", "mel_filters", "stft_to_mel", "mel_spectrogram",
-    "spectrum_multiply", "istft_filtered", "stft_onesided", "spectrogram",
+    "spectrum_multiply", "istft_filtered", "spectrum_mask", "istft_masked", "stft_onesided", "spectrogram",
     "Context", "DeviceBuffer", "default_context", "ArgumentError",
     "NxSignalDeviceError", "NxSignalLibraryError", "NxSignalUnsupported",
 ]
@@ -371,8 +371,9 @@ def istft_filtered(data, h, window, ctx: Context | None = None, **opts):
     return _istft(data, window, ctx, opts, hh)
 
 
-def _istft(data, window, ctx, opts, hh, packed=False):
-    data, window = _as_tensor(data), _as_tensor(window)
+def _istft_options(window, opts):
+    """the options of NxSignal.istft/3 with their defaults and errors, shared by istft, istft_filtered, istft_packed and istft_masked
+    (needs no context) -> (options, host window, N, hop, sampling rate)"""
     o = _validate(opts, {"fft_length": None, "overlap_length": None, "scaling": None, "sampling_rate": 1000}, "istft")
     w = _window_host(window)
     N = int(w.shape[0])
@@ -385,6 +386,20 @@ def _istft(data, window, ctx, opts, hh, packed=False):
     if overlap >= N:  # overlap_and_add check, :692-695
         raise ArgumentError(f"overlap_length must be a number less than the window size {N}, got: {N}")
     hop = N - overlap
+    return o, w, N, hop, fs
+
+
+def _istft_fft_length(o, Kin):
+    """:fft_length against the spectrum's last axis (ifft pad / truncate is not built)"""
+    K = _resolve_fft_length(o["fft_length"], Kin)
+    if K != Kin:
+        raise NxSignalUnsupported("istft: fft_length different from the spectrum's last axis (ifft pad/truncate) is not built")
+    return K
+
+
+def _istft(data, window, ctx, opts, hh, packed=False):
+    data, window = _as_tensor(data), _as_tensor(window)
+    o, w, N, hop, fs = _istft_options(window, opts)
     lib = _lib.load()
     wide = False   # f64 tier: a c128 spectrum is inverted in c128 (Nx.ifft :609)
     if is_device(data):
@@ -409,9 +424,7 @@ def _istft(data, window, ctx, opts, hh, packed=False):
     Mf, Kin = int(shape[-2]), int(shape[-1])
     if packed:
         Kin *= 2   # the packed rows hold fft_length / 2 complex values
-    K = _resolve_fft_length(o["fft_length"], Kin)
-    if K != Kin:
-        raise NxSignalUnsupported("istft: fft_length different from the spectrum's last axis (ifft pad/truncate) is not built")
+    K = _istft_fft_length(o, Kin)
     if hh is not None and int(hh.shape[0]) != K:
         raise ArgumentError("istft_filtered: h must have fft_length bins")
     batch = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
@@ -570,6 +583,116 @@ def spectrum_multiply(z, h, ctx: Context | None = None):
     rows = int(np.prod(zin.shape[:-1], dtype=np.int64))
     _lib.check(lib.nxsig_spectrum_mul_c64(c.handle, _as_ptr(zin), rows, K, _as_ptr(hh), _as_ptr(out), _lib.HOST))
     return out
+
+
+_MASK_REAL, _MASK_ONESIDED, _MASK_COMPLEX = 0, 1, 2   # nxsig_mask_kind
+
+
+def _mask_operands(z, mask, fn):
+    """Shape / type / placement checks shared by spectrum_mask and istft_masked — all of them before a context exists.
+    -> (dev, zv, mv, (M, K), kind, (Bz, Bm), lead): zv / mv are (ptr, shape, dtype) of device operands or contiguous host arrays."""
+    z, mask = _as_tensor(z), _as_tensor(mask)
+    dev = is_device(z)
+    if dev != is_device(mask):
+        raise ArgumentError(f"{fn}: z and mask must both be host tensors or both be device-resident")
+    if dev:
+        zv, mv = device_view(z), device_view(mask)
+        zshape, zdt, mshape, mdt = tuple(zv[1]), np.dtype(zv[2]), tuple(mv[1]), np.dtype(mv[2])
+        cz, cm = getattr(z, "ctx", None), getattr(mask, "ctx", None)
+        if cz is not None and cm is not None and cz is not cm:
+            raise ArgumentError(f"{fn}: z and mask live on different contexts")
+    else:
+        zv, mv = np.asarray(z), np.asarray(mask)
+        zshape, zdt, mshape, mdt = zv.shape, zv.dtype, mv.shape, mv.dtype
+    if zdt in (np.dtype(np.complex128), np.dtype(np.float64)) or mdt in (np.dtype(np.complex128), np.dtype(np.float64)):
+        raise ArgumentError(f"{fn} is an f32 extension: f64 / c128 operands are not taken (cast to complex64 / float32)")
+    if dev and zdt != np.dtype(np.complex64):
+        raise ArgumentError(f"{fn}: device spectrum must be complex64")
+    if mdt.kind == "c":
+        cplx = True
+    elif mdt.kind in "fiub":
+        cplx = False
+    else:
+        raise ArgumentError(f"{fn}: unsupported mask dtype {mdt}")
+    if dev and mdt not in (np.dtype(np.float32), np.dtype(np.complex64)):
+        raise ArgumentError(f"{fn}: device mask must be float32 or complex64")
+    if len(zshape) < 2 or len(mshape) < 2:
+        raise ArgumentError(f"{fn} expects tensors of shape {{..., frames, frequencies}}")
+    M, K = int(zshape[-2]), int(zshape[-1])
+    if M < 1 or K < 1:
+        raise ArgumentError(f"{fn}: the spectrum needs at least one frame and one bin")
+    if int(mshape[-2]) != M:
+        raise ArgumentError(f"{fn}: mask has {int(mshape[-2])} frames, the spectrum {M}")
+    Km = int(mshape[-1])
+    if Km == K:
+        kind = _MASK_COMPLEX if cplx else _MASK_REAL
+    elif Km == K // 2 + 1 and K % 2 == 0:
+        if cplx:
+            raise ArgumentError(f"{fn}: a one-sided mask must be real")
+        kind = _MASK_ONESIDED
+    elif K % 2 == 1 and Km == K // 2 + 1:
+        raise ArgumentError(f"{fn}: a one-sided mask needs an even fft_length, got {K}")
+    else:
+        raise ArgumentError(f"{fn}: the mask's last axis must be fft_length ({K}) or fft_length / 2 + 1, got {Km}")
+    Bz = int(np.prod(zshape[:-2], dtype=np.int64)) if len(zshape) > 2 else 1
+    Bm = int(np.prod(mshape[:-2], dtype=np.int64)) if len(mshape) > 2 else 1
+    if Bz != Bm and Bz != 1 and Bm != 1:
+        raise ArgumentError(f"{fn}: z has {Bz} rows and mask {Bm}: they must be equal, or one of them 1")
+    if max(Bz, Bm) < 1:
+        raise ArgumentError(f"{fn}: empty leading axes")
+    if max(Bz, Bm) > 65535:
+        raise ArgumentError(f"{fn}: at most 65535 rows")
+    # the leading shape of whichever operand carries the rows (the spectrum's when both do)
+    lead = tuple(zshape[:-2]) if (Bz >= Bm and (Bz > 1 or len(zshape) >= len(mshape))) else tuple(mshape[:-2])
+    if not dev:
+        zv = np.ascontiguousarray(zv.astype(np.complex64))
+        mv = np.ascontiguousarray(mv.astype(np.complex64 if cplx else np.float32))
+    return dev, zv, mv, (M, K), kind, (Bz, Bm), tuple(int(d) for d in lead)
+
+
+def spectrum_mask(z, mask, ctx: Context | None = None):
+    """Extension: `Nx.multiply(z, mask)` for a time-frequency mask kept on the device.  z c64[..., M, K]; mask f32[..., M, K],
+    c64[..., M, K] or the one-sided real f32[..., M, K/2 + 1] (bin k > K/2 takes mask[K - k]).  The flattened leading axes are equal
+    or one of them is 1 (broadcast: one mixture and S masks).  Complex masks multiply like spectrum_multiply; a real gain
+    multiplies each component on its own, in double with one rounding.  -> c64[lead..., M, K], host or DeviceBuffer like the inputs."""
+    dev, zv, mv, (M, K), kind, (Bz, Bm), lead = _mask_operands(z, mask, "spectrum_mask")
+    lib = _lib.load()
+    c = _ctx_of(z if isinstance(z, DeviceBuffer) else (mask if isinstance(mask, DeviceBuffer) else None), ctx)
+    if dev:
+        out = c.empty(lead + (M, K), np.complex64)
+        _lib.check(lib.nxsig_spectrum_mask_c64(c.handle, C.c_void_p(zv[0]), Bz, C.c_void_p(mv[0]), kind, Bm, M, K,
+                                               C.c_void_p(out.ptr), _lib.DEVICE))
+        return out
+    out = np.empty(lead + (M, K), dtype=np.complex64)
+    _lib.check(lib.nxsig_spectrum_mask_c64(c.handle, _as_ptr(zv), Bz, _as_ptr(mv), kind, Bm, M, K, _as_ptr(out), _lib.HOST))
+    return out
+
+
+def istft_masked(z, mask, window, ctx: Context | None = None, **opts):
+    """Extension: `istft(Nx.multiply(z, mask), window, opts)` in one call — the denoising / source-separation / spectral-gating step.
+    Operands as in spectrum_mask, options, defaults and errors as in istft.  Bit-identical to
+    `istft(spectrum_mask(z, mask), window, **opts)`; for 1024-point frames at hop 128 / 256 / 512 / 1024 the mask rows stream into
+    the inverse-STFT kernel next to the spectrum and the masked spectrogram never exists in HBM."""
+    window = _as_tensor(window)
+    o, w, N, hop, fs = _istft_options(window, opts)
+    if w.dtype == np.float64:
+        raise ArgumentError("istft_masked is an f32 extension: an f64 window is not taken")
+    dev, zv, mv, (M, K), kind, (Bz, Bm), lead = _mask_operands(z, mask, "istft_masked")
+    K = _istft_fft_length(o, K)
+    if K != N:
+        raise ArgumentError("istft: fft_length must equal the window length (the reference broadcasts {M,K} x {N}, lib/nx_signal.ex:628)")
+    lib = _lib.load()
+    c = _ctx_of(z if isinstance(z, DeviceBuffer) else (mask if isinstance(mask, DeviceBuffer) else None), ctx)
+    p = StftParams(N, hop, K, 0, 0, 0, _SCALING[o["scaling"]], 0, fs)
+    out_len = _lib.check(lib.nxsig_ola_length(M, N, hop))
+    if dev:
+        y = c.empty(lead + (out_len,), np.complex64)
+        _lib.check(lib.nxsig_istft_masked_c64(c.handle, C.c_void_p(zv[0]), Bz, M, _as_ptr(w), C.byref(p), C.c_void_p(mv[0]), kind, Bm,
+                                              C.c_void_p(y.ptr), _lib.DEVICE))
+        return y
+    y = np.empty(lead + (out_len,), dtype=np.complex64)
+    _lib.check(lib.nxsig_istft_masked_c64(c.handle, _as_ptr(zv), Bz, M, _as_ptr(w), C.byref(p), _as_ptr(mv), kind, Bm, _as_ptr(y), _lib.HOST))
+    return y
 
 
 def mel_spectrogram(data, window, ctx: Context | None = None, **opts):

@@ -47,6 +47,7 @@ UNITS = [
     ("kernels_wave_fir32.hip", []),
     ("kernels_wave_firlong.hip", []),  # 1 026 ... 32 769 taps: uniformly partitioned frequency-domain delay line (round 6)
     ("kernels_wave_packed.hip", []),
+    ("kernels_wave_mask.hip", []),  # istft with a time-frequency mask fused in (N = 1024)
     ("kernels_f64.hip", []),  # the f64 / c128 tier (workgroup-per-frame kernels in double)
     ("kernels_filters.hip", []),  # Filters.median / wiener (no FMA contraction: the file says so itself)
     ("kernels_peaks.hip", []),  # PeakFinding.argrelextrema / nonzero: mark, scan, compact

@@ -227,7 +227,10 @@ int launch_istft(Ctx* c, const IstftLaunch& a, const float* window_host) {
     for (int32_t r0 = 0; r0 < a.batch; r0 += kSlabRows) {
       IstftLaunch b = a;
       b.batch = a.batch - r0 < kSlabRows ? a.batch - r0 : kSlabRows;
-      b.z = a.z + (size_t)r0 * a.M * a.K;
+      b.z = a.z + (a.z_bcast ? 0 : (size_t)r0 * a.M * a.K);
+      if (a.mask && !a.mask_bcast)
+        b.mask = reinterpret_cast<const char*>(a.mask) +
+                 (size_t)r0 * a.M * mask_row_len(a.mask_kind, a.K) * (a.mask_kind == NXSIG_MASK_COMPLEX ? sizeof(float2) : sizeof(float));
       b.y = a.y + (size_t)r0 * out_len;
       int rc2 = launch_istft(c, b, window_host);
       if (rc2) return rc2;
@@ -253,8 +256,18 @@ int launch_istft(Ctx* c, const IstftLaunch& a, const float* window_host) {
     if ((rc = launch_istft(c, b, window_host))) return rc;
     return launch_real_from_c64(c, b.y, (int64_t)a.batch * out_len, reinterpret_cast<float*>(a.y));
   }
-  rc = launch_istft_wave(c, a, window_host, &handled);
+  rc = a.mask ? launch_istft_wave_mask(c, a, window_host, &handled) : launch_istft_wave(c, a, window_host, &handled);
   if (rc) return rc;
+  if (!handled && a.mask) {
+    // no fused kernel for this geometry: the masked spectrogram is materialised once (the two-step chain), then the size's own inverse runs
+    void* zf = nullptr;
+    if ((rc = ctx_scratch(c, 20, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
+    if ((rc = launch_spectrum_mask(c, a.z, a.z_bcast, a.mask, a.mask_kind, a.mask_bcast, a.batch, a.M, a.K, reinterpret_cast<float2*>(zf)))) return rc;
+    IstftLaunch b = a;
+    b.z = reinterpret_cast<const float2*>(zf);
+    b.mask = nullptr; b.z_bcast = false; b.mask_bcast = false;
+    return launch_istft(c, b, window_host);
+  }
   if (!handled && a.filt) {
     // no fused kernel for this geometry: the filter product is materialised once (the two-step chain), then the plain path runs
     void* zf = nullptr;
@@ -1105,8 +1118,32 @@ int nxsig_stft_c64(nxsig_ctx* ctx, const nxsig_c64* x, int64_t length, int32_t b
   NXSIG_API_END
 }
 
+// the operands of a time-frequency mask (nxsig_spectrum_mask_c64 / nxsig_istft_masked_c64)
+struct MaskOperand {
+  const void* mask = nullptr;
+  int32_t kind = 0, z_rows = 1, mask_rows = 1;
+};
+static int check_mask(const char* fn, const MaskOperand& mo, int32_t K, int32_t* rows) {
+  const std::string f(fn);
+  if (!mo.mask) return set_error(NXSIG_ERR_INVALID_ARG, f + ": null mask");
+  if (mo.kind != NXSIG_MASK_REAL && mo.kind != NXSIG_MASK_ONESIDED && mo.kind != NXSIG_MASK_COMPLEX)
+    return set_error(NXSIG_ERR_INVALID_ARG, f + ": mask_kind must be NXSIG_MASK_REAL, NXSIG_MASK_ONESIDED or NXSIG_MASK_COMPLEX");
+  if (mo.kind == NXSIG_MASK_ONESIDED && (K & 1)) return set_error(NXSIG_ERR_INVALID_ARG, f + ": a one-sided mask needs an even fft_length");
+  if (mo.z_rows < 1 || mo.mask_rows < 1) return set_error(NXSIG_ERR_INVALID_ARG, f + ": z_rows and mask_rows must be >= 1");
+  if (mo.z_rows != mo.mask_rows && mo.z_rows != 1 && mo.mask_rows != 1)
+    return set_error(NXSIG_ERR_INVALID_ARG, f + ": z_rows and mask_rows must be equal, or one of them 1, got " + std::to_string(mo.z_rows) +
+                                                " and " + std::to_string(mo.mask_rows));
+  *rows = mo.z_rows > mo.mask_rows ? mo.z_rows : mo.mask_rows;
+  if (*rows > 65535) return set_error(NXSIG_ERR_INVALID_ARG, f + ": at most 65535 rows");
+  return NXSIG_OK;
+}
+static size_t mask_bytes(const MaskOperand& mo, int64_t num_frames, int32_t K) {
+  return (size_t)mo.mask_rows * num_frames * mask_row_len(mo.kind, K) * (mo.kind == NXSIG_MASK_COMPLEX ? sizeof(float2) : sizeof(float));
+}
+
 static int istft_common(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_frames, int32_t batch, const float* window,
-                        const nxsig_stft_params* p, const nxsig_c64* h, nxsig_c64* y, int32_t mem, bool onesided = false) {
+                        const nxsig_stft_params* p, const nxsig_c64* h, nxsig_c64* y, int32_t mem, bool onesided = false,
+                        const MaskOperand* mo = nullptr) {
   NXSIG_CHECK_CTX(ctx)
   DispatchScope dispatch_scope(c);
   if (!z || !window || !p || !y) return set_error(NXSIG_ERR_INVALID_ARG, "istft: null pointer argument");
@@ -1139,8 +1176,12 @@ static int istft_common(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_frames, 
     a.filt = reinterpret_cast<const float2*>(hd);
   }
   const int64_t out_len = num_frames * hop + (N - hop);
-  const size_t zbytes = (size_t)batch * num_frames * (onesided ? K / 2 : K) * sizeof(float2);
+  const size_t zbytes = (size_t)(mo ? mo->z_rows : batch) * num_frames * (onesided ? K / 2 : K) * sizeof(float2);
   const size_t ybytes = (size_t)batch * out_len * (onesided ? sizeof(float) : sizeof(float2));
+  if (mo) {
+    a.mask = mo->mask; a.mask_kind = mo->kind;
+    a.z_bcast = mo->z_rows == 1 && batch > 1; a.mask_bcast = mo->mask_rows == 1 && batch > 1;
+  }
   if (mem == NXSIG_DEVICE) {
     a.z = reinterpret_cast<const float2*>(z); a.y = reinterpret_cast<float2*>(y);
     return launch_istft(c, a, window);
@@ -1148,6 +1189,7 @@ static int istft_common(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_frames, 
   Staged st(c);
   const void* zd = nullptr; void* yd = nullptr;
   if ((rc = st.in(1, z, zbytes, &zd))) return rc;
+  if (mo && (rc = st.in(17, mo->mask, mask_bytes(*mo, num_frames, K), &a.mask))) return rc;
   if ((rc = st.out_alloc(2, ybytes, &yd))) return rc;
   a.z = reinterpret_cast<const float2*>(zd); a.y = reinterpret_cast<float2*>(yd);
   if ((rc = launch_istft(c, a, window))) return rc;
@@ -1173,6 +1215,49 @@ int nxsig_istft_filtered_c64(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_fra
   NXSIG_API_BEGIN
   if (!h) return set_error(NXSIG_ERR_INVALID_ARG, "istft_filtered: null filter spectrum");
   return istft_common(ctx, z, num_frames, batch, window, p, h, y, mem);
+  NXSIG_API_END
+}
+
+int nxsig_istft_masked_c64(nxsig_ctx* ctx, const nxsig_c64* z, int32_t z_rows, int64_t num_frames, const float* window,
+                           const nxsig_stft_params* p, const void* mask, int32_t mask_kind, int32_t mask_rows, nxsig_c64* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  if (!p) return set_error(NXSIG_ERR_INVALID_ARG, "istft: null pointer argument");
+  MaskOperand mo;
+  mo.mask = mask; mo.kind = mask_kind; mo.z_rows = z_rows; mo.mask_rows = mask_rows;
+  int32_t rows = 0;
+  int rc = check_mask("istft_masked", mo, p->fft_length, &rows);
+  if (rc) return rc;
+  return istft_common(ctx, z, num_frames, rows, window, p, nullptr, y, mem, false, &mo);
+  NXSIG_API_END
+}
+
+int nxsig_spectrum_mask_c64(nxsig_ctx* ctx, const nxsig_c64* z, int32_t z_rows, const void* mask, int32_t mask_kind, int32_t mask_rows,
+                            int64_t num_frames, int32_t fft_length, nxsig_c64* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!z || !out) return set_error(NXSIG_ERR_INVALID_ARG, "spectrum_mask: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (num_frames < 1 || fft_length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "spectrum_mask: num_frames and fft_length must be >= 1");
+  MaskOperand mo;
+  mo.mask = mask; mo.kind = mask_kind; mo.z_rows = z_rows; mo.mask_rows = mask_rows;
+  int32_t rows = 0;
+  if ((rc = check_mask("spectrum_mask", mo, fft_length, &rows))) return rc;
+  const bool zb = z_rows == 1 && rows > 1, mb = mask_rows == 1 && rows > 1;
+  const size_t zbytes = (size_t)z_rows * num_frames * fft_length * sizeof(float2);
+  const size_t obytes = (size_t)rows * num_frames * fft_length * sizeof(float2);
+  if (mem == NXSIG_DEVICE)
+    return launch_spectrum_mask(c, reinterpret_cast<const float2*>(z), zb, mask, mask_kind, mb, rows, num_frames, fft_length,
+                                reinterpret_cast<float2*>(out));
+  Staged st(c);
+  const void *zd = nullptr, *md = nullptr; void* od = nullptr;
+  if ((rc = st.in(1, z, zbytes, &zd))) return rc;
+  if ((rc = st.in(17, mask, mask_bytes(mo, num_frames, fft_length), &md))) return rc;
+  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
+  if ((rc = launch_spectrum_mask(c, reinterpret_cast<const float2*>(zd), zb, md, mask_kind, mb, rows, num_frames, fft_length,
+                                 reinterpret_cast<float2*>(od)))) return rc;
+  return st.out_copy(out, od, obytes);
   NXSIG_API_END
 }
 

@@ -437,6 +437,19 @@ struct EdgeFixArgs {
   int32_t onesided = 0;     // 1: z is the packed half spectrum c64[batch][M][N / 2] (Re X[N/2] in the imaginary part of bin 0)
                             //    and y is REAL f32[batch][out_len] (nxsig_istft_packed_f32)
 };
+// the masked istft (IstftLaunch::mask): bin k of frame m of row r is z * mask rounded to c64 first.  A parameter of its own, of the
+// MASK instantiations of the fix-up kernels only: the kernels behind every other istft keep their arguments, registers and occupancy
+struct EdgeMask {
+  const void* mask = nullptr;
+  int32_t kind = 0;              // nxsig_mask_kind
+  int64_t z_row_stride = 0;      // c64 between rows of z (0: one row for every output row)
+  int64_t mask_row_stride = 0;   // mask elements between rows of the mask (0 likewise)
+};
+// the mask row of frame m of row `row` (MASK instantiations)
+__device__ __forceinline__ const void* edge_mask_row(const EdgeMask& mk, int N, int64_t row, int64_t m) {
+  const int msz = mk.kind == NXSIG_MASK_COMPLEX ? 8 : 4;
+  return reinterpret_cast<const char*>(mk.mask) + ((size_t)row * mk.mask_row_stride + (size_t)m * mask_row_len(mk.kind, N)) * msz;
+}
 // bin k of frame row zr in either layout
 __device__ __forceinline__ float2 istft_bin(const EdgeFixArgs& a, const float2* __restrict__ zr, int k) {
   if (!a.onesided) return zr[k];
@@ -452,15 +465,18 @@ __device__ __forceinline__ float2 istft_bin(const EdgeFixArgs& a, const float2* 
 // time in an 8-level LDS reduction with barriers; a wave keeps N / 64 terms per lane in flight and reduces with six shuffles, and four
 // times as many samples are resident per CU — the pass after config 3's kernel went from 15.6 to 10.6 us in rocprofv3, together with the twiddle recurrence below).
 // the sum itself: frames m_lo .. m_hi cover sample n, d = the guarded normaliser
+template <bool MASK>
 __device__ __forceinline__ void istft_sample_body(const EdgeFixArgs& a, const int64_t row, const int64_t n, const int64_t m_lo, const int64_t m_hi,
-                                                  const float d) {
+                                                  const float d, const EdgeMask& mk) {
   const int lane = threadIdx.x & 63;
   const int rowlen = a.onesided ? (a.N >> 1) : a.N;
-  const float2* zb = a.z + (size_t)row * a.M * rowlen;
+  const float2* zb = a.z + (MASK ? (size_t)row * mk.z_row_stride : (size_t)row * a.M * rowlen);
   double acc_re = 0.0, acc_im = 0.0;
   for (int64_t m = m_lo; m <= m_hi; ++m) {
     const int j = (int)(n - m * a.hop);
     const float2* zr = zb + (size_t)m * rowlen;
+    const void* mr = nullptr;
+    if constexpr (MASK) mr = edge_mask_row(mk, a.N, row, m);
     double sr = 0.0, si = 0.0;
     // twiddle index j k mod N, advanced without a division per term (32-bit: j < N, and N < 2^24 for every caller)
     int tix = a.N < (1 << 24) ? (int)((uint32_t)(j * lane) % (uint32_t)a.N) : (int)(((int64_t)j * lane) % a.N);
@@ -471,6 +487,7 @@ __device__ __forceinline__ void istft_sample_body(const EdgeFixArgs& a, const in
         v = make_float2((float)((double)v.x * (double)h.x - (double)v.y * (double)h.y),
                         (float)((double)v.x * (double)h.y + (double)v.y * (double)h.x));
       }
+      if constexpr (MASK) v = spectrum_mask_apply(v, mr, mk.kind, k, a.N);
       sr += (double)v.x * t.x - (double)v.y * t.y;
       si += (double)v.x * t.y + (double)v.y * t.x;
     };
@@ -518,8 +535,8 @@ __device__ __forceinline__ void istft_sample_body(const EdgeFixArgs& a, const in
 }
 
 // ALL = false: only ill-conditioned samples (1e-10 < den < tau) are recomputed; true: any sample (den <= 1e-10 divides by 1, :635)
-template <bool ALL>
-__device__ __forceinline__ void istft_sample_f64(const EdgeFixArgs& a, const int64_t row, const int64_t n) {
+template <bool ALL, bool MASK>
+__device__ __forceinline__ void istft_sample_f64(const EdgeFixArgs& a, const int64_t row, const int64_t n, const EdgeMask& mk) {
   int64_t m_hi = n / a.hop;
   if (m_hi > a.M - 1) m_hi = a.M - 1;
   const int64_t m_lo = (n - a.N + 1 <= 0) ? 0 : (n - a.N + a.hop) / a.hop;
@@ -531,7 +548,7 @@ __device__ __forceinline__ void istft_sample_f64(const EdgeFixArgs& a, const int
   float d = (float)den;
   if (ALL) { if (!(d > 1.0e-10f)) d = 1.0f; }
   else if (!(d > 1.0e-10f) || d >= a.tau) return;  // uniform across the wave
-  istft_sample_body(a, row, n, m_lo, m_hi, d);
+  istft_sample_body<MASK>(a, row, n, m_lo, m_hi, d, mk);
 }
 
 constexpr int kFixWaves = kThreads / 64;   // samples per workgroup of the two fix-up kernels
@@ -549,8 +566,9 @@ constexpr int kFixWaves = kThreads / 64;   // samples per workgroup of the two f
 //    list[0] = number of entries appended (may exceed the capacity list[1]); entries follow as int64 from list + 2; list[-2] is a
 //    ticket: the workgroup that finishes last puts the count back to zero, so an empty list (every call but the poisoned ones) costs
 //    one load per workgroup and nothing is cleared between calls.
-__global__ __launch_bounds__(kThreads) void k_istft_edge_fix(EdgeFixArgs a, int64_t edge_blocks, int* __restrict__ list, int32_t frames_per_unit,
-                                                             int32_t nf_blocks) {
+template <bool MASK>
+__device__ __forceinline__ void istft_edge_fix_body(const EdgeFixArgs& a, int64_t edge_blocks, int* __restrict__ list, int32_t frames_per_unit,
+                                                    int32_t nf_blocks, const EdgeMask& mk) {
   const int wave = threadIdx.x >> 6;
   const int64_t b = blockIdx.x;
   if (b < edge_blocks * a.batch) {
@@ -559,9 +577,9 @@ __global__ __launch_bounds__(kThreads) void k_istft_edge_fix(EdgeFixArgs a, int6
     if (a.idx) {
       if (i >= a.n_idx) return;
       const int64_t* e = a.idx + 4 * i;
-      istft_sample_body(a, row, e[0], e[1], e[2], __int_as_float((int)e[3]));
+      istft_sample_body<MASK>(a, row, e[0], e[1], e[2], __int_as_float((int)e[3]), mk);
     } else if (i < a.out_len) {
-      istft_sample_f64<false>(a, row, i);
+      istft_sample_f64<false, MASK>(a, row, i, mk);
     }
     return;
   }
@@ -576,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void k_istft_edge_fix(EdgeFixArgs a, int6
     const int64_t e = wk / span, si = wk - e * span;
     const int64_t row = ent[e] >> 40, m0 = ent[e] & (((int64_t)1 << 40) - 1);
     const int64_t n = m0 * a.hop + si;
-    if (row < a.batch && n < a.out_len) istft_sample_f64<true>(a, row, n);
+    if (row < a.batch && n < a.out_len) istft_sample_f64<true, MASK>(a, row, n, mk);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -586,6 +604,15 @@ __global__ __launch_bounds__(kThreads) void k_istft_edge_fix(EdgeFixArgs a, int6
       atomicExch(list - 2, 0);
     }
   }
+}
+__global__ __launch_bounds__(kThreads) void k_istft_edge_fix(EdgeFixArgs a, int64_t edge_blocks, int* __restrict__ list, int32_t frames_per_unit,
+                                                             int32_t nf_blocks) {
+  istft_edge_fix_body<false>(a, edge_blocks, list, frames_per_unit, nf_blocks, EdgeMask{});
+}
+// the same pass behind the masked istft (launch_istft_wave_mask: one frame per transform, so only the edge role has work)
+__global__ __launch_bounds__(kThreads) void k_istft_edge_fix_mask(EdgeFixArgs a, int64_t edge_blocks, int* __restrict__ list,
+                                                                  int32_t frames_per_unit, int32_t nf_blocks, EdgeMask mk) {
+  istft_edge_fix_body<true>(a, edge_blocks, list, frames_per_unit, nf_blocks, mk);
 }
 
 // ---- the edge role for N = A SP, SP in {2, 4, 8, 16, 32}, A <= 64 lanes (round 5; the text below says 64 for A).  k_istft_edge_fix spends N / 64 complex multiply-adds plus a
@@ -600,8 +627,15 @@ __global__ __launch_bounds__(kThreads) void k_istft_edge_fix(EdgeFixArgs a, int6
 // over the frames in double, divide by the normaliser: lib/nx_signal.ex:609-637).  Same roundings as istft_sample_body except for the
 // order of the double sums.  Chunk entry (20 x int64, host-built): n0, m_lo, m_hi, mask of the flagged positions, then the bits of the
 // f32 normalisers, two per int64.
-template <int SP>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SP >= 32 ? 1 : 2, 8))) void k_istft_edge_chunks(EdgeFixArgs a, int64_t chunk_blocks) {
+// MK: nothing, or one EdgeMask (the masked istft).  A parameter pack, so that the instantiation behind every other istft keeps the
+// argument list it had and its body stays the kernel's own (moved into a helper it compiled to more scratch)
+__device__ __forceinline__ EdgeMask edge_mask_of() { return EdgeMask{}; }
+__device__ __forceinline__ EdgeMask edge_mask_of(const EdgeMask& m) { return m; }
+template <int SP, typename... MK>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SP >= 32 ? 1 : 2, 8))) void k_istft_edge_chunks(EdgeFixArgs a, int64_t chunk_blocks, MK... mkp) {
+  constexpr bool MASK = sizeof...(MK) != 0;
+  static_assert(sizeof...(MK) <= 1, "at most one EdgeMask");
+  const EdgeMask mk = edge_mask_of(mkp...);
   constexpr int LOG = SP == 2 ? 1 : SP == 4 ? 2 : SP == 8 ? 3 : SP == 16 ? 4 : 5;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t b = blockIdx.x;
@@ -615,12 +649,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SP >= 
   const bool mine = ((mask >> g) & 1u) != 0;
   const int N = a.N, rowlen = a.onesided ? (N >> 1) : N;
   const int A = N / SP;                                  // active lanes: bin k = lane + A s
-  const float2* zb = a.z + (size_t)row * a.M * rowlen;
+  const float2* zb = a.z + (MASK ? (size_t)row * mk.z_row_stride : (size_t)row * a.M * rowlen);
   double acc_re = 0.0, acc_im = 0.0;
   for (int64_t m = m_lo; m <= m_hi; ++m) {
     const int64_t j0 = n0 - m * a.hop;                   // may be negative for positions outside the mask
     const int rot = (int)(((j0 % SP) + SP) % SP);        // uniform
     const float2* zr = zb + (size_t)m * rowlen;
+    const void* mr = nullptr;
+    if constexpr (MASK) mr = edge_mask_row(mk, N, row, m);
     double2 x[SP];
 #pragma unroll
     for (int s = 0; s < SP; ++s) {
@@ -630,6 +666,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SP >= 
         v = make_float2((float)((double)v.x * (double)h.x - (double)v.y * (double)h.y),
                         (float)((double)v.x * (double)h.y + (double)v.y * (double)h.x));
       }
+      if constexpr (MASK) { if (lane < A) v = spectrum_mask_apply(v, mr, mk.kind, lane + A * s, N); }
       x[s] = make_double2((double)v.x, (double)v.y);
     }
     if (rot != 0) {   // x_s *= e^(2 pi i rot s / SP) = w_N^(64 rot s)
@@ -895,6 +932,23 @@ __global__ __launch_bounds__(kThreads) void k_spectrum_mul(const float2* __restr
     const double re = (double)a.x * (double)b.x - (double)a.y * (double)b.y;
     const double im = (double)a.x * (double)b.y + (double)a.y * (double)b.x;
     out[i] = make_float2((float)re, (float)im);
+  }
+}
+
+// out[r][m][k] = z[r or 0][m][k] * mask[r or 0][m][k] (Nx.multiply(z, mask) with a time-frequency mask, nxsig_spectrum_mask_c64): the
+// two-step form of the masked istft and a call of its own.  per_z / per_mask: elements of one row of that operand, 0 when it is
+// broadcast over the rows.  One workgroup walks whole frames, so the frame's mask row is addressed once
+__global__ __launch_bounds__(kThreads) void k_spectrum_mask(const float2* __restrict__ z, const void* __restrict__ mask, float2* __restrict__ out,
+                                                            int64_t frames_total, int64_t M, int32_t K, int32_t kind, int64_t per_z,
+                                                            int64_t per_mask) {
+  const int msz = kind == NXSIG_MASK_COMPLEX ? 8 : 4;
+  const int64_t mlen = mask_row_len(kind, K);
+  for (int64_t f = blockIdx.x; f < frames_total; f += gridDim.x) {
+    const int64_t r = f / M, m = f - r * M;
+    const float2* zr = z + (size_t)r * per_z + (size_t)m * K;
+    const void* mr = reinterpret_cast<const char*>(mask) + ((size_t)r * per_mask + (size_t)m * mlen) * msz;
+    float2* o = out + (size_t)f * K;
+    for (int k = threadIdx.x; k < K; k += kThreads) o[k] = spectrum_mask_apply(zr[k], mr, kind, k, K);
   }
 }
 
@@ -1688,6 +1742,12 @@ int launch_istft_fix(Ctx* c, const IstftLaunch& s, const float* window_host) {
   EdgeFixArgs a;
   a.z = s.z; a.filt = s.filt; a.M = s.M; a.N = N; a.hop = hop; a.window = s.window; a.scale = s.scale_mul; a.has_scale = s.has_scale;
   a.y = s.y; a.out_len = out_len; a.onesided = s.onesided ? 1 : 0; a.batch = s.batch;
+  EdgeMask mk;
+  if (s.mask) {
+    mk.mask = s.mask; mk.kind = s.mask_kind;
+    mk.z_row_stride = s.z_bcast ? 0 : s.M * (int64_t)N;
+    mk.mask_row_stride = s.mask_bcast ? 0 : s.M * mask_row_len(s.mask_kind, N);
+  }
   a.idx = nullptr; a.n_idx = 0; a.tau = 0.0f; a.tw = nullptr;
   // which samples are candidates is a pure function of (window, hop, M): memoised per context as {mode, tau bits, idx, n_idx}
   // key = hash of (hop, M, N) AS DATA followed by the window's content (shifting them into the seed aliased for large M / hop)
@@ -1783,12 +1843,17 @@ int launch_istft_fix(Ctx* c, const IstftLaunch& s, const float* window_host) {
     const int64_t chunk_blocks = (a.n_idx + kFixWaves - 1) / kFixWaves;
     const int64_t blocks = chunk_blocks * s.batch;
     if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "istft: signal too long for the edge fix-up grid");
+    dispatch_note("istft.edge_chunks");
+    auto chunks = [&](auto plain, auto masked) {
+      if (s.mask) hipLaunchKernelGGL(masked, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks, mk);
+      else hipLaunchKernelGGL(plain, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks);
+    };
     switch ((int)(mode >> 4)) {
-      case 2: dispatch_note("istft.edge_chunks"); hipLaunchKernelGGL(k_istft_edge_chunks<2>, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks); break;
-      case 4: dispatch_note("istft.edge_chunks"); hipLaunchKernelGGL(k_istft_edge_chunks<4>, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks); break;
-      case 8: dispatch_note("istft.edge_chunks"); hipLaunchKernelGGL(k_istft_edge_chunks<8>, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks); break;
-      case 16: dispatch_note("istft.edge_chunks"); hipLaunchKernelGGL(k_istft_edge_chunks<16>, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks); break;
-      default: dispatch_note("istft.edge_chunks"); hipLaunchKernelGGL(k_istft_edge_chunks<32>, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, chunk_blocks); break;
+      case 2: chunks(k_istft_edge_chunks<2>, k_istft_edge_chunks<2, EdgeMask>); break;
+      case 4: chunks(k_istft_edge_chunks<4>, k_istft_edge_chunks<4, EdgeMask>); break;
+      case 8: chunks(k_istft_edge_chunks<8>, k_istft_edge_chunks<8, EdgeMask>); break;
+      case 16: chunks(k_istft_edge_chunks<16>, k_istft_edge_chunks<16, EdgeMask>); break;
+      default: chunks(k_istft_edge_chunks<32>, k_istft_edge_chunks<32, EdgeMask>); break;
     }
     NXSIG_HIP_TRY(hipGetLastError());
     if (!s.nf_list) return NXSIG_OK;
@@ -1800,8 +1865,12 @@ int launch_istft_fix(Ctx* c, const IstftLaunch& s, const float* window_host) {
   const int64_t blocks = edge_blocks * s.batch + nf_blocks;
   if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "istft: signal too long for the edge fix-up grid");
   dispatch_note("istft.edge_fix");
-  hipLaunchKernelGGL(k_istft_edge_fix, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, edge_blocks, s.nf_list,
-                     (int32_t)s.nf_frames_per_unit, nf_blocks);
+  if (s.mask)
+    hipLaunchKernelGGL(k_istft_edge_fix_mask, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, edge_blocks, s.nf_list,
+                       (int32_t)s.nf_frames_per_unit, nf_blocks, mk);
+  else
+    hipLaunchKernelGGL(k_istft_edge_fix, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, a, edge_blocks, s.nf_list,
+                       (int32_t)s.nf_frames_per_unit, nf_blocks);
   NXSIG_HIP_TRY(hipGetLastError());
   return NXSIG_OK;
 }
@@ -1836,6 +1905,20 @@ int launch_spectrum_mul(Ctx* c, const float2* z, int64_t rows, int32_t K, const 
   if (blocks > cap) blocks = cap;
   dispatch_note("spectrum_mul");
   hipLaunchKernelGGL(k_spectrum_mul, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, z, h_dev, out, total, K);
+  NXSIG_HIP_TRY(hipGetLastError());
+  return NXSIG_OK;
+}
+
+int launch_spectrum_mask(Ctx* c, const float2* z, bool z_bcast, const void* mask, int32_t kind, bool mask_bcast, int64_t rows, int64_t M,
+                         int32_t K, float2* out) {
+  const int64_t frames = rows * M;
+  if (frames == 0 || K == 0) return NXSIG_OK;
+  int64_t blocks = frames;
+  const int64_t cap = (int64_t)c->num_cus * 32;
+  if (blocks > cap) blocks = cap;
+  dispatch_note("spectrum_mask");
+  hipLaunchKernelGGL(k_spectrum_mask, dim3((unsigned)blocks), dim3(kThreads), 0, c->stream, z, mask, out, frames, M, K, kind,
+                     z_bcast ? (int64_t)0 : M * (int64_t)K, mask_bcast ? (int64_t)0 : M * mask_row_len(kind, K));
   NXSIG_HIP_TRY(hipGetLastError());
   return NXSIG_OK;
 }

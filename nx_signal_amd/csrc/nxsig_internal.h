@@ -75,7 +75,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
 // tools, tests); nothing in a launch path looks at the process environment.  Names are the NXSIG_<NAME> variables of
 // INTEGRATION.md.  The knobs of concluded experiments are gone (round 4): their winning value is a constant at the use site.
 #define NXSIG_TUNABLES(X)                                                                                                      \
-  X(DISABLE_WAVE) X(DISABLE_WAVE_ROWS) X(DISABLE_BLUE_WAVE) X(DISABLE_R20) X(DISABLE_RAB) X(DISABLE_8K) X(DISABLE_4K) X(DISABLE_FUSED_FILTER) \
+  X(DISABLE_WAVE) X(DISABLE_WAVE_ROWS) X(DISABLE_BLUE_WAVE) X(DISABLE_R20) X(DISABLE_RAB) X(DISABLE_8K) X(DISABLE_4K) X(DISABLE_FUSED_FILTER) X(DISABLE_FUSED_MASK) \
   X(ISTFT_DEEP) X(ISTFT_HALF_DEEP) X(ISTFT_RUNS_PER_CU) X(ISTFT_MIN_RUN) X(ISTFT_REGOLA)                                                    \
   X(STORE_POLICY) X(WAVE_NO_SPLIT) X(NO_AL8) X(NO_STAGE) X(WAVE_UNITS_PER_WAVE) X(STAGE_PAD) X(NO_HOP4) X(WAVE_SMALL_W) X(WAVE_SMALL_CHUNK) \
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
@@ -228,6 +228,11 @@ struct IstftLaunch {
   float2* y;             // device c64[batch][M*hop + N-hop]
   const float2* filt = nullptr;  // optional device c64[K]: every frame's spectrum is multiplied by it first (z * H of the
                                  // STFT-domain filtering chain, guides/filtering.livemd:141), rounded to c64 like Nx.multiply
+  // optional time-frequency mask (nxsig_istft_masked_c64): frame m of row r is z[r][m][k] * mask[r][m][k] rounded to c64 first.
+  // mask_kind: nxsig_mask_kind.  z_bcast / mask_bcast: that operand has ONE row, read for every row of the batch (row stride 0)
+  const void* mask = nullptr;
+  int32_t mask_kind = 0;
+  bool z_bcast = false, mask_bcast = false;
   // set by a wave launcher whose kernel inverts several frames with ONE transform: the device list of units that hold a
   // non-finite bin and the frames per unit; launch_istft then recomputes those units' samples frame by frame (k_istft_edge_fix's second role)
   mutable int* nf_list = nullptr;
@@ -236,6 +241,23 @@ struct IstftLaunch {
   // part of bin 0 — and y is REAL f32[batch][M*hop + N-hop]
   bool onesided = false;
 };
+// elements (f32 or c64, by kind) of one mask row of one frame
+__host__ __device__ __forceinline__ int64_t mask_row_len(int32_t kind, int32_t K) { return kind == NXSIG_MASK_ONESIDED ? K / 2 + 1 : K; }
+// one bin of a masked spectrum: the product Nx.multiply forms on the BinaryBackend (double, one rounding per component); a real
+// gain multiplies each component on its own.  mrow: the mask row of the bin's (row, frame).  Shared by k_spectrum_mask, the fused
+// kernel and the edge fix-up, so that every path rounds alike
+__device__ __forceinline__ float2 spectrum_mask_apply(float2 v, const void* mrow, int32_t kind, int32_t k, int32_t K) {
+  if (kind == NXSIG_MASK_COMPLEX) {
+    const float2 h = reinterpret_cast<const float2*>(mrow)[k];
+    return make_float2((float)((double)v.x * (double)h.x - (double)v.y * (double)h.y),
+                       (float)((double)v.x * (double)h.y + (double)v.y * (double)h.x));
+  }
+  const float g = reinterpret_cast<const float*>(mrow)[(kind == NXSIG_MASK_ONESIDED && k > K / 2) ? K - k : k];
+  return make_float2((float)((double)v.x * (double)g), (float)((double)v.y * (double)g));
+}
+int launch_spectrum_mask(Ctx* c, const float2* z, bool z_bcast, const void* mask, int32_t kind, bool mask_bcast, int64_t rows, int64_t M,
+                         int32_t K, float2* out);
+int launch_istft_wave_mask(Ctx* c, const IstftLaunch& s, const float* window_host, bool* handled);   // kernels_wave_mask.hip
 int launch_half_from_spectrum(Ctx* c, const float2* z, int64_t rows, int32_t K, float2* out, bool packed);
 int launch_full_from_packed(Ctx* c, const float2* zp, int64_t rows, int32_t K, float2* out);
 int launch_real_from_c64(Ctx* c, const float2* in, int64_t n, float* out);
