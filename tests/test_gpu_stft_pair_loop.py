@@ -122,7 +122,8 @@ def test_non_finite_unit_with_a_silent_frame(geometry):
     """the solo route and the eps clean-up meet: frame A of a unit holds a NaN, its frame B is digital silence (every component +0 in the
     reference, and here: the redone frame is cleaned eagerly); further on a silent unit (the speculative drain's re-drain) and a silent
     frame beside an ordinary one (its bins are the round-off of the shared transform, far above the 1e-10 threshold and inside the
-    tolerance: the paired route's known limit, not this loop's business, so only the tolerance is asked of it)"""
+    tolerance: the paired route's limit — DESIGN.md 3.0, third rule: a frame is bounded at the level of the loudest frame of its
+    unit — which tests/test_gpu_frame_isolation.py bounds and pins to the unit; here only the tolerance is asked of it)"""
     x = signal(77)
     w = S.windows.hann(K)
     for r, u in ((0, 9), (1, 12), (2, 6)):                        # chunk slots 1, 3 (first units) and 4 (a last unit) in the headline geometry
