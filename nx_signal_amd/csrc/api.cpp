@@ -6,7 +6,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <new>
+#include <string>
 #include <thread>
 #include <vector>
 #ifdef __linux__
@@ -154,7 +156,7 @@ MelDeferScope::MelDeferScope(const Ctx* c) { t_mel_defer = c; }
 MelDeferScope::~MelDeferScope() { t_mel_defer = nullptr; }
 bool mel_deferred(const Ctx* c) { return t_mel_defer == c; }
 
-int ctx_scratch(Ctx* c, int slot, size_t bytes, void** out) {
+int ctx_scratch(Ctx* c, ScratchSlot slot, size_t bytes, void** out) {
   if (c->scratch_bytes[slot] < bytes) {
     if (c->scratch[slot]) {
       NXSIG_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -247,8 +249,8 @@ int launch_istft(Ctx* c, const IstftLaunch& a, const float* window_host) {
     // no fused kernel for this geometry: the Hermitian rows are written out, the complex path runs, its real part is kept
     const int64_t out_len = a.M * a.hop + (a.N - a.hop);
     void *zf = nullptr, *yf = nullptr;
-    if ((rc = ctx_scratch(c, 24, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
-    if ((rc = ctx_scratch(c, 25, (size_t)a.batch * out_len * sizeof(float2), &yf))) return rc;
+    if ((rc = ctx_scratch(c, kScratchPackedSpectrum, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
+    if ((rc = ctx_scratch(c, kScratchPackedSignal, (size_t)a.batch * out_len * sizeof(float2), &yf))) return rc;
     if ((rc = launch_full_from_packed(c, a.z, (int64_t)a.batch * a.M, a.K, reinterpret_cast<float2*>(zf)))) return rc;
     IstftLaunch b = a;
     b.onesided = false; b.z = reinterpret_cast<const float2*>(zf); b.y = reinterpret_cast<float2*>(yf);
@@ -261,7 +263,7 @@ int launch_istft(Ctx* c, const IstftLaunch& a, const float* window_host) {
   if (!handled && a.mask) {
     // no fused kernel for this geometry: the masked spectrogram is materialised once (the two-step chain), then the size's own inverse runs
     void* zf = nullptr;
-    if ((rc = ctx_scratch(c, 20, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
+    if ((rc = ctx_scratch(c, kScratchIstftProduct, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
     if ((rc = launch_spectrum_mask(c, a.z, a.z_bcast, a.mask, a.mask_kind, a.mask_bcast, a.batch, a.M, a.K, reinterpret_cast<float2*>(zf)))) return rc;
     IstftLaunch b = a;
     b.z = reinterpret_cast<const float2*>(zf);
@@ -271,7 +273,7 @@ int launch_istft(Ctx* c, const IstftLaunch& a, const float* window_host) {
   if (!handled && a.filt) {
     // no fused kernel for this geometry: the filter product is materialised once (the two-step chain), then the plain path runs
     void* zf = nullptr;
-    if ((rc = ctx_scratch(c, 20, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
+    if ((rc = ctx_scratch(c, kScratchIstftProduct, (size_t)a.batch * a.M * a.K * sizeof(float2), &zf))) return rc;
     if ((rc = launch_spectrum_mul(c, a.z, (int64_t)a.batch * a.M, a.K, a.filt, reinterpret_cast<float2*>(zf)))) return rc;
     IstftLaunch b = a;
     b.z = reinterpret_cast<const float2*>(zf);
@@ -295,7 +297,7 @@ static int launch_fir_long(Ctx* c, const FirLaunch& a) {
   int rc = ctx_table(c, 0xF17A95ull ^ ((uint64_t)a.taps << 24), a.h_host, (size_t)a.taps * sizeof(float), &hd);
   if (rc) return rc;
   void* tmp = nullptr;
-  if ((rc = ctx_scratch(c, 21, (size_t)full * sizeof(float), &tmp))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFirLong, (size_t)full * sizeof(float), &tmp))) return rc;
   const int64_t s1 = a.L, s2 = a.taps;
   for (int32_t row = 0; row < a.batch; ++row) {
     if ((rc = launch_fftconvolve_nd(c, a.x + (size_t)row * a.batch_stride, true, &s1, hd, true, &s2, 1, NXSIG_CONV_FULL, tmp, nullptr))) return rc;
@@ -337,7 +339,7 @@ static int launch_fir_partitioned(Ctx* c, const FirLaunch& a_in) {
   void* tmp = nullptr;
   const int n_parts = (a.taps - 1 + S - 1) / S;
   const int first_round = n_parts < per_round ? n_parts : per_round;
-  if ((rc = ctx_scratch(c, 21, (size_t)first_round * (size_t)row_bytes, &tmp))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFirLong, (size_t)first_round * (size_t)row_bytes, &tmp))) return rc;
   bool any = false;
   for (int p0 = 0; p0 < n_parts; p0 += per_round) {
     const float* src[8];
@@ -431,7 +433,7 @@ struct DeviceGuard {
   bool ok;
 };
 
-// staging of host signal buffers through scratch slots (convenience path, PCIe-bound)
+// the transfers of host signal buffers through scratch slots (convenience path, PCIe-bound); the entry points use it through HostIo
 struct Staged {
   Ctx* c;
   explicit Staged(Ctx* ctx) : c(ctx) {}
@@ -470,7 +472,7 @@ struct Staged {
   // below take 15.5 ms into a resident result buffer and 17.6 ms into a fresh one, this pipeline 16.3-16.5 / 16.9-17.5 ms: the runtime
   // pins resident user pages on the fly and DMAs straight into them, which the extra host copy cannot beat; profiles/r06/host_path.txt)
   bool piped(size_t bytes) const { return bytes >= kPinMin && tune(c, kT_HOST_PIPE, 0) != 0; }
-  int in(int slot, const void* host, size_t bytes, const void** dev) {
+  int in(ScratchSlot slot, const void* host, size_t bytes, const void** dev) {
     void* d = nullptr;
     int rc = ctx_scratch(c, slot, bytes ? bytes : 4, &d);
     if (rc) return rc;
@@ -499,7 +501,7 @@ struct Staged {
     NXSIG_HIP_TRY(hipStreamWaitEvent(c->stream, c->xfer_ready, 0));
     return NXSIG_OK;
   }
-  int out_alloc(int slot, size_t bytes, void** dev) { return ctx_scratch(c, slot, bytes ? bytes : 4, dev); }
+  int out_alloc(ScratchSlot slot, size_t bytes, void** dev) { return ctx_scratch(c, slot, bytes ? bytes : 4, dev); }
   // A pageable device-to-host copy runs at PCIe speed (56 GB/s measured) into RESIDENT pages but at 20-25 GB/s into a
   // freshly allocated result buffer (np.empty, enif_make_new_binary): first-touch page faults, taken one at a time
   // inside the copy.  So the result is copied in chunks, and while chunk k is on the wire a few threads pre-fault the
@@ -580,16 +582,74 @@ struct Staged {
   }
 };
 
+
+// The tensor operands of one call (mem = NXSIG_HOST or NXSIG_DEVICE): device pointers pass through as they are, host pointers go through
+// scratch slots — up to three inputs are uploaded by open(), up to three results are written by the kernels into their slots and
+// copied back by close(), in the order they were listed.  in[] / out[] are the pointers to launch with either way.  A null input stays
+// null (optional operands).  Results that share a slot are packed into it, each at the next 256-byte boundary.
+struct HostIo {
+  struct In { const void* p; size_t bytes; ScratchSlot slot; };
+  // reserve: bytes to set aside when that is more than what is copied back (a result whose size the launcher decides: `bytes` is set
+  // after the launch, before close(); the whole 256-byte units of a waveform result)
+  struct Out { void* p; size_t bytes; ScratchSlot slot; size_t reserve = 0; };
+  static constexpr int kMax = 3;
+  Staged st;
+  const bool host;
+  bool plain_upload = false;   // uploads as one hipMemcpyAsync on the compute stream whatever NXSIG_HOST_PIPE says (the n-D calls)
+  const void* in[kMax] = {};
+  void* out[kMax] = {};
+  Out outs[kMax] = {};
+  int nout = 0;
+  HostIo(Ctx* c, int32_t mem) : st(c), host(mem == NXSIG_HOST) {}
+  int open(std::initializer_list<In> ins, std::initializer_list<Out> results) {
+    int rc, j = 0;
+    for (const In& i : ins) {
+      in[j] = i.p;
+      if (host && i.p) {
+        if (!plain_upload) {
+          if ((rc = st.in(i.slot, i.p, i.bytes, &in[j]))) return rc;
+        } else {
+          void* d = nullptr;
+          if ((rc = ctx_scratch(st.c, i.slot, i.bytes, &d))) return rc;
+          NXSIG_HIP_TRY(hipMemcpyAsync(d, i.p, i.bytes, hipMemcpyHostToDevice, st.c->stream));
+          in[j] = d;
+        }
+      }
+      ++j;
+    }
+    for (const Out& o : results) { outs[nout] = o; out[nout] = o.p; ++nout; }
+    if (!host) return NXSIG_OK;
+    for (int a = 0; a < nout; ++a) {
+      bool first = true;
+      for (int b = 0; b < a; ++b) first = first && outs[b].slot != outs[a].slot;
+      if (!first) continue;
+      size_t off[kMax] = {}, total = 0;
+      for (int b = a; b < nout; ++b) {
+        if (outs[b].slot != outs[a].slot) continue;
+        off[b] = total = (total + 255) & ~(size_t)255;
+        total += outs[b].reserve > outs[b].bytes ? outs[b].reserve : outs[b].bytes;
+      }
+      void* base = nullptr;
+      if ((rc = st.out_alloc(outs[a].slot, total, &base))) return rc;
+      for (int b = a; b < nout; ++b)
+        if (outs[b].slot == outs[a].slot) out[b] = static_cast<char*>(base) + off[b];
+    }
+    return NXSIG_OK;
+  }
+  int close() {
+    if (!host) return NXSIG_OK;
+    for (int j = 0; j < nout; ++j) {
+      const int rc = st.out_copy(outs[j].p, out[j], outs[j].bytes);
+      if (rc) return rc;
+    }
+    return NXSIG_OK;
+  }
+  // one device-to-host copy by out_copy's rules (chunked, pre-faulting, piped), for a result that sits elsewhere than in out[]
+  int download(void* host_dst, const void* dev, size_t bytes) { return st.out_copy(host_dst, dev, bytes); }
+};
 }  // namespace nxsig
 
 using namespace nxsig;
-
-#define NXSIG_API_BEGIN try {
-#define NXSIG_API_END                                                                   \
-  }                                                                                     \
-  catch (const std::bad_alloc&) { return set_error(NXSIG_ERR_OOM, "host out of memory"); } \
-  catch (const std::exception& e) { return set_error(NXSIG_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); } \
-  catch (...) { return set_error(NXSIG_ERR_INVALID_ARG, "internal error"); }
 
 #define NXSIG_CHECK_CTX(ctx)                                                            \
   if (!(ctx)) return set_error(NXSIG_ERR_INVALID_ARG, "null context");                  \
@@ -661,6 +721,422 @@ bool tuning_value_ok(int key, long value, long* lo, long* hi) { return tuning_in
 static int check_mem(int32_t mem) {
   if (mem != NXSIG_HOST && mem != NXSIG_DEVICE) return set_error(NXSIG_ERR_INVALID_ARG, "mem must be NXSIG_HOST or NXSIG_DEVICE");
   return NXSIG_OK;
+}
+
+
+/* ---------------------------------------------------------------- helpers of the compute entry points */
+static int check_scaling(int32_t s) {
+  if (s != NXSIG_SCALE_NONE && s != NXSIG_SCALE_SPECTRUM && s != NXSIG_SCALE_PSD)  // lib/nx_signal.ex:124-126, :622-624
+    return set_error(NXSIG_ERR_INVALID_ARG, "invalid :scaling, expected one of :spectrum, :psd or nil");
+  return NXSIG_OK;
+}
+
+// bytes of `batch` rows of `length` elements that lie batch_stride elements apart
+static size_t rows_bytes(int32_t batch, int64_t batch_stride, int64_t length, size_t elem) {
+  return ((size_t)(batch - 1) * batch_stride + length) * elem;
+}
+
+// ---- the prologue of the f32 STFT family (stft, stft_c64, stft_mel, stft_onesided / stft_packed, stft_magnitude), in two parts: a
+// checker that needs no context and a planner that fills the launch.  Every entry point keeps its own NXSIG_CHECK_CTX: stft, stft_c64
+// and stft_mel look at the context first, the others validate (and write *num_frames_out) first.
+struct StftEntry {
+  const char* name;             // prefix of the messages
+  int32_t max_batch;            // 0 = unbounded (rows beyond one launch run as slabs, see launch_stft)
+  int32_t min_fft_length;
+  const char* fft_length_msg;   // what follows the prefix when fft_length is too short (or fft_length_also is set)
+  bool extra_null = false;      // a pointer of the entry point's own (the mel filterbank) is null
+  bool fft_length_also = false; // a condition of the entry point's own that shares the fft_length message (mel_bins < 1)
+  const char* after_null = nullptr;  // a failed check of the entry point's own that sits right behind the null check: its whole message
+  const char* after_mem = nullptr;   // the same, behind the check of `mem`
+};
+
+static int stft_check(const StftEntry& e, const void* x, const float* window, const nxsig_stft_params* p, const void* out, int64_t length,
+                      int32_t batch, int64_t batch_stride, int32_t mem, Framing* fr, int64_t* num_frames_out) {
+  auto bad = [&](const std::string& what) { return set_error(NXSIG_ERR_INVALID_ARG, std::string(e.name) + what); };
+  if (!x || !window || !p || !out || e.extra_null) return bad(": null pointer argument");
+  if (e.after_null) return set_error(NXSIG_ERR_INVALID_ARG, e.after_null);
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (e.after_mem) return set_error(NXSIG_ERR_INVALID_ARG, e.after_mem);
+  if (batch < 1 || (e.max_batch && batch > e.max_batch))
+    return bad(e.max_batch ? ": batch must be in [1, " + std::to_string(e.max_batch) + "]" : std::string(": batch must be >= 1"));
+  if (batch_stride < length) return bad(": batch_stride < length");
+  if (p->fft_length < e.min_fft_length || e.fft_length_also) return bad(e.fft_length_msg);
+  if ((rc = check_scaling(p->scaling))) return rc;
+  if ((rc = make_framing(length, p->frame_length, p->hop, p->pad_mode, p->pad_lo, p->pad_hi, fr))) return rc;
+  if (num_frames_out) *num_frames_out = fr->M;
+  return NXSIG_OK;
+}
+
+// everything of the launch but the operands: geometry, :scaling divisor, the window's device copies (a.x / a.z are the caller's)
+static int stft_plan(Ctx* c, const Framing& fr, int32_t batch, int64_t batch_stride, const float* window, const nxsig_stft_params* p,
+                     StftLaunch* a) {
+  a->fr = fr; a->batch = batch; a->batch_stride = batch_stride; a->K = p->fft_length;
+  a->has_scale = p->scaling != NXSIG_SCALE_NONE;
+  a->inv_scale_div = a->has_scale ? scaling_factor(window, p->frame_length, p->scaling, p->sampling_rate) : 1.0f;
+  a->x = nullptr; a->z = nullptr;
+  return ctx_window(c, window, p->frame_length, p->fft_length, &a->window, &a->window_padK);
+}
+
+// nxsig_stft_f32 / nxsig_stft_c64: x_elem bytes per sample, the full spectrum out
+static int stft_full(nxsig_ctx* ctx, const void* x, size_t x_elem, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
+                     const nxsig_stft_params* p, nxsig_c64* z, int64_t* num_frames_out, int32_t mem, int (*launch)(Ctx*, const StftLaunch&)) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  static const StftEntry e{"stft", 0, 1, ": fft_length must be >= 1"};
+  Framing fr;
+  int rc = stft_check(e, x, window, p, z, length, batch, batch_stride, mem, &fr, num_frames_out);
+  if (rc) return rc;
+  StftLaunch a;
+  if ((rc = stft_plan(c, fr, batch, batch_stride, window, p, &a))) return rc;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, x_elem), kScratchStageIn}},
+                    {{z, (size_t)batch * fr.M * p->fft_length * sizeof(float2), kScratchStageOut}}))) return rc;
+  a.x = static_cast<const float*>(io.in[0]); a.z = static_cast<float2*>(io.out[0]);
+  if ((rc = launch(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+// The tail of the fused sinks (mel, one-sided / packed, magnitude): out_count results of out_elem bytes.  fused(a, out, &handled) tries
+// the wave kernel that reduces in registers; when it declines, the full spectrum goes to a scratch slot and reduce(a, out) runs on it.
+template <class Fused, class Reduce>
+static int stft_fused_sink(Ctx* c, StftLaunch& a, const float* x, int64_t length, void* out, size_t out_elem, size_t out_count, int32_t mem,
+                           Fused fused, Reduce reduce) {
+  HostIo io(c, mem);
+  int rc = io.open({{x, rows_bytes(a.batch, a.batch_stride, length, sizeof(float)), kScratchStageIn}}, {{out, out_count * out_elem, kScratchStageOut}});
+  if (rc) return rc;
+  a.x = static_cast<const float*>(io.in[0]);
+  bool handled = false;
+  if ((rc = fused(a, io.out[0], &handled))) return rc;
+  if (!handled) {
+    void* zs = nullptr;
+    if ((rc = ctx_scratch(c, kScratchFusedSpectrum, (size_t)a.batch * a.fr.M * a.K * sizeof(float2), &zs))) return rc;
+    a.z = reinterpret_cast<float2*>(zs);
+    if ((rc = launch_stft(c, a))) return rc;
+    if ((rc = reduce(a, io.out[0]))) return rc;
+  }
+  return io.close();
+}
+
+// nxsig_stft_onesided_f32 / nxsig_stft_packed_f32 (the messages carry the one-sided prefix for both, the parity check aside)
+static int stft_onesided_impl(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
+                              const nxsig_stft_params* p, nxsig_c64* out, int64_t* num_frames_out, int32_t mem, bool packed) {
+  NXSIG_API_BEGIN
+  StftEntry e{"stft_onesided", 65535, 2, ": fft_length >= 2 required"};
+  if (packed && p && (p->fft_length & 1)) e.after_null = "stft_packed: fft_length must be even";
+  Framing fr;
+  int rc = stft_check(e, x, window, p, out, length, batch, batch_stride, mem, &fr, num_frames_out);
+  if (rc) return rc;
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  StftLaunch a;
+  if ((rc = stft_plan(c, fr, batch, batch_stride, window, p, &a))) return rc;
+  const int64_t rows = (int64_t)batch * fr.M;
+  return stft_fused_sink(
+      c, a, x, length, out, sizeof(float2), (size_t)rows * (p->fft_length / 2), mem,
+      [&](const StftLaunch& s, void* od, bool* handled) {
+        return launch_stft_mag_wave(c, s, packed ? 4 : 3 /* complex bins */, static_cast<float*>(od), handled);
+      },
+      [&](const StftLaunch& s, void* od) { return launch_half_from_spectrum(c, s.z, rows, s.K, static_cast<float2*>(od), packed); });
+  NXSIG_API_END
+}
+
+// the operands of a time-frequency mask (nxsig_spectrum_mask_c64 / nxsig_istft_masked_c64)
+struct MaskOperand {
+  const void* mask = nullptr;
+  int32_t kind = 0, z_rows = 1, mask_rows = 1;
+};
+static int check_mask(const char* fn, const MaskOperand& mo, int32_t K, int32_t* rows) {
+  const std::string f(fn);
+  if (!mo.mask) return set_error(NXSIG_ERR_INVALID_ARG, f + ": null mask");
+  if (mo.kind != NXSIG_MASK_REAL && mo.kind != NXSIG_MASK_ONESIDED && mo.kind != NXSIG_MASK_COMPLEX)
+    return set_error(NXSIG_ERR_INVALID_ARG, f + ": mask_kind must be NXSIG_MASK_REAL, NXSIG_MASK_ONESIDED or NXSIG_MASK_COMPLEX");
+  if (mo.kind == NXSIG_MASK_ONESIDED && (K & 1)) return set_error(NXSIG_ERR_INVALID_ARG, f + ": a one-sided mask needs an even fft_length");
+  if (mo.z_rows < 1 || mo.mask_rows < 1) return set_error(NXSIG_ERR_INVALID_ARG, f + ": z_rows and mask_rows must be >= 1");
+  if (mo.z_rows != mo.mask_rows && mo.z_rows != 1 && mo.mask_rows != 1)
+    return set_error(NXSIG_ERR_INVALID_ARG, f + ": z_rows and mask_rows must be equal, or one of them 1, got " + std::to_string(mo.z_rows) +
+                                                " and " + std::to_string(mo.mask_rows));
+  *rows = mo.z_rows > mo.mask_rows ? mo.z_rows : mo.mask_rows;
+  if (*rows > 65535) return set_error(NXSIG_ERR_INVALID_ARG, f + ": at most 65535 rows");
+  return NXSIG_OK;
+}
+static size_t mask_bytes(const MaskOperand& mo, int64_t num_frames, int32_t K) {
+  return (size_t)mo.mask_rows * num_frames * mask_row_len(mo.kind, K) * (mo.kind == NXSIG_MASK_COMPLEX ? sizeof(float2) : sizeof(float));
+}
+
+static int istft_common(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_frames, int32_t batch, const float* window,
+                        const nxsig_stft_params* p, const nxsig_c64* h, nxsig_c64* y, int32_t mem, bool onesided = false,
+                        const MaskOperand* mo = nullptr) {
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!z || !window || !p || !y) return set_error(NXSIG_ERR_INVALID_ARG, "istft: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (batch < 1 || (batch > 65535 && (onesided || h)))
+    return set_error(NXSIG_ERR_INVALID_ARG, "istft: batch must be >= 1 (and <= 65535 for the packed and the filtered forms)");
+  if (num_frames < 1) return set_error(NXSIG_ERR_INVALID_ARG, "istft: num_frames must be >= 1");
+  rc = check_scaling(p->scaling);
+  if (rc) return rc;
+  const int N = p->frame_length, hop = p->hop, K = p->fft_length;
+  if (N < 1 || hop < 1) return set_error(NXSIG_ERR_INVALID_ARG, "istft: frame_length and hop must be >= 1");
+  if (hop > N)  // overlap_length < 0 cannot be expressed; overlap >= N -> hop <= 0 handled above (lib/nx_signal.ex:692-695)
+    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_length must be a number less than the window size");
+  if (K != N)
+    return set_error(NXSIG_ERR_INVALID_ARG,
+                     "istft: fft_length must equal the window length (the reference broadcasts {M,K} x {N}, lib/nx_signal.ex:628)");
+  if (onesided && (K & 1)) return set_error(NXSIG_ERR_INVALID_ARG, "istft_packed: fft_length must be even");
+  IstftLaunch a;
+  a.M = num_frames; a.batch = batch; a.N = N; a.hop = hop; a.K = K; a.onesided = onesided;
+  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
+  a.scale_mul = a.has_scale ? scaling_factor(window, N, p->scaling, p->sampling_rate) : 1.0f;
+  const void* wdev = nullptr;
+  rc = ctx_table(c, 0x57494Eull, window, (size_t)N * sizeof(float), &wdev);
+  if (rc) return rc;
+  a.window = reinterpret_cast<const float*>(wdev);
+  if (h) {  // same table key as spectrum_mul: the two-step and the fused form share the filter's device copy
+    const void* hd = nullptr;
+    if ((rc = ctx_table(c, 0x5BEC0ull ^ (uint64_t)K, h, (size_t)K * sizeof(float2), &hd))) return rc;
+    a.filt = reinterpret_cast<const float2*>(hd);
+  }
+  const int64_t out_len = num_frames * hop + (N - hop);
+  const size_t zbytes = (size_t)(mo ? mo->z_rows : batch) * num_frames * (onesided ? K / 2 : K) * sizeof(float2);
+  const size_t ybytes = (size_t)batch * out_len * (onesided ? sizeof(float) : sizeof(float2));
+  if (mo) {
+    a.mask_kind = mo->kind;
+    a.z_bcast = mo->z_rows == 1 && batch > 1; a.mask_bcast = mo->mask_rows == 1 && batch > 1;
+  }
+  HostIo io(c, mem);
+  if ((rc = io.open({{z, zbytes, kScratchStageIn}, {mo ? mo->mask : nullptr, mo ? mask_bytes(*mo, num_frames, K) : 0, kScratchNdStageA}},
+                    {{y, ybytes, kScratchStageOut}}))) return rc;
+  a.z = static_cast<const float2*>(io.in[0]); a.mask = io.in[1]; a.y = static_cast<float2*>(io.out[0]);
+  if ((rc = launch_istft(c, a, window))) return rc;
+  return io.close();
+}
+
+// ---- what the f32 and the f64 tier of as_windowed / overlap_and_add / fir differ in: the launcher, the names in one message, and the
+// FIR's row limit (f32: unbounded, rows beyond one launch run as slabs, see launch_fir)
+template <class T> struct Tier;
+template <> struct Tier<float> {
+  static constexpr const char* kReal = "f32";
+  static constexpr const char* kComplex = "c64";
+  static constexpr int32_t kFirMaxBatch = 0;
+  using Fir = FirLaunch;
+  static int as_windowed(Ctx* c, const float* x, int64_t batch_stride, int32_t batch, const Framing& fr, float* out) {
+    return launch_as_windowed(c, x, batch_stride, batch, fr, out);
+  }
+  static int overlap_and_add(Ctx* c, const float* frames, int64_t M, int32_t batch, int32_t N, int32_t hop, int32_t comps, float* out) {
+    return launch_overlap_and_add(c, frames, M, batch, N, hop, comps, out);
+  }
+  static int fir(Ctx* c, const FirLaunch& a) { return launch_fir(c, a); }
+};
+template <> struct Tier<double> {
+  static constexpr const char* kReal = "f64";
+  static constexpr const char* kComplex = "c128";
+  static constexpr int32_t kFirMaxBatch = 65535;
+  using Fir = FirLaunchD;
+  static int as_windowed(Ctx* c, const double* x, int64_t batch_stride, int32_t batch, const Framing& fr, double* out) {
+    return launch_as_windowed_f64(c, x, batch_stride, batch, fr, out);
+  }
+  static int overlap_and_add(Ctx* c, const double* frames, int64_t M, int32_t batch, int32_t N, int32_t hop, int32_t comps, double* out) {
+    return launch_ola_f64(c, frames, M, batch, N, hop, comps, nullptr, false, false, out);
+  }
+  static int fir(Ctx* c, const FirLaunchD& a) { return launch_fir_f64(c, a); }
+};
+
+template <class T>
+static int as_windowed(nxsig_ctx* ctx, const T* x, int64_t length, int32_t batch, int64_t batch_stride, int32_t window_length, int32_t stride,
+                       int32_t pad_mode, int64_t pad_lo, int64_t pad_hi, T* out, int64_t* num_frames_out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!x || !out) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (batch < 1 || batch > 65535) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: batch must be in [1, 65535]");
+  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: batch_stride < length");
+  Framing fr;
+  rc = make_framing(length, window_length, stride, pad_mode, pad_lo, pad_hi, &fr);
+  if (rc) return rc;
+  if (num_frames_out) *num_frames_out = fr.M;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(T)), kScratchStageIn}},
+                    {{out, (size_t)batch * fr.M * fr.N * sizeof(T), kScratchStageOut}}))) return rc;
+  if ((rc = Tier<T>::as_windowed(c, static_cast<const T*>(io.in[0]), batch_stride, batch, fr, static_cast<T*>(io.out[0])))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+template <class T>
+static int overlap_and_add(nxsig_ctx* ctx, const T* frames, int64_t num_frames, int32_t batch, int32_t frame_length, int32_t overlap_length,
+                           int32_t components, T* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!frames || !out) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (components != 1 && components != 2)
+    return set_error(NXSIG_ERR_INVALID_ARG, std::string("overlap_and_add: components must be 1 (") + Tier<T>::kReal + ") or 2 (" + Tier<T>::kComplex + ")");
+  if (batch < 1 || batch > 65535 || num_frames < 1 || frame_length < 1)
+    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: batch, num_frames and frame_length must be >= 1");
+  if (overlap_length >= frame_length)  // lib/nx_signal.ex:692-695 (message prints the window size twice, quirk B10)
+    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_length must be a number less than the window size " +
+                                                std::to_string(frame_length) + ", got: " + std::to_string(frame_length));
+  if (overlap_length < 0) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: overlap_length must be >= 0");
+  const int hop = frame_length - overlap_length;
+  const int64_t out_len = num_frames * hop + overlap_length;
+  HostIo io(c, mem);
+  if ((rc = io.open({{frames, (size_t)batch * num_frames * frame_length * components * sizeof(T), kScratchStageIn}},
+                    {{out, (size_t)batch * out_len * components * sizeof(T), kScratchStageOut}}))) return rc;
+  if ((rc = Tier<T>::overlap_and_add(c, static_cast<const T*>(io.in[0]), num_frames, batch, frame_length, hop, components,
+                                     static_cast<T*>(io.out[0])))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+template <class T>
+static int fir_common(nxsig_ctx* ctx, const T* x, int64_t length, int32_t batch, int64_t batch_stride, const T* h, int32_t num_taps,
+                      int64_t start, int64_t out_len, T* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (!x || !h || !y) return set_error(NXSIG_ERR_INVALID_ARG, "fir: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (batch < 1 || (Tier<T>::kFirMaxBatch && batch > Tier<T>::kFirMaxBatch) || length < 1 || num_taps < 1)
+    return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch, length and num_taps must be >= 1");
+  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch_stride < length");
+  if (start < 0 || out_len < 1 || start + out_len > length + num_taps - 1)
+    return set_error(NXSIG_ERR_INVALID_ARG, "fir: requested slice lies outside the full convolution");
+  typename Tier<T>::Fir a;
+  a.L = length; a.batch = batch; a.batch_stride = batch_stride; a.h_host = h; a.taps = num_taps;
+  a.out_start = start; a.out_len = out_len;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(T)), kScratchStageIn}},
+                    {{y, (size_t)batch * out_len * sizeof(T), kScratchStageOut}}))) return rc;
+  a.x = static_cast<const T*>(io.in[0]); a.y = static_cast<T*>(io.out[0]);
+  if ((rc = Tier<T>::fir(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+// the slice of the full 1-D convolution of n1 and n2 samples a mode names (lib/nx_signal/convolution.ex:300-329: centered(out, shape)
+// starts at div(full - new, 2); an unknown mode: convolution.ex:41-44)
+static int conv_slice(int64_t n1, int64_t n2, int32_t mode, int64_t* start, int64_t* out_len) {
+  const int64_t full = n1 + n2 - 1;
+  switch (mode) {
+    case NXSIG_CONV_FULL: *out_len = full; break;
+    case NXSIG_CONV_SAME: *out_len = n1; break;
+    case NXSIG_CONV_VALID: *out_len = (n1 >= n2 ? n1 - n2 : n2 - n1) + 1; break;
+    default: return set_error(NXSIG_ERR_INVALID_ARG, "expected mode to be one of [:full, :same, :valid]");
+  }
+  *start = (full - *out_len) / 2;
+  return NXSIG_OK;
+}
+
+// nxsig_fir_f32 / _f64: the slice of the full convolution a mode names (its length checks come ahead of the context's)
+template <class T>
+static int fir_mode(nxsig_ctx* ctx, const T* x, int64_t length, int32_t batch, int64_t batch_stride, const T* h, int32_t num_taps, int32_t mode,
+                    T* y, int32_t mem) {
+  if (length < 1 || num_taps < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch, length and num_taps must be >= 1");
+  int64_t out_len, start;
+  const int rc = conv_slice(length, num_taps, mode, &start, &out_len);
+  if (rc) return rc;
+  return fir_common<T>(ctx, x, length, batch, batch_stride, h, num_taps, start, out_len, y, mem);
+}
+
+// nxsig_fftconvolve_nd / nxsig_convolve_direct: the same entry point around two launchers
+typedef int (*ConvNdLaunch)(Ctx* c, const void* a, bool a_is_real, const int64_t* s1, const void* b, bool b_is_real, const int64_t* s2, int rank,
+                            int mode, void* out, int64_t* out_shape);
+static int conv_nd(const char* name, ConvNdLaunch launch, nxsig_ctx* ctx, const void* a, int32_t a_is_real, const int64_t* a_shape, const void* b,
+                   int32_t b_is_real, const int64_t* b_shape, int32_t rank, int32_t mode, void* out, int64_t* out_shape, int32_t mem) {
+  NXSIG_API_BEGIN
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  const std::string f(name);
+  if (!a || !b || !out || !a_shape || !b_shape) return set_error(NXSIG_ERR_INVALID_ARG, f + ": null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, f + ": rank must be in [1, 8]");
+  if (mem == NXSIG_DEVICE) return launch(c, a, a_is_real != 0, a_shape, b, b_is_real != 0, b_shape, rank, mode, out, out_shape);
+  int64_t na = 1, nb = 1, no = 1, osh[8];
+  for (int d = 0; d < rank; ++d) {
+    if (a_shape[d] < 1 || b_shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, f + ": empty dimension");
+    na *= a_shape[d]; nb *= b_shape[d]; no *= a_shape[d] + b_shape[d] - 1;  // upper bound of every mode's result
+  }
+  const size_t out_elem = a_is_real && b_is_real ? 4 : 8;
+  HostIo io(c, mem);
+  io.plain_upload = true;
+  if ((rc = io.open({{a, (size_t)na * (a_is_real ? 4 : 8), kScratchNdStageA}, {b, (size_t)nb * (b_is_real ? 4 : 8), kScratchNdStageB}},
+                    {{out, 0, kScratchNdStageOut, (size_t)no * out_elem}}))) return rc;
+  if ((rc = launch(c, io.in[0], a_is_real != 0, a_shape, io.in[1], b_is_real != 0, b_shape, rank, mode, io.out[0], osh))) return rc;
+  int64_t nres = 1;
+  for (int d = 0; d < rank; ++d) { nres *= osh[d]; if (out_shape) out_shape[d] = osh[d]; }
+  io.outs[0].bytes = (size_t)nres * out_elem;
+  return io.close();
+  NXSIG_API_END
+}
+
+// Filters.median / wiener: the shape checks of filters.ex (and of the Nx.slice / Nx.conv they compose)
+static int filter_shape(const char* fn, const int64_t* shape, int32_t rank, const int64_t* ks, int64_t* n) {
+  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": rank must be in [1, 8]");
+  *n = 1;
+  for (int d = 0; d < rank; ++d) {
+    if (shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": empty dimension");
+    if (ks[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": window lengths must be >= 1");
+    *n *= shape[d];
+  }
+  return NXSIG_OK;
+}
+
+// PeakFinding.argrelextrema / nonzero: the port's limits
+static int peaks_shape(const char* fn, const int64_t* shape, int32_t rank, int64_t* n) {
+  if (!shape) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": rank must be in [1, 8]");
+  *n = 1;
+  for (int d = 0; d < rank; ++d) {
+    if (shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": empty dimension");
+    if (shape[d] >= ((int64_t)1 << 31)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": a dimension of 2^31 or more");
+    *n *= shape[d];
+    if (*n >= ((int64_t)1 << 32)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": 2^32 or more elements");
+  }
+  return NXSIG_OK;
+}
+// x in; out[0] = valid, out[1] = indices [n][rank] (`valid` travels back first)
+static int peaks_open(HostIo& io, const void* x, size_t x_bytes, int64_t n, int32_t rank, int32_t* indices, uint32_t* valid) {
+  return io.open({{x, x_bytes, kScratchNdStageA}}, {{valid, 4, kScratchNdStageB}, {indices, (size_t)n * rank * 4, kScratchNdStageOut}});
+}
+
+// NxSignal.Waveforms (lib/nx_signal/waveforms.ex; DESIGN.md section 3.10): the reference's ArgumentErrors, the scalars that do not
+// depend on t computed once under the tier's rounding (f32: every op in double on f32 operands, rounded to f32; f64: no rounding;
+// pi() the f32 constant in both)
+constexpr double kWavePi = 3.1415927410125732;   // Nx.Constants.pi() as f32
+constexpr double kWaveTwoPi = 2.0 * kWavePi;     // 2 * pi(): exact
+
+struct WaveRound {
+  bool f64;
+  double operator()(double x) const { return f64 ? x : (double)(float)x; }
+};
+
+static std::string wave_num(double v) {
+  char buf[40];
+  std::snprintf(buf, sizeof buf, "%.17g", v);
+  return buf;
+}
+
+static int wave_args(const char* fn, const void* t, const void* out, int64_t n, int32_t mem) {
+  if (n < 0) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": n must be >= 0");
+  if (n > 0 && (!t || !out)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  return check_mem(mem);
+}
+// a staged waveform result takes a whole number of 256-byte units of its slot
+static size_t wave_span(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// t (and an optional second stream) of in_elem-byte elements in, one result of out_elem-byte elements out
+static int wave_open(HostIo& io, const void* t, const void* second, size_t in_elem, int64_t n, void* out, size_t out_elem) {
+  return io.open({{t, (size_t)n * in_elem, kScratchNdStageA}, {second, (size_t)n * in_elem, kScratchNdStageB}},
+                 {{out, (size_t)n * out_elem, kScratchNdStageOut, wave_span((size_t)n * out_elem)}});
 }
 
 extern "C" {
@@ -871,8 +1347,8 @@ int nxsig_download(nxsig_ctx* ctx, void* dst_host, const void* src_device, size_
   NXSIG_API_BEGIN
   NXSIG_CHECK_CTX(ctx)
   if (!dst_host || !src_device) return set_error(NXSIG_ERR_INVALID_ARG, "download: null pointer");
-  Staged st(c);  // large results: chunked copy with the next chunk's pages pre-faulted (freshly allocated destinations)
-  return st.out_copy(dst_host, src_device, bytes);
+  // large results: chunked copy with the next chunk's pages pre-faulted (freshly allocated destinations)
+  return HostIo(c, NXSIG_HOST).download(dst_host, src_device, bytes);
   NXSIG_API_END
 }
 
@@ -1033,167 +1509,14 @@ int nxsig_stft_times_f32(int32_t frame_length, double sampling_rate, int64_t num
 }
 
 /* ---------------------------------------------------------------- hot path */
-static int check_scaling(int32_t s) {
-  if (s != NXSIG_SCALE_NONE && s != NXSIG_SCALE_SPECTRUM && s != NXSIG_SCALE_PSD)  // lib/nx_signal.ex:124-126, :622-624
-    return set_error(NXSIG_ERR_INVALID_ARG, "invalid :scaling, expected one of :spectrum, :psd or nil");
-  return NXSIG_OK;
-}
-
 int nxsig_stft_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride,
                    const float* window, const nxsig_stft_params* p, nxsig_c64* z, int64_t* num_frames_out, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!x || !window || !p || !z) return set_error(NXSIG_ERR_INVALID_ARG, "stft: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1) return set_error(NXSIG_ERR_INVALID_ARG, "stft: batch must be >= 1");   // (more than 65 504 rows: slabs, see launch_stft)
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "stft: batch_stride < length");
-  if (p->fft_length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "stft: fft_length must be >= 1");
-  rc = check_scaling(p->scaling);
-  if (rc) return rc;
-  Framing fr;
-  rc = make_framing(length, p->frame_length, p->hop, p->pad_mode, p->pad_lo, p->pad_hi, &fr);
-  if (rc) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
-
-  StftLaunch a;
-  a.fr = fr; a.batch = batch; a.batch_stride = batch_stride; a.K = p->fft_length;
-  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
-  a.inv_scale_div = a.has_scale ? scaling_factor(window, p->frame_length, p->scaling, p->sampling_rate) : 1.0f;
-  rc = ctx_window(c, window, p->frame_length, p->fft_length, &a.window, &a.window_padK);
-  if (rc) return rc;
-  const size_t zbytes = (size_t)batch * fr.M * p->fft_length * sizeof(float2);
-  if (mem == NXSIG_DEVICE) {
-    a.x = x; a.z = reinterpret_cast<float2*>(z);
-    return launch_stft(c, a);
-  }
-  Staged st(c);
-  const void* xd = nullptr; void* zd = nullptr;
-  const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, zbytes, &zd))) return rc;
-  a.x = reinterpret_cast<const float*>(xd); a.z = reinterpret_cast<float2*>(zd);
-  if ((rc = launch_stft(c, a))) return rc;
-  return st.out_copy(z, zd, zbytes);
-  NXSIG_API_END
+  return stft_full(ctx, x, sizeof(float), length, batch, batch_stride, window, p, z, num_frames_out, mem, launch_stft);
 }
 
 int nxsig_stft_c64(nxsig_ctx* ctx, const nxsig_c64* x, int64_t length, int32_t batch, int64_t batch_stride,
                    const float* window, const nxsig_stft_params* p, nxsig_c64* z, int64_t* num_frames_out, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!x || !window || !p || !z) return set_error(NXSIG_ERR_INVALID_ARG, "stft: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1) return set_error(NXSIG_ERR_INVALID_ARG, "stft: batch must be >= 1");   // (more than 65 504 rows: slabs, see launch_stft_c64)
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "stft: batch_stride < length");
-  if (p->fft_length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "stft: fft_length must be >= 1");
-  rc = check_scaling(p->scaling);
-  if (rc) return rc;
-  Framing fr;
-  rc = make_framing(length, p->frame_length, p->hop, p->pad_mode, p->pad_lo, p->pad_hi, &fr);
-  if (rc) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
-  StftLaunch a;
-  a.fr = fr; a.batch = batch; a.batch_stride = batch_stride; a.K = p->fft_length;
-  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
-  a.inv_scale_div = a.has_scale ? scaling_factor(window, p->frame_length, p->scaling, p->sampling_rate) : 1.0f;
-  rc = ctx_window(c, window, p->frame_length, p->fft_length, &a.window, &a.window_padK);
-  if (rc) return rc;
-  const size_t zbytes = (size_t)batch * fr.M * p->fft_length * sizeof(float2);
-  if (mem == NXSIG_DEVICE) {
-    a.x = reinterpret_cast<const float*>(x); a.z = reinterpret_cast<float2*>(z);
-    return launch_stft_c64(c, a);
-  }
-  Staged st(c);
-  const void* xd = nullptr; void* zd = nullptr;
-  const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float2);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, zbytes, &zd))) return rc;
-  a.x = reinterpret_cast<const float*>(xd); a.z = reinterpret_cast<float2*>(zd);
-  if ((rc = launch_stft_c64(c, a))) return rc;
-  return st.out_copy(z, zd, zbytes);
-  NXSIG_API_END
-}
-
-// the operands of a time-frequency mask (nxsig_spectrum_mask_c64 / nxsig_istft_masked_c64)
-struct MaskOperand {
-  const void* mask = nullptr;
-  int32_t kind = 0, z_rows = 1, mask_rows = 1;
-};
-static int check_mask(const char* fn, const MaskOperand& mo, int32_t K, int32_t* rows) {
-  const std::string f(fn);
-  if (!mo.mask) return set_error(NXSIG_ERR_INVALID_ARG, f + ": null mask");
-  if (mo.kind != NXSIG_MASK_REAL && mo.kind != NXSIG_MASK_ONESIDED && mo.kind != NXSIG_MASK_COMPLEX)
-    return set_error(NXSIG_ERR_INVALID_ARG, f + ": mask_kind must be NXSIG_MASK_REAL, NXSIG_MASK_ONESIDED or NXSIG_MASK_COMPLEX");
-  if (mo.kind == NXSIG_MASK_ONESIDED && (K & 1)) return set_error(NXSIG_ERR_INVALID_ARG, f + ": a one-sided mask needs an even fft_length");
-  if (mo.z_rows < 1 || mo.mask_rows < 1) return set_error(NXSIG_ERR_INVALID_ARG, f + ": z_rows and mask_rows must be >= 1");
-  if (mo.z_rows != mo.mask_rows && mo.z_rows != 1 && mo.mask_rows != 1)
-    return set_error(NXSIG_ERR_INVALID_ARG, f + ": z_rows and mask_rows must be equal, or one of them 1, got " + std::to_string(mo.z_rows) +
-                                                " and " + std::to_string(mo.mask_rows));
-  *rows = mo.z_rows > mo.mask_rows ? mo.z_rows : mo.mask_rows;
-  if (*rows > 65535) return set_error(NXSIG_ERR_INVALID_ARG, f + ": at most 65535 rows");
-  return NXSIG_OK;
-}
-static size_t mask_bytes(const MaskOperand& mo, int64_t num_frames, int32_t K) {
-  return (size_t)mo.mask_rows * num_frames * mask_row_len(mo.kind, K) * (mo.kind == NXSIG_MASK_COMPLEX ? sizeof(float2) : sizeof(float));
-}
-
-static int istft_common(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_frames, int32_t batch, const float* window,
-                        const nxsig_stft_params* p, const nxsig_c64* h, nxsig_c64* y, int32_t mem, bool onesided = false,
-                        const MaskOperand* mo = nullptr) {
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!z || !window || !p || !y) return set_error(NXSIG_ERR_INVALID_ARG, "istft: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || (batch > 65535 && (onesided || h)))
-    return set_error(NXSIG_ERR_INVALID_ARG, "istft: batch must be >= 1 (and <= 65535 for the packed and the filtered forms)");
-  if (num_frames < 1) return set_error(NXSIG_ERR_INVALID_ARG, "istft: num_frames must be >= 1");
-  rc = check_scaling(p->scaling);
-  if (rc) return rc;
-  const int N = p->frame_length, hop = p->hop, K = p->fft_length;
-  if (N < 1 || hop < 1) return set_error(NXSIG_ERR_INVALID_ARG, "istft: frame_length and hop must be >= 1");
-  if (hop > N)  // overlap_length < 0 cannot be expressed; overlap >= N -> hop <= 0 handled above (lib/nx_signal.ex:692-695)
-    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_length must be a number less than the window size");
-  if (K != N)
-    return set_error(NXSIG_ERR_INVALID_ARG,
-                     "istft: fft_length must equal the window length (the reference broadcasts {M,K} x {N}, lib/nx_signal.ex:628)");
-  if (onesided && (K & 1)) return set_error(NXSIG_ERR_INVALID_ARG, "istft_packed: fft_length must be even");
-  IstftLaunch a;
-  a.M = num_frames; a.batch = batch; a.N = N; a.hop = hop; a.K = K; a.onesided = onesided;
-  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
-  a.scale_mul = a.has_scale ? scaling_factor(window, N, p->scaling, p->sampling_rate) : 1.0f;
-  const void* wdev = nullptr;
-  rc = ctx_table(c, 0x57494Eull, window, (size_t)N * sizeof(float), &wdev);
-  if (rc) return rc;
-  a.window = reinterpret_cast<const float*>(wdev);
-  if (h) {  // same table key as spectrum_mul: the two-step and the fused form share the filter's device copy
-    const void* hd = nullptr;
-    if ((rc = ctx_table(c, 0x5BEC0ull ^ (uint64_t)K, h, (size_t)K * sizeof(float2), &hd))) return rc;
-    a.filt = reinterpret_cast<const float2*>(hd);
-  }
-  const int64_t out_len = num_frames * hop + (N - hop);
-  const size_t zbytes = (size_t)(mo ? mo->z_rows : batch) * num_frames * (onesided ? K / 2 : K) * sizeof(float2);
-  const size_t ybytes = (size_t)batch * out_len * (onesided ? sizeof(float) : sizeof(float2));
-  if (mo) {
-    a.mask = mo->mask; a.mask_kind = mo->kind;
-    a.z_bcast = mo->z_rows == 1 && batch > 1; a.mask_bcast = mo->mask_rows == 1 && batch > 1;
-  }
-  if (mem == NXSIG_DEVICE) {
-    a.z = reinterpret_cast<const float2*>(z); a.y = reinterpret_cast<float2*>(y);
-    return launch_istft(c, a, window);
-  }
-  Staged st(c);
-  const void* zd = nullptr; void* yd = nullptr;
-  if ((rc = st.in(1, z, zbytes, &zd))) return rc;
-  if (mo && (rc = st.in(17, mo->mask, mask_bytes(*mo, num_frames, K), &a.mask))) return rc;
-  if ((rc = st.out_alloc(2, ybytes, &yd))) return rc;
-  a.z = reinterpret_cast<const float2*>(zd); a.y = reinterpret_cast<float2*>(yd);
-  if ((rc = launch_istft(c, a, window))) return rc;
-  return st.out_copy(y, yd, ybytes);
+  return stft_full(ctx, x, sizeof(float2), length, batch, batch_stride, window, p, z, num_frames_out, mem, launch_stft_c64);
 }
 
 int nxsig_istft_c64(nxsig_ctx* ctx, const nxsig_c64* z, int64_t num_frames, int32_t batch, const float* window,
@@ -1245,77 +1568,25 @@ int nxsig_spectrum_mask_c64(nxsig_ctx* ctx, const nxsig_c64* z, int32_t z_rows, 
   int32_t rows = 0;
   if ((rc = check_mask("spectrum_mask", mo, fft_length, &rows))) return rc;
   const bool zb = z_rows == 1 && rows > 1, mb = mask_rows == 1 && rows > 1;
-  const size_t zbytes = (size_t)z_rows * num_frames * fft_length * sizeof(float2);
-  const size_t obytes = (size_t)rows * num_frames * fft_length * sizeof(float2);
-  if (mem == NXSIG_DEVICE)
-    return launch_spectrum_mask(c, reinterpret_cast<const float2*>(z), zb, mask, mask_kind, mb, rows, num_frames, fft_length,
-                                reinterpret_cast<float2*>(out));
-  Staged st(c);
-  const void *zd = nullptr, *md = nullptr; void* od = nullptr;
-  if ((rc = st.in(1, z, zbytes, &zd))) return rc;
-  if ((rc = st.in(17, mask, mask_bytes(mo, num_frames, fft_length), &md))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_spectrum_mask(c, reinterpret_cast<const float2*>(zd), zb, md, mask_kind, mb, rows, num_frames, fft_length,
-                                 reinterpret_cast<float2*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
+  HostIo io(c, mem);
+  if ((rc = io.open({{z, (size_t)z_rows * num_frames * fft_length * sizeof(float2), kScratchStageIn},
+                     {mask, mask_bytes(mo, num_frames, fft_length), kScratchNdStageA}},
+                    {{out, (size_t)rows * num_frames * fft_length * sizeof(float2), kScratchStageOut}}))) return rc;
+  if ((rc = launch_spectrum_mask(c, static_cast<const float2*>(io.in[0]), zb, io.in[1], mask_kind, mb, rows, num_frames, fft_length,
+                                 static_cast<float2*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
 int nxsig_as_windowed_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride,
                           int32_t window_length, int32_t stride, int32_t pad_mode, int64_t pad_lo, int64_t pad_hi,
                           float* out, int64_t* num_frames_out, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!x || !out) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || batch > 65535) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: batch must be in [1, 65535]");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: batch_stride < length");
-  Framing fr;
-  rc = make_framing(length, window_length, stride, pad_mode, pad_lo, pad_hi, &fr);
-  if (rc) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
-  const size_t obytes = (size_t)batch * fr.M * fr.N * sizeof(float);
-  if (mem == NXSIG_DEVICE) return launch_as_windowed(c, x, batch_stride, batch, fr, out);
-  Staged st(c);
-  const void* xd = nullptr; void* od = nullptr;
-  const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_as_windowed(c, reinterpret_cast<const float*>(xd), batch_stride, batch, fr, reinterpret_cast<float*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
-  NXSIG_API_END
+  return as_windowed<float>(ctx, x, length, batch, batch_stride, window_length, stride, pad_mode, pad_lo, pad_hi, out, num_frames_out, mem);
 }
 
 int nxsig_overlap_and_add(nxsig_ctx* ctx, const float* frames, int64_t num_frames, int32_t batch, int32_t frame_length,
                           int32_t overlap_length, int32_t components, float* out, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!frames || !out) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (components != 1 && components != 2) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: components must be 1 (f32) or 2 (c64)");
-  if (batch < 1 || batch > 65535 || num_frames < 1 || frame_length < 1)
-    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: batch, num_frames and frame_length must be >= 1");
-  if (overlap_length >= frame_length)  // lib/nx_signal.ex:692-695 (message prints the window size twice, quirk B10)
-    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_length must be a number less than the window size " +
-                                                std::to_string(frame_length) + ", got: " + std::to_string(frame_length));
-  if (overlap_length < 0) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: overlap_length must be >= 0");
-  const int hop = frame_length - overlap_length;
-  const int64_t out_len = num_frames * hop + overlap_length;
-  const size_t ibytes = (size_t)batch * num_frames * frame_length * components * sizeof(float);
-  const size_t obytes = (size_t)batch * out_len * components * sizeof(float);
-  if (mem == NXSIG_DEVICE) return launch_overlap_and_add(c, frames, num_frames, batch, frame_length, hop, components, out);
-  Staged st(c);
-  const void* fd = nullptr; void* od = nullptr;
-  if ((rc = st.in(1, frames, ibytes, &fd))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_overlap_and_add(c, reinterpret_cast<const float*>(fd), num_frames, batch, frame_length, hop, components,
-                                   reinterpret_cast<float*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
-  NXSIG_API_END
+  return overlap_and_add<float>(ctx, frames, num_frames, batch, frame_length, overlap_length, components, out, mem);
 }
 
 int nxsig_fft(nxsig_ctx* ctx, const void* in, int32_t in_is_real, int64_t rows, int32_t n_in, int32_t fft_length,
@@ -1327,71 +1598,22 @@ int nxsig_fft(nxsig_ctx* ctx, const void* in, int32_t in_is_real, int64_t rows, 
   int rc = check_mem(mem);
   if (rc) return rc;
   if (rows < 1 || n_in < 1 || fft_length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fft: rows, n_in and fft_length must be >= 1");
-  const size_t ibytes = (size_t)rows * n_in * (in_is_real ? sizeof(float) : sizeof(float2));
-  const size_t obytes = (size_t)rows * fft_length * sizeof(float2);
-  if (mem == NXSIG_DEVICE) return launch_fft(c, in, in_is_real != 0, rows, n_in, fft_length, inverse != 0, reinterpret_cast<float2*>(out));
-  Staged st(c);
-  const void* id = nullptr; void* od = nullptr;
-  if ((rc = st.in(1, in, ibytes, &id))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_fft(c, id, in_is_real != 0, rows, n_in, fft_length, inverse != 0, reinterpret_cast<float2*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
-  NXSIG_API_END
-}
-
-static int fir_common(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* h,
-                      int32_t num_taps, int64_t start, int64_t out_len, float* y, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!x || !h || !y) return set_error(NXSIG_ERR_INVALID_ARG, "fir: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || length < 1 || num_taps < 1)   // (more than 65 504 rows: slabs, see launch_fir)
-    return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch, length and num_taps must be >= 1");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch_stride < length");
-  if (start < 0 || out_len < 1 || start + out_len > length + num_taps - 1)
-    return set_error(NXSIG_ERR_INVALID_ARG, "fir: requested slice lies outside the full convolution");
-  FirLaunch a;
-  a.L = length; a.batch = batch; a.batch_stride = batch_stride; a.h_host = h; a.taps = num_taps;
-  a.out_start = start; a.out_len = out_len;
-  const size_t ybytes = (size_t)batch * out_len * sizeof(float);
-  if (mem == NXSIG_DEVICE) {
-    a.x = x; a.y = y;
-    return launch_fir(c, a);
-  }
-  Staged st(c);
-  const void* xd = nullptr; void* yd = nullptr;
-  const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, ybytes, &yd))) return rc;
-  a.x = reinterpret_cast<const float*>(xd); a.y = reinterpret_cast<float*>(yd);
-  if ((rc = launch_fir(c, a))) return rc;
-  return st.out_copy(y, yd, ybytes);
+  HostIo io(c, mem);
+  if ((rc = io.open({{in, (size_t)rows * n_in * (in_is_real ? sizeof(float) : sizeof(float2)), kScratchStageIn}},
+                    {{out, (size_t)rows * fft_length * sizeof(float2), kScratchStageOut}}))) return rc;
+  if ((rc = launch_fft(c, io.in[0], in_is_real != 0, rows, n_in, fft_length, inverse != 0, static_cast<float2*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
 int nxsig_fir_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* h,
                   int32_t num_taps, int32_t mode, float* y, int32_t mem) {
-  if (length < 1 || num_taps < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch, length and num_taps must be >= 1");
-  const int64_t full = length + num_taps - 1;
-  int64_t out_len, start;
-  switch (mode) {  // lib/nx_signal/convolution.ex:300-329: centered(out, shape) starts at div(full - new, 2)
-    case NXSIG_CONV_FULL: out_len = full; start = 0; break;
-    case NXSIG_CONV_SAME: out_len = length; start = (full - out_len) / 2; break;
-    case NXSIG_CONV_VALID:
-      out_len = (length >= num_taps ? length - num_taps : num_taps - length) + 1;
-      start = (full - out_len) / 2;
-      break;
-    default:  // convolution.ex:41-44
-      return set_error(NXSIG_ERR_INVALID_ARG, "expected mode to be one of [:full, :same, :valid]");
-  }
-  return fir_common(ctx, x, length, batch, batch_stride, h, num_taps, start, out_len, y, mem);
+  return fir_mode<float>(ctx, x, length, batch, batch_stride, h, num_taps, mode, y, mem);
 }
 
 int nxsig_fir_slice_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* h,
                         int32_t num_taps, int64_t out_start, int64_t out_len, float* y, int32_t mem) {
-  return fir_common(ctx, x, length, batch, batch_stride, h, num_taps, out_start, out_len, y, mem);
+  return fir_common<float>(ctx, x, length, batch, batch_stride, h, num_taps, out_start, out_len, y, mem);
 }
 
 int nxsig_fft_nd(nxsig_ctx* ctx, const void* in, int32_t in_is_real, const int64_t* shape, int32_t rank, const int32_t* axes,
@@ -1413,91 +1635,23 @@ int nxsig_fft_nd(nxsig_ctx* ctx, const void* in, int32_t in_is_real, const int64
     osh[ax] = lengths[i];
   }
   for (auto v : osh) n_out *= v;
-  if (mem == NXSIG_DEVICE) return launch_fft_nd(c, in, in_is_real != 0, shape, rank, axes, lengths, n_axes, inverse != 0, reinterpret_cast<float2*>(out));
-  void *di = nullptr, *dout = nullptr;
-  const size_t ibytes = (size_t)n_in * (in_is_real ? sizeof(float) : sizeof(float2)), obytes = (size_t)n_out * sizeof(float2);
-  if ((rc = ctx_scratch(c, 17, ibytes, &di))) return rc;
-  if ((rc = ctx_scratch(c, 18, obytes, &dout))) return rc;
-  NXSIG_HIP_TRY(hipMemcpyAsync(di, in, ibytes, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_fft_nd(c, di, in_is_real != 0, shape, rank, axes, lengths, n_axes, inverse != 0, reinterpret_cast<float2*>(dout)))) return rc;
-  Staged st(c);
-  return st.out_copy(out, dout, obytes);
+  HostIo io(c, mem);
+  io.plain_upload = true;
+  if ((rc = io.open({{in, (size_t)n_in * (in_is_real ? sizeof(float) : sizeof(float2)), kScratchNdStageA}},
+                    {{out, (size_t)n_out * sizeof(float2), kScratchNdStageB}}))) return rc;
+  if ((rc = launch_fft_nd(c, io.in[0], in_is_real != 0, shape, rank, axes, lengths, n_axes, inverse != 0, static_cast<float2*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
 int nxsig_fftconvolve_nd(nxsig_ctx* ctx, const void* a, int32_t a_is_real, const int64_t* a_shape, const void* b, int32_t b_is_real,
                          const int64_t* b_shape, int32_t rank, int32_t mode, void* out, int64_t* out_shape, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!a || !b || !out || !a_shape || !b_shape) return set_error(NXSIG_ERR_INVALID_ARG, "fftconvolve: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, "fftconvolve: rank must be in [1, 8]");
-  if (mem == NXSIG_DEVICE) return launch_fftconvolve_nd(c, a, a_is_real != 0, a_shape, b, b_is_real != 0, b_shape, rank, mode, out, out_shape);
-  int64_t na = 1, nb = 1, no = 1, osh[8];
-  for (int d = 0; d < rank; ++d) {
-    if (a_shape[d] < 1 || b_shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fftconvolve: empty dimension");
-    na *= a_shape[d]; nb *= b_shape[d]; no *= a_shape[d] + b_shape[d] - 1;  // upper bound of every mode's result
-  }
-  const bool real_out = a_is_real && b_is_real;
-  void *da = nullptr, *db = nullptr, *dout = nullptr;
-  const size_t abytes = (size_t)na * (a_is_real ? 4 : 8), bbytes = (size_t)nb * (b_is_real ? 4 : 8);
-  if ((rc = ctx_scratch(c, 17, abytes, &da))) return rc;
-  if ((rc = ctx_scratch(c, 18, bbytes, &db))) return rc;
-  if ((rc = ctx_scratch(c, 19, (size_t)no * (real_out ? 4 : 8), &dout))) return rc;
-  NXSIG_HIP_TRY(hipMemcpyAsync(da, a, abytes, hipMemcpyHostToDevice, c->stream));
-  NXSIG_HIP_TRY(hipMemcpyAsync(db, b, bbytes, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_fftconvolve_nd(c, da, a_is_real != 0, a_shape, db, b_is_real != 0, b_shape, rank, mode, dout, osh))) return rc;
-  int64_t nres = 1;
-  for (int d = 0; d < rank; ++d) { nres *= osh[d]; if (out_shape) out_shape[d] = osh[d]; }
-  Staged st(c);
-  return st.out_copy(out, dout, (size_t)nres * (real_out ? 4 : 8));
-  NXSIG_API_END
+  return conv_nd("fftconvolve", launch_fftconvolve_nd, ctx, a, a_is_real, a_shape, b, b_is_real, b_shape, rank, mode, out, out_shape, mem);
 }
 
 int nxsig_convolve_direct(nxsig_ctx* ctx, const void* a, int32_t a_is_real, const int64_t* a_shape, const void* b, int32_t b_is_real,
                           const int64_t* b_shape, int32_t rank, int32_t mode, void* out, int64_t* out_shape, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!a || !b || !out || !a_shape || !b_shape) return set_error(NXSIG_ERR_INVALID_ARG, "convolve: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, "convolve: rank must be in [1, 8]");
-  if (mem == NXSIG_DEVICE) return launch_convolve_direct(c, a, a_is_real != 0, a_shape, b, b_is_real != 0, b_shape, rank, mode, out, out_shape);
-  int64_t na = 1, nb = 1, no = 1, osh[8];
-  for (int d = 0; d < rank; ++d) {
-    if (a_shape[d] < 1 || b_shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, "convolve: empty dimension");
-    na *= a_shape[d]; nb *= b_shape[d]; no *= a_shape[d] + b_shape[d] - 1;  // upper bound of every mode's result
-  }
-  const bool real_out = a_is_real && b_is_real;
-  void *da = nullptr, *db = nullptr, *dout = nullptr;
-  const size_t abytes = (size_t)na * (a_is_real ? 4 : 8), bbytes = (size_t)nb * (b_is_real ? 4 : 8);
-  if ((rc = ctx_scratch(c, 17, abytes, &da))) return rc;
-  if ((rc = ctx_scratch(c, 18, bbytes, &db))) return rc;
-  if ((rc = ctx_scratch(c, 19, (size_t)no * (real_out ? 4 : 8), &dout))) return rc;
-  NXSIG_HIP_TRY(hipMemcpyAsync(da, a, abytes, hipMemcpyHostToDevice, c->stream));
-  NXSIG_HIP_TRY(hipMemcpyAsync(db, b, bbytes, hipMemcpyHostToDevice, c->stream));
-  if ((rc = launch_convolve_direct(c, da, a_is_real != 0, a_shape, db, b_is_real != 0, b_shape, rank, mode, dout, osh))) return rc;
-  int64_t nres = 1;
-  for (int d = 0; d < rank; ++d) { nres *= osh[d]; if (out_shape) out_shape[d] = osh[d]; }
-  Staged st(c);
-  return st.out_copy(out, dout, (size_t)nres * (real_out ? 4 : 8));
-  NXSIG_API_END
-}
-
-// Filters.median / wiener: the shape checks of filters.ex (and of the Nx.slice / Nx.conv they compose), host staging as in
-// nxsig_convolve_direct
-static int filter_shape(const char* fn, const int64_t* shape, int32_t rank, const int64_t* ks, int64_t* n) {
-  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": rank must be in [1, 8]");
-  *n = 1;
-  for (int d = 0; d < rank; ++d) {
-    if (shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": empty dimension");
-    if (ks[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": window lengths must be >= 1");
-    *n *= shape[d];
-  }
-  return NXSIG_OK;
+  return conv_nd("convolve", launch_convolve_direct, ctx, a, a_is_real, a_shape, b, b_is_real, b_shape, rank, mode, out, out_shape, mem);
 }
 
 int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_shape,
@@ -1514,14 +1668,10 @@ int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int
     if (kernel_shape[d] > shape[d])
       return set_error(NXSIG_ERR_INVALID_ARG, "median: kernel_shape " + std::to_string(kernel_shape[d]) + " exceeds dimension " +
                                                   std::to_string(shape[d]) + " of axis " + std::to_string(d));
-  if (mem == NXSIG_DEVICE) return launch_median(c, x, is_f64 != 0, shape, rank, kernel_shape, out);
-  Staged st(c);
-  const void* dx = nullptr;
-  void* dout = nullptr;
-  if ((rc = st.in(17, x, (size_t)n * (is_f64 ? 8 : 4), &dx))) return rc;
-  if ((rc = st.out_alloc(19, (size_t)n * 4, &dout))) return rc;
-  if ((rc = launch_median(c, dx, is_f64 != 0, shape, rank, kernel_shape, static_cast<float*>(dout)))) return rc;
-  return st.out_copy(out, dout, (size_t)n * 4);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, (size_t)n * (is_f64 ? 8 : 4), kScratchNdStageA}}, {{out, (size_t)n * 4, kScratchNdStageOut}}))) return rc;
+  if ((rc = launch_median(c, io.in[0], is_f64 != 0, shape, rank, kernel_shape, static_cast<float*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1537,17 +1687,10 @@ int nxsig_wiener(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* s
   if ((rc = filter_shape("wiener", shape, rank, kernel_size, &n))) return rc;
   const size_t bytes = (size_t)n * (is_f64 ? 8 : 4);
   const double* noise_dev = nullptr;
-  if (mem == NXSIG_DEVICE) {
-    if ((rc = launch_wiener(c, x, is_f64 != 0, shape, rank, kernel_size, has_noise != 0, noise, out, &noise_dev))) return rc;
-  } else {
-    Staged st(c);
-    const void* dx = nullptr;
-    void* dout = nullptr;
-    if ((rc = st.in(17, x, bytes, &dx))) return rc;
-    if ((rc = st.out_alloc(19, bytes, &dout))) return rc;
-    if ((rc = launch_wiener(c, dx, is_f64 != 0, shape, rank, kernel_size, has_noise != 0, noise, dout, &noise_dev))) return rc;
-    if ((rc = st.out_copy(out, dout, bytes))) return rc;
-  }
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, bytes, kScratchNdStageA}}, {{out, bytes, kScratchNdStageOut}}))) return rc;
+  if ((rc = launch_wiener(c, io.in[0], is_f64 != 0, shape, rank, kernel_size, has_noise != 0, noise, io.out[0], &noise_dev))) return rc;
+  if ((rc = io.close())) return rc;
   if (noise_used) {
     if (noise_dev) {
       NXSIG_HIP_TRY(hipMemcpyAsync(noise_used, noise_dev, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1558,40 +1701,6 @@ int nxsig_wiener(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* s
   }
   return NXSIG_OK;
   NXSIG_API_END
-}
-
-// PeakFinding.argrelextrema / nonzero: the port's limits, host staging as in nxsig_median_filter
-static int peaks_shape(const char* fn, const int64_t* shape, int32_t rank, int64_t* n) {
-  if (!shape) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
-  if (rank < 1 || rank > 8) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": rank must be in [1, 8]");
-  *n = 1;
-  for (int d = 0; d < rank; ++d) {
-    if (shape[d] < 1) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": empty dimension");
-    if (shape[d] >= ((int64_t)1 << 31)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": a dimension of 2^31 or more");
-    *n *= shape[d];
-    if (*n >= ((int64_t)1 << 32)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": 2^32 or more elements");
-  }
-  return NXSIG_OK;
-}
-
-static int peaks_out(int64_t n, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem, Staged* st, int32_t** di, uint32_t** dv) {
-  if (mem == NXSIG_DEVICE) {
-    *di = indices;
-    *dv = valid;
-    return NXSIG_OK;
-  }
-  void *a = nullptr, *b = nullptr;
-  int rc = st->out_alloc(19, (size_t)n * rank * 4, &a);
-  if (rc || (rc = st->out_alloc(18, 4, &b))) return rc;
-  *di = static_cast<int32_t*>(a);
-  *dv = static_cast<uint32_t*>(b);
-  return NXSIG_OK;
-}
-
-static int peaks_copy(int64_t n, int32_t rank, int32_t* indices, uint32_t* valid, int32_t mem, Staged* st, int32_t* di, uint32_t* dv) {
-  if (mem == NXSIG_DEVICE) return NXSIG_OK;
-  int rc = st->out_copy(valid, dv, 4);
-  return rc ? rc : st->out_copy(indices, di, (size_t)n * rank * 4);
 }
 
 int nxsig_argrelextrema(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t* shape, int32_t rank, int32_t axis, int64_t shifts,
@@ -1610,14 +1719,11 @@ int nxsig_argrelextrema(nxsig_ctx* ctx, const void* x, int32_t dtype, const int6
   if (comparator < NXSIG_CMP_LESS || comparator > NXSIG_CMP_GREATER_EQUAL) return set_error(NXSIG_ERR_INVALID_ARG, "argrelextrema: unknown comparator");
   if (shifts < 0) shifts = 0;
   const size_t es = dtype == NXSIG_DT_F64 || dtype == NXSIG_DT_S64 || dtype == NXSIG_DT_U64 ? 8 : 4;
-  Staged st(c);
-  const void* dx = x;
-  if (mem == NXSIG_HOST && (rc = st.in(17, x, (size_t)n * es, &dx))) return rc;
-  int32_t* di = nullptr;
-  uint32_t* dv = nullptr;
-  if ((rc = peaks_out(n, rank, indices, valid, mem, &st, &di, &dv))) return rc;
-  if ((rc = launch_argrelextrema(c, dx, dtype, shape, rank, axis, shifts, comparator, di, dv))) return rc;
-  return peaks_copy(n, rank, indices, valid, mem, &st, di, dv);
+  HostIo io(c, mem);
+  if ((rc = peaks_open(io, x, (size_t)n * es, n, rank, indices, valid))) return rc;
+  if ((rc = launch_argrelextrema(c, io.in[0], dtype, shape, rank, axis, shifts, comparator, static_cast<int32_t*>(io.out[1]),
+                                 static_cast<uint32_t*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1630,78 +1736,13 @@ int nxsig_nonzero(nxsig_ctx* ctx, const uint8_t* mask, const int64_t* shape, int
   if (rc) return rc;
   int64_t n = 0;
   if ((rc = peaks_shape("nonzero", shape, rank, &n))) return rc;
-  Staged st(c);
-  const void* dm = mask;
-  if (mem == NXSIG_HOST && (rc = st.in(17, mask, (size_t)n, &dm))) return rc;
-  int32_t* di = nullptr;
-  uint32_t* dv = nullptr;
-  if ((rc = peaks_out(n, rank, indices, valid, mem, &st, &di, &dv))) return rc;
-  if ((rc = launch_nonzero(c, static_cast<const uint8_t*>(dm), shape, rank, di, dv))) return rc;
-  return peaks_copy(n, rank, indices, valid, mem, &st, di, dv);
+  HostIo io(c, mem);
+  if ((rc = peaks_open(io, mask, (size_t)n, n, rank, indices, valid))) return rc;
+  if ((rc = launch_nonzero(c, static_cast<const uint8_t*>(io.in[0]), shape, rank, static_cast<int32_t*>(io.out[1]),
+                           static_cast<uint32_t*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
-
-// NxSignal.Waveforms (lib/nx_signal/waveforms.ex; DESIGN.md section 3.10): the reference's ArgumentErrors, the scalars that do not
-// depend on t computed once under the tier's rounding (f32: every op in double on f32 operands, rounded to f32; f64: no rounding;
-// pi() the f32 constant in both), host staging as in nxsig_median_filter.
-extern "C++" {
-namespace {
-constexpr double kWavePi = 3.1415927410125732;   // Nx.Constants.pi() as f32
-constexpr double kWaveTwoPi = 2.0 * kWavePi;     // 2 * pi(): exact
-
-struct WaveRound {
-  bool f64;
-  double operator()(double x) const { return f64 ? x : (double)(float)x; }
-};
-
-std::string wave_num(double v) {
-  char buf[40];
-  std::snprintf(buf, sizeof buf, "%.17g", v);
-  return buf;
-}
-
-// t (and a second stream) in, `nout` outputs of out_es-byte elements out: device pointers are used as they are, host ones are staged
-struct WaveIo {
-  Staged st;
-  const void *dt = nullptr, *d2 = nullptr;
-  void* dout[3] = {};
-  void* hout[3] = {};
-  size_t out_bytes = 0;
-  bool host = false;
-  explicit WaveIo(Ctx* c) : st(c) {}
-  int open(int32_t mem, const void* t, const void* second, size_t in_es, int64_t n, void* const* outs, int nout, size_t out_es) {
-    host = mem == NXSIG_HOST;
-    out_bytes = (size_t)n * out_es;
-    dt = t;
-    d2 = second;
-    for (int j = 0; j < nout; ++j) dout[j] = hout[j] = outs[j];
-    if (!host) return NXSIG_OK;
-    int rc = st.in(17, t, (size_t)n * in_es, &dt);
-    if (rc) return rc;
-    if (second && (rc = st.in(18, second, (size_t)n * in_es, &d2))) return rc;
-    const size_t stride = (out_bytes + 255) & ~(size_t)255;
-    void* base = nullptr;
-    if ((rc = st.out_alloc(19, stride * nout, &base))) return rc;
-    for (int j = 0; j < nout; ++j) dout[j] = static_cast<char*>(base) + stride * j;
-    return NXSIG_OK;
-  }
-  int close(int nout) {
-    if (!host) return NXSIG_OK;
-    for (int j = 0; j < nout; ++j) {
-      const int rc = st.out_copy(hout[j], dout[j], out_bytes);
-      if (rc) return rc;
-    }
-    return NXSIG_OK;
-  }
-};
-
-int wave_args(const char* fn, const void* t, const void* out, int64_t n, int32_t mem) {
-  if (n < 0) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": n must be >= 0");
-  if (n > 0 && (!t || !out)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
-  return check_mem(mem);
-}
-}  // namespace
-}  // extern "C++"
 
 int nxsig_sawtooth(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double width, void* out, int32_t mem) {
   NXSIG_API_BEGIN
@@ -1720,11 +1761,11 @@ int nxsig_sawtooth(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, dou
   p.c_fall = R(kWavePi * (width + 1.0));
   p.d_fall = R(kWavePi * (1.0 - width));
   p.mode = width == 1.0 ? 1 : width == 0.0 ? 0 : 2;
-  WaveIo io(c);
+  HostIo io(c, mem);
   const size_t es = is_f64 ? 8 : 4;
-  if ((rc = io.open(mem, t, nullptr, es, n, &out, 1, es))) return rc;
-  if ((rc = launch_sawtooth(c, io.dt, is_f64 != 0, n, p, io.dout[0]))) return rc;
-  return io.close(1);
+  if ((rc = wave_open(io, t, nullptr, es, n, out, es))) return rc;
+  if ((rc = launch_sawtooth(c, io.in[0], is_f64 != 0, n, p, io.out[0]))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1739,11 +1780,10 @@ int nxsig_square(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, doubl
   p.two_pi = kWaveTwoPi;
   p.pi = kWavePi;
   p.thr = R(R(R(duty) * 2.0) * kWavePi);   // duty * 2 * pi(), duty a tensor argument of square_n
-  WaveIo io(c);
-  void* o = out;
-  if ((rc = io.open(mem, t, duty_tensor, is_f64 ? 8 : 4, n, &o, 1, 4))) return rc;
-  if ((rc = launch_square(c, io.dt, is_f64 != 0, n, p, io.d2, static_cast<int32_t*>(io.dout[0])))) return rc;
-  return io.close(1);
+  HostIo io(c, mem);
+  if ((rc = wave_open(io, t, duty_tensor, is_f64 ? 8 : 4, n, out, 4))) return rc;
+  if ((rc = launch_square(c, io.in[0], is_f64 != 0, n, p, io.in[1], static_cast<int32_t*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1768,12 +1808,13 @@ int nxsig_gaussian_pulse(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t 
   WaveGauss p;
   p.neg_a = R(-a);
   p.w = R(kWaveTwoPi * R(fc));
-  WaveIo io(c);
-  const size_t es = is_f64 ? 8 : 4;
-  void* outs[3] = {envelope, in_phase, quadrature};
-  if ((rc = io.open(mem, t, nullptr, es, n, outs, 3, es))) return rc;
-  if ((rc = launch_gaussian_pulse(c, io.dt, is_f64 != 0, n, p, io.dout[0], io.dout[1], io.dout[2]))) return rc;
-  return io.close(3);
+  HostIo io(c, mem);
+  const size_t bytes = (size_t)n * (is_f64 ? 8 : 4);
+  if ((rc = io.open({{t, bytes, kScratchNdStageA}},
+                    {{envelope, bytes, kScratchNdStageOut, wave_span(bytes)}, {in_phase, bytes, kScratchNdStageOut, wave_span(bytes)},
+                     {quadrature, bytes, kScratchNdStageOut, wave_span(bytes)}}))) return rc;
+  if ((rc = launch_gaussian_pulse(c, io.in[0], is_f64 != 0, n, p, io.out[0], io.out[1], io.out[2]))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1830,11 +1871,11 @@ int nxsig_chirp(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_t n, double
       p.b = sp;
     }
   }
-  WaveIo io(c);
+  HostIo io(c, mem);
   const size_t es = is_f64 ? 8 : 4;
-  if ((rc = io.open(mem, t, nullptr, es, n, &out, 1, es))) return rc;
-  if ((rc = launch_chirp(c, io.dt, is_f64 != 0, n, p, family, io.dout[0]))) return rc;
-  return io.close(1);
+  if ((rc = wave_open(io, t, nullptr, es, n, out, es))) return rc;
+  if ((rc = launch_chirp(c, io.in[0], is_f64 != 0, n, p, family, io.out[0]))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1855,11 +1896,11 @@ int nxsig_polynomial_sweep(nxsig_ctx* ctx, const void* t, int32_t is_f64, int64_
   p.two_pi = kWaveTwoPi;
   p.phi = phi_degrees ? R(phi * kWavePi / 180.0) : R(phi);   // phi * pi() / 180: constants, folded in double
   for (int k = 0; k < ncoefs; ++k) p.coef[k] = R(R(coefs[k]) / (double)(ncoefs - k));
-  WaveIo io(c);
+  HostIo io(c, mem);
   const size_t es = is_f64 ? 8 : 4;
-  if ((rc = io.open(mem, t, nullptr, es, n, &out, 1, es))) return rc;
-  if ((rc = launch_polynomial_sweep(c, io.dt, is_f64 != 0, n, p, io.dout[0]))) return rc;
-  return io.close(1);
+  if ((rc = wave_open(io, t, nullptr, es, n, out, es))) return rc;
+  if ((rc = launch_polynomial_sweep(c, io.in[0], is_f64 != 0, n, p, io.out[0]))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1888,12 +1929,10 @@ int nxsig_unit_impulse(nxsig_ctx* ctx, int32_t dtype, const int64_t* shape, int3
     at = at * shape[d] + index[d];
   }
   const size_t bytes = (size_t)n * (dtype == NXSIG_DT_F64 || dtype == NXSIG_DT_S64 || dtype == NXSIG_DT_U64 ? 8 : 4);
-  if (mem == NXSIG_DEVICE) return launch_unit_impulse(c, out, dtype, n, at);
-  Staged st(c);
-  void* dout = nullptr;
-  if ((rc = st.out_alloc(19, bytes, &dout))) return rc;
-  if ((rc = launch_unit_impulse(c, dout, dtype, n, at))) return rc;
-  return st.out_copy(out, dout, bytes);
+  HostIo io(c, mem);
+  if ((rc = io.open({}, {{out, bytes, kScratchNdStageOut}}))) return rc;
+  if ((rc = launch_unit_impulse(c, io.out[0], dtype, n, at))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1906,26 +1945,15 @@ int nxsig_fftconvolve_c64(nxsig_ctx* ctx, const nxsig_c64* a, int64_t n1, const 
   int rc = check_mem(mem);
   if (rc) return rc;
   if (n1 < 1 || n2 < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fftconvolve: lengths must be >= 1");
-  const int64_t full = n1 + n2 - 1;
   int64_t out_len, start;
-  switch (mode) {  // lib/nx_signal/convolution.ex:300-329
-    case NXSIG_CONV_FULL: out_len = full; start = 0; break;
-    case NXSIG_CONV_SAME: out_len = n1; start = (full - out_len) / 2; break;
-    case NXSIG_CONV_VALID: out_len = (n1 >= n2 ? n1 - n2 : n2 - n1) + 1; start = (full - out_len) / 2; break;
-    default: return set_error(NXSIG_ERR_INVALID_ARG, "expected mode to be one of [:full, :same, :valid]");
-  }
-  if (mem == NXSIG_DEVICE)
-    return launch_fftconvolve_c64(c, reinterpret_cast<const float2*>(a), n1, reinterpret_cast<const float2*>(b), n2, start, out_len,
-                                  reinterpret_cast<float2*>(out));
-  Staged st(c);
-  const void *ad = nullptr, *bd = nullptr;
-  void* od = nullptr;
-  if ((rc = st.in(1, a, (size_t)n1 * sizeof(float2), &ad))) return rc;
-  if ((rc = st.in(2, b, (size_t)n2 * sizeof(float2), &bd))) return rc;
-  if ((rc = ctx_scratch(c, 4, (size_t)(out_len > 8192 ? out_len : 8192) * sizeof(float2), &od))) return rc;
-  if ((rc = launch_fftconvolve_c64(c, reinterpret_cast<const float2*>(ad), n1, reinterpret_cast<const float2*>(bd), n2, start, out_len,
-                                   reinterpret_cast<float2*>(od)))) return rc;
-  return st.out_copy(out, od, (size_t)out_len * sizeof(float2));
+  if ((rc = conv_slice(n1, n2, mode, &start, &out_len))) return rc;
+  // (the launcher works in blocks of 8 192 points: the staged result is never shorter)
+  HostIo io(c, mem);
+  if ((rc = io.open({{a, (size_t)n1 * sizeof(float2), kScratchStageIn}, {b, (size_t)n2 * sizeof(float2), kScratchStageOut}},
+                    {{out, (size_t)out_len * sizeof(float2), kScratchFusedSpectrum, (size_t)8192 * sizeof(float2)}}))) return rc;
+  if ((rc = launch_fftconvolve_c64(c, static_cast<const float2*>(io.in[0]), n1, static_cast<const float2*>(io.in[1]), n2, start, out_len,
+                                   static_cast<float2*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1949,14 +1977,11 @@ int nxsig_stft_to_mel(nxsig_ctx* ctx, const nxsig_c64* z, int64_t rows, int32_t 
   if (rc) return rc;
   if (rows < 1 || fft_length < 2 || mel_bins < 1) return set_error(NXSIG_ERR_INVALID_ARG, "stft_to_mel: rows, fft_length, mel_bins must be positive");
   if (fft_length / 2 > 8192) return set_error(NXSIG_ERR_UNSUPPORTED, "stft_to_mel: fft_length > 16384 is not supported");
-  const size_t zbytes = (size_t)rows * fft_length * sizeof(float2), obytes = (size_t)rows * mel_bins * sizeof(float);
-  if (mem == NXSIG_DEVICE) return launch_stft_to_mel(c, reinterpret_cast<const float2*>(z), rows, fft_length, mel_bins, filters, out);
-  Staged st(c);
-  const void* zd = nullptr; void* od = nullptr;
-  if ((rc = st.in(1, z, zbytes, &zd))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_stft_to_mel(c, reinterpret_cast<const float2*>(zd), rows, fft_length, mel_bins, filters, reinterpret_cast<float*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
+  HostIo io(c, mem);
+  if ((rc = io.open({{z, (size_t)rows * fft_length * sizeof(float2), kScratchStageIn}}, {{out, (size_t)rows * mel_bins * sizeof(float), kScratchStageOut}})))
+    return rc;
+  if ((rc = launch_stft_to_mel(c, static_cast<const float2*>(io.in[0]), rows, fft_length, mel_bins, filters, static_cast<float*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
@@ -1976,12 +2001,11 @@ int nxsig_spectrum_mul_c64(nxsig_ctx* ctx, const nxsig_c64* z, int64_t rows, int
   if (mem == NXSIG_DEVICE)
     return launch_spectrum_mul(c, reinterpret_cast<const float2*>(z), rows, fft_length, reinterpret_cast<const float2*>(hd),
                                reinterpret_cast<float2*>(out));
-  Staged st(c);
-  const void* zd = nullptr;
-  if ((rc = st.in(1, z, bytes, &zd))) return rc;
-  float2* zw = reinterpret_cast<float2*>(const_cast<void*>(zd));
+  HostIo io(c, mem);   // host tensors: the product is formed in place in the staged input
+  if ((rc = io.open({{z, bytes, kScratchStageIn}}, {}))) return rc;
+  float2* zw = static_cast<float2*>(const_cast<void*>(io.in[0]));
   if ((rc = launch_spectrum_mul(c, zw, rows, fft_length, reinterpret_cast<const float2*>(hd), zw))) return rc;
-  return st.out_copy(out, zw, bytes);
+  return io.download(out, zw, bytes);
   NXSIG_API_END
 }
 
@@ -1991,56 +2015,22 @@ int nxsig_stft_mel_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t b
   NXSIG_API_BEGIN
   NXSIG_CHECK_CTX(ctx)
   DispatchScope dispatch_scope(c);
-  if (!x || !window || !p || !filters || !out) return set_error(NXSIG_ERR_INVALID_ARG, "stft_mel: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || batch > 65535) return set_error(NXSIG_ERR_INVALID_ARG, "stft_mel: batch must be in [1, 65535]");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "stft_mel: batch_stride < length");
-  if (p->fft_length < 2 || mel_bins < 1) return set_error(NXSIG_ERR_INVALID_ARG, "stft_mel: fft_length >= 2 and mel_bins >= 1 required");
-  rc = check_scaling(p->scaling);
-  if (rc) return rc;
+  StftEntry e{"stft_mel", 65535, 2, ": fft_length >= 2 and mel_bins >= 1 required"};
+  e.extra_null = !filters;
+  e.fft_length_also = mel_bins < 1;
   Framing fr;
-  rc = make_framing(length, p->frame_length, p->hop, p->pad_mode, p->pad_lo, p->pad_hi, &fr);
+  int rc = stft_check(e, x, window, p, out, length, batch, batch_stride, mem, &fr, num_frames_out);
   if (rc) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
   StftLaunch a;
-  a.fr = fr; a.batch = batch; a.batch_stride = batch_stride; a.K = p->fft_length;
-  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
-  a.inv_scale_div = a.has_scale ? scaling_factor(window, p->frame_length, p->scaling, p->sampling_rate) : 1.0f;
-  rc = ctx_window(c, window, p->frame_length, p->fft_length, &a.window, &a.window_padK);
-  if (rc) return rc;
-  a.z = nullptr;
-  const size_t obytes = (size_t)batch * fr.M * mel_bins * sizeof(float);
-  Staged st(c);
-  float* od = out;
-  if (mem == NXSIG_DEVICE) {
-    a.x = x;
-  } else {
-    const void* xd = nullptr; void* o2 = nullptr;
-    const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
-    if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-    if ((rc = st.out_alloc(2, obytes, &o2))) return rc;
-    a.x = reinterpret_cast<const float*>(xd); od = reinterpret_cast<float*>(o2);
-  }
-  bool handled = false;
-  rc = launch_stft_mel_wave(c, a, mel_bins, filters, od, &handled);
-  if (rc) return rc;
-  if (!handled) {  // two-step path: spectrum in a scratch buffer, then the band-sum kernel
-    void* zs = nullptr;
-    if ((rc = ctx_scratch(c, 4, (size_t)batch * fr.M * p->fft_length * sizeof(float2), &zs))) return rc;
-    a.z = reinterpret_cast<float2*>(zs);
-    if ((rc = launch_stft(c, a))) return rc;
-    if ((rc = launch_stft_to_mel(c, a.z, (int64_t)batch * fr.M, p->fft_length, mel_bins, filters, od))) return rc;
-  }
-  if (mem == NXSIG_DEVICE) return NXSIG_OK;
-  return st.out_copy(out, od, obytes);
+  if ((rc = stft_plan(c, fr, batch, batch_stride, window, p, &a))) return rc;
+  const int64_t rows = (int64_t)batch * fr.M;
+  return stft_fused_sink(
+      c, a, x, length, out, sizeof(float), (size_t)rows * mel_bins, mem,
+      [&](const StftLaunch& s, void* od, bool* handled) { return launch_stft_mel_wave(c, s, mel_bins, filters, static_cast<float*>(od), handled); },
+      [&](const StftLaunch& s, void* od) { return launch_stft_to_mel(c, s.z, rows, s.K, mel_bins, filters, static_cast<float*>(od)); });
   NXSIG_API_END
 }
 
-}  // extern "C"
-static int stft_onesided_impl(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
-                              const nxsig_stft_params* p, nxsig_c64* out, int64_t* num_frames_out, int32_t mem, bool packed);
-extern "C" {
 int nxsig_stft_onesided_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
                             const nxsig_stft_params* p, nxsig_c64* out, int64_t* num_frames_out, int32_t mem) {
   return stft_onesided_impl(ctx, x, length, batch, batch_stride, window, p, out, num_frames_out, mem, false);
@@ -2049,115 +2039,29 @@ int nxsig_stft_packed_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_
                           const nxsig_stft_params* p, nxsig_c64* out, int64_t* num_frames_out, int32_t mem) {
   return stft_onesided_impl(ctx, x, length, batch, batch_stride, window, p, out, num_frames_out, mem, true);
 }
-}  // extern "C"
-static int stft_onesided_impl(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
-                              const nxsig_stft_params* p, nxsig_c64* out, int64_t* num_frames_out, int32_t mem, bool packed) {
-  NXSIG_API_BEGIN
-  if (!x || !window || !p || !out) return set_error(NXSIG_ERR_INVALID_ARG, "stft_onesided: null pointer argument");
-  if (packed && (p->fft_length & 1)) return set_error(NXSIG_ERR_INVALID_ARG, "stft_packed: fft_length must be even");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || batch > 65535) return set_error(NXSIG_ERR_INVALID_ARG, "stft_onesided: batch must be in [1, 65535]");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "stft_onesided: batch_stride < length");
-  if (p->fft_length < 2) return set_error(NXSIG_ERR_INVALID_ARG, "stft_onesided: fft_length >= 2 required");
-  rc = check_scaling(p->scaling);
-  if (rc) return rc;
-  Framing fr;
-  rc = make_framing(length, p->frame_length, p->hop, p->pad_mode, p->pad_lo, p->pad_hi, &fr);
-  if (rc) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  StftLaunch a;
-  a.fr = fr; a.batch = batch; a.batch_stride = batch_stride; a.K = p->fft_length;
-  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
-  a.inv_scale_div = a.has_scale ? scaling_factor(window, p->frame_length, p->scaling, p->sampling_rate) : 1.0f;
-  rc = ctx_window(c, window, p->frame_length, p->fft_length, &a.window, &a.window_padK);
-  if (rc) return rc;
-  a.z = nullptr;
-  const int half = p->fft_length / 2;
-  const size_t obytes = (size_t)batch * fr.M * half * sizeof(float2);
-  Staged st(c);
-  float2* od = reinterpret_cast<float2*>(out);
-  if (mem == NXSIG_DEVICE) {
-    a.x = x;
-  } else {
-    const void* xd = nullptr; void* o2 = nullptr;
-    const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
-    if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-    if ((rc = st.out_alloc(2, obytes, &o2))) return rc;
-    a.x = reinterpret_cast<const float*>(xd); od = reinterpret_cast<float2*>(o2);
-  }
-  bool handled = false;
-  rc = launch_stft_mag_wave(c, a, packed ? 4 : 3 /* complex bins */, reinterpret_cast<float*>(od), &handled);
-  if (rc) return rc;
-  if (!handled) {  // two-step path: full spectrum in a scratch buffer, then the slice
-    void* zs = nullptr;
-    if ((rc = ctx_scratch(c, 4, (size_t)batch * fr.M * p->fft_length * sizeof(float2), &zs))) return rc;
-    a.z = reinterpret_cast<float2*>(zs);
-    if ((rc = launch_stft(c, a))) return rc;
-    if ((rc = launch_half_from_spectrum(c, a.z, (int64_t)batch * fr.M, p->fft_length, od, packed))) return rc;
-  }
-  if (mem == NXSIG_DEVICE) return NXSIG_OK;
-  return st.out_copy(out, od, obytes);
-  NXSIG_API_END
-}
-extern "C" {
 
 int nxsig_stft_magnitude_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride,
                              const float* window, const nxsig_stft_params* p, int32_t kind, float* out,
                              int64_t* num_frames_out, int32_t mem) {
   NXSIG_API_BEGIN
-  if (!x || !window || !p || !out) return set_error(NXSIG_ERR_INVALID_ARG, "stft_magnitude: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
+  StftEntry e{"stft_magnitude", 65535, 2, ": fft_length >= 2 required"};
   if (kind != NXSIG_MAG_ABS && kind != NXSIG_MAG_POWER && kind != NXSIG_MAG_DBFS)
-    return set_error(NXSIG_ERR_INVALID_ARG, "stft_magnitude: kind must be NXSIG_MAG_ABS, NXSIG_MAG_POWER or NXSIG_MAG_DBFS");
-  if (batch < 1 || batch > 65535) return set_error(NXSIG_ERR_INVALID_ARG, "stft_magnitude: batch must be in [1, 65535]");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "stft_magnitude: batch_stride < length");
-  if (p->fft_length < 2) return set_error(NXSIG_ERR_INVALID_ARG, "stft_magnitude: fft_length >= 2 required");
-  rc = check_scaling(p->scaling);
-  if (rc) return rc;
+    e.after_mem = "stft_magnitude: kind must be NXSIG_MAG_ABS, NXSIG_MAG_POWER or NXSIG_MAG_DBFS";
   Framing fr;
-  rc = make_framing(length, p->frame_length, p->hop, p->pad_mode, p->pad_lo, p->pad_hi, &fr);
+  int rc = stft_check(e, x, window, p, out, length, batch, batch_stride, mem, &fr, num_frames_out);
   if (rc) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
   NXSIG_CHECK_CTX(ctx)
   DispatchScope dispatch_scope(c);
   StftLaunch a;
-  a.fr = fr; a.batch = batch; a.batch_stride = batch_stride; a.K = p->fft_length;
-  a.has_scale = p->scaling != NXSIG_SCALE_NONE;
-  a.inv_scale_div = a.has_scale ? scaling_factor(window, p->frame_length, p->scaling, p->sampling_rate) : 1.0f;
-  rc = ctx_window(c, window, p->frame_length, p->fft_length, &a.window, &a.window_padK);
-  if (rc) return rc;
-  a.z = nullptr;
-  const int half = p->fft_length / 2;
-  const size_t obytes = (size_t)batch * fr.M * half * sizeof(float);
-  Staged st(c);
-  float* od = out;
-  if (mem == NXSIG_DEVICE) {
-    a.x = x;
-  } else {
-    const void* xd = nullptr; void* o2 = nullptr;
-    const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
-    if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-    if ((rc = st.out_alloc(2, obytes, &o2))) return rc;
-    a.x = reinterpret_cast<const float*>(xd); od = reinterpret_cast<float*>(o2);
-  }
-  bool handled = false;
-  rc = launch_stft_mag_wave(c, a, kind, od, &handled);
-  if (rc) return rc;
-  if (!handled) {  // two-step path: spectrum in a scratch buffer, then the magnitude kernel
-    void* zs = nullptr;
-    if ((rc = ctx_scratch(c, 4, (size_t)batch * fr.M * p->fft_length * sizeof(float2), &zs))) return rc;
-    a.z = reinterpret_cast<float2*>(zs);
-    if ((rc = launch_stft(c, a))) return rc;
-    if ((rc = launch_mag_from_spectrum(c, a.z, (int64_t)batch * fr.M, p->fft_length, kind, od))) return rc;
-  }
-  if (mem == NXSIG_DEVICE) return NXSIG_OK;
-  return st.out_copy(out, od, obytes);
+  if ((rc = stft_plan(c, fr, batch, batch_stride, window, p, &a))) return rc;
+  const int64_t rows = (int64_t)batch * fr.M;
+  return stft_fused_sink(
+      c, a, x, length, out, sizeof(float), (size_t)rows * (p->fft_length / 2), mem,
+      [&](const StftLaunch& s, void* od, bool* handled) { return launch_stft_mag_wave(c, s, kind, static_cast<float*>(od), handled); },
+      [&](const StftLaunch& s, void* od) { return launch_mag_from_spectrum(c, s.z, rows, s.K, kind, static_cast<float*>(od)); });
   NXSIG_API_END
 }
+
 
 /* ---------------------------------------------------------------- f64 / c128 tier (kernels_f64.hip) */
 int nxsig_window_f64(int32_t kind, int32_t n, int32_t is_periodic, double beta, double eps, double* out) {
@@ -2231,18 +2135,12 @@ int nxsig_stft_f64(nxsig_ctx* ctx, const double* x, int64_t length, int32_t batc
   std::vector<double> wide;
   if ((rc = window_dev_f64(c, window, window_is_f64, p->frame_length, wide, &a.window))) return rc;
   const size_t zbytes = (size_t)batch * fr.M * p->fft_length * sizeof(double2);
-  if (mem == NXSIG_DEVICE) {
-    a.x = x; a.z = reinterpret_cast<double2*>(z);
-    return launch_stft_f64(c, a);
-  }
-  Staged st(c);
-  const void* xd = nullptr; void* zd = nullptr;
   const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(double);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, zbytes, &zd))) return rc;
-  a.x = reinterpret_cast<const double*>(xd); a.z = reinterpret_cast<double2*>(zd);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, xbytes, kScratchStageIn}}, {{z, zbytes, kScratchStageOut}}))) return rc;
+  a.x = static_cast<const double*>(io.in[0]); a.z = static_cast<double2*>(io.out[0]);
   if ((rc = launch_stft_f64(c, a))) return rc;
-  return st.out_copy(z, zd, zbytes);
+  return io.close();
   NXSIG_API_END
 }
 
@@ -2269,18 +2167,12 @@ int nxsig_stft_c128(nxsig_ctx* ctx, const nxsig_c128* x, int64_t length, int32_t
   if ((rc = window_dev_f64(c, window, window_is_f64, p->frame_length, wide, &a.window))) return rc;
   dispatch_note("stft.f64.c128");
   const size_t zbytes = (size_t)batch * fr.M * p->fft_length * sizeof(double2);
-  if (mem == NXSIG_DEVICE) {
-    a.x = reinterpret_cast<const double*>(x); a.z = reinterpret_cast<double2*>(z);
-    return launch_stft_f64(c, a);
-  }
-  Staged st(c);
-  const void* xd = nullptr; void* zd = nullptr;
   const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(double2);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, zbytes, &zd))) return rc;
-  a.x = reinterpret_cast<const double*>(xd); a.z = reinterpret_cast<double2*>(zd);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, xbytes, kScratchStageIn}}, {{z, zbytes, kScratchStageOut}}))) return rc;
+  a.x = static_cast<const double*>(io.in[0]); a.z = static_cast<double2*>(io.out[0]);
   if ((rc = launch_stft_f64(c, a))) return rc;
-  return st.out_copy(z, zd, zbytes);
+  return io.close();
   NXSIG_API_END
 }
 
@@ -2309,17 +2201,11 @@ int nxsig_istft_c128(nxsig_ctx* ctx, const nxsig_c128* z, int64_t num_frames, in
   if ((rc = window_dev_f64(c, window, window_is_f64, N, wide, &a.window))) return rc;
   const int64_t out_len = num_frames * hop + (N - hop);
   const size_t zbytes = (size_t)batch * num_frames * K * sizeof(double2), ybytes = (size_t)batch * out_len * sizeof(double2);
-  if (mem == NXSIG_DEVICE) {
-    a.z = reinterpret_cast<const double2*>(z); a.y = reinterpret_cast<double2*>(y);
-    return launch_istft_f64(c, a);
-  }
-  Staged st(c);
-  const void* zd = nullptr; void* yd = nullptr;
-  if ((rc = st.in(1, z, zbytes, &zd))) return rc;
-  if ((rc = st.out_alloc(2, ybytes, &yd))) return rc;
-  a.z = reinterpret_cast<const double2*>(zd); a.y = reinterpret_cast<double2*>(yd);
+  HostIo io(c, mem);
+  if ((rc = io.open({{z, zbytes, kScratchStageIn}}, {{y, ybytes, kScratchStageOut}}))) return rc;
+  a.z = static_cast<const double2*>(io.in[0]); a.y = static_cast<double2*>(io.out[0]);
   if ((rc = launch_istft_f64(c, a))) return rc;
-  return st.out_copy(y, yd, ybytes);
+  return io.close();
   NXSIG_API_END
 }
 
@@ -2334,125 +2220,32 @@ int nxsig_fft_c128(nxsig_ctx* ctx, const void* in, int32_t in_is_real, int64_t r
   if (rows < 1 || n_in < 1 || fft_length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fft: rows, n_in and fft_length must be >= 1");
   const size_t ibytes = (size_t)rows * n_in * (in_is_real ? sizeof(double) : sizeof(double2));
   const size_t obytes = (size_t)rows * fft_length * sizeof(double2);
-  if (mem == NXSIG_DEVICE) return launch_fft_f64(c, in, in_is_real != 0, rows, n_in, fft_length, inverse != 0, reinterpret_cast<double2*>(out));
-  Staged st(c);
-  const void* id = nullptr; void* od = nullptr;
-  if ((rc = st.in(1, in, ibytes, &id))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_fft_f64(c, id, in_is_real != 0, rows, n_in, fft_length, inverse != 0, reinterpret_cast<double2*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
+  HostIo io(c, mem);
+  if ((rc = io.open({{in, ibytes, kScratchStageIn}}, {{out, obytes, kScratchStageOut}}))) return rc;
+  if ((rc = launch_fft_f64(c, io.in[0], in_is_real != 0, rows, n_in, fft_length, inverse != 0, static_cast<double2*>(io.out[0])))) return rc;
+  return io.close();
   NXSIG_API_END
 }
 
 int nxsig_as_windowed_f64(nxsig_ctx* ctx, const double* x, int64_t length, int32_t batch, int64_t batch_stride, int32_t window_length,
                           int32_t stride, int32_t pad_mode, int64_t pad_lo, int64_t pad_hi, double* out, int64_t* num_frames_out,
                           int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!x || !out) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || batch > 65535) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: batch must be in [1, 65535]");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "as_windowed: batch_stride < length");
-  Framing fr;
-  if ((rc = make_framing(length, window_length, stride, pad_mode, pad_lo, pad_hi, &fr))) return rc;
-  if (num_frames_out) *num_frames_out = fr.M;
-  const size_t obytes = (size_t)batch * fr.M * fr.N * sizeof(double);
-  if (mem == NXSIG_DEVICE) return launch_as_windowed_f64(c, x, batch_stride, batch, fr, out);
-  Staged st(c);
-  const void* xd = nullptr; void* od = nullptr;
-  const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(double);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_as_windowed_f64(c, reinterpret_cast<const double*>(xd), batch_stride, batch, fr, reinterpret_cast<double*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
-  NXSIG_API_END
+  return as_windowed<double>(ctx, x, length, batch, batch_stride, window_length, stride, pad_mode, pad_lo, pad_hi, out, num_frames_out, mem);
 }
 
 int nxsig_overlap_and_add_f64(nxsig_ctx* ctx, const double* frames, int64_t num_frames, int32_t batch, int32_t frame_length,
                               int32_t overlap_length, int32_t components, double* out, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!frames || !out) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (components != 1 && components != 2) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: components must be 1 (f64) or 2 (c128)");
-  if (batch < 1 || batch > 65535 || num_frames < 1 || frame_length < 1)
-    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: batch, num_frames and frame_length must be >= 1");
-  if (overlap_length >= frame_length)
-    return set_error(NXSIG_ERR_INVALID_ARG, "overlap_length must be a number less than the window size " +
-                                                std::to_string(frame_length) + ", got: " + std::to_string(frame_length));
-  if (overlap_length < 0) return set_error(NXSIG_ERR_INVALID_ARG, "overlap_and_add: overlap_length must be >= 0");
-  const int hop = frame_length - overlap_length;
-  const int64_t out_len = num_frames * hop + overlap_length;
-  const size_t ibytes = (size_t)batch * num_frames * frame_length * components * sizeof(double);
-  const size_t obytes = (size_t)batch * out_len * components * sizeof(double);
-  if (mem == NXSIG_DEVICE) return launch_ola_f64(c, frames, num_frames, batch, frame_length, hop, components, nullptr, false, false, out);
-  Staged st(c);
-  const void* fd = nullptr; void* od = nullptr;
-  if ((rc = st.in(1, frames, ibytes, &fd))) return rc;
-  if ((rc = st.out_alloc(2, obytes, &od))) return rc;
-  if ((rc = launch_ola_f64(c, reinterpret_cast<const double*>(fd), num_frames, batch, frame_length, hop, components, nullptr, false, false,
-                           reinterpret_cast<double*>(od)))) return rc;
-  return st.out_copy(out, od, obytes);
-  NXSIG_API_END
-}
-
-static int fir_common_f64(nxsig_ctx* ctx, const double* x, int64_t length, int32_t batch, int64_t batch_stride, const double* h,
-                          int32_t num_taps, int64_t start, int64_t out_len, double* y, int32_t mem) {
-  NXSIG_API_BEGIN
-  NXSIG_CHECK_CTX(ctx)
-  DispatchScope dispatch_scope(c);
-  if (!x || !h || !y) return set_error(NXSIG_ERR_INVALID_ARG, "fir: null pointer argument");
-  int rc = check_mem(mem);
-  if (rc) return rc;
-  if (batch < 1 || batch > 65535 || length < 1 || num_taps < 1)
-    return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch, length and num_taps must be >= 1");
-  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch_stride < length");
-  if (start < 0 || out_len < 1 || start + out_len > length + num_taps - 1)
-    return set_error(NXSIG_ERR_INVALID_ARG, "fir: requested slice lies outside the full convolution");
-  FirLaunchD a;
-  a.L = length; a.batch = batch; a.batch_stride = batch_stride; a.h_host = h; a.taps = num_taps;
-  a.out_start = start; a.out_len = out_len;
-  const size_t ybytes = (size_t)batch * out_len * sizeof(double);
-  if (mem == NXSIG_DEVICE) {
-    a.x = x; a.y = y;
-    return launch_fir_f64(c, a);
-  }
-  Staged st(c);
-  const void* xd = nullptr; void* yd = nullptr;
-  const size_t xbytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(double);
-  if ((rc = st.in(1, x, xbytes, &xd))) return rc;
-  if ((rc = st.out_alloc(2, ybytes, &yd))) return rc;
-  a.x = reinterpret_cast<const double*>(xd); a.y = reinterpret_cast<double*>(yd);
-  if ((rc = launch_fir_f64(c, a))) return rc;
-  return st.out_copy(y, yd, ybytes);
-  NXSIG_API_END
+  return overlap_and_add<double>(ctx, frames, num_frames, batch, frame_length, overlap_length, components, out, mem);
 }
 
 int nxsig_fir_f64(nxsig_ctx* ctx, const double* x, int64_t length, int32_t batch, int64_t batch_stride, const double* h,
                   int32_t num_taps, int32_t mode, double* y, int32_t mem) {
-  if (length < 1 || num_taps < 1) return set_error(NXSIG_ERR_INVALID_ARG, "fir: batch, length and num_taps must be >= 1");
-  const int64_t full = length + num_taps - 1;
-  int64_t out_len, start;
-  switch (mode) {
-    case NXSIG_CONV_FULL: out_len = full; start = 0; break;
-    case NXSIG_CONV_SAME: out_len = length; start = (full - out_len) / 2; break;
-    case NXSIG_CONV_VALID:
-      out_len = (length >= num_taps ? length - num_taps : num_taps - length) + 1;
-      start = (full - out_len) / 2;
-      break;
-    default:
-      return set_error(NXSIG_ERR_INVALID_ARG, "expected mode to be one of [:full, :same, :valid]");
-  }
-  return fir_common_f64(ctx, x, length, batch, batch_stride, h, num_taps, start, out_len, y, mem);
+  return fir_mode<double>(ctx, x, length, batch, batch_stride, h, num_taps, mode, y, mem);
 }
 
 int nxsig_fir_slice_f64(nxsig_ctx* ctx, const double* x, int64_t length, int32_t batch, int64_t batch_stride, const double* h,
                         int32_t num_taps, int64_t out_start, int64_t out_len, double* y, int32_t mem) {
-  return fir_common_f64(ctx, x, length, batch, batch_stride, h, num_taps, out_start, out_len, y, mem);
+  return fir_common<double>(ctx, x, length, batch, batch_stride, h, num_taps, out_start, out_len, y, mem);
 }
 
 }  // extern "C"

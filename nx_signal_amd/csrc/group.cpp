@@ -197,13 +197,6 @@ struct Part {
 
 using namespace nxsig;
 
-#define NXSIG_API_BEGIN try {
-#define NXSIG_API_END                                                                   \
-  }                                                                                     \
-  catch (const std::bad_alloc&) { return set_error(NXSIG_ERR_OOM, "host out of memory"); } \
-  catch (const std::exception& e) { return set_error(NXSIG_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); } \
-  catch (...) { return set_error(NXSIG_ERR_INVALID_ARG, "internal error"); }
-
 extern "C" {
 
 /* ------------------------------------------------------------------------------------------------ shard plans (pure) */
@@ -1131,7 +1124,7 @@ int nxsig_stft_mel_sharded_f32(nxsig_group* grp, const float* const* x, int64_t 
     }
     if (rc) return fail(rc);
     void* gm = nullptr;
-    if ((rc = ctx_scratch(c, 5, 256, &gm))) return fail(rc);
+    if ((rc = ctx_scratch(c, kScratchReductionCells, 256, &gm))) return fail(rc);
     q.cell = reinterpret_cast<int*>(gm);
     if (mem == NXSIG_DEVICE) q.dout = nullptr;
   }

@@ -676,7 +676,7 @@ int launch_istft_f64(Ctx* c, const IstftLaunchD& s) {
   if (s.M == 0 || s.batch == 0) return NXSIG_OK;
   void* fr = nullptr;
   const int64_t rows = (int64_t)s.batch * s.M;
-  int rc = ctx_scratch(c, 27, (size_t)rows * s.N * sizeof(double2), &fr);
+  int rc = ctx_scratch(c, kScratchIstftF64Frames, (size_t)rows * s.N * sizeof(double2), &fr);
   if (rc) return rc;
   if ((rc = launch_fft_f64(c, s.z, false, rows, s.K, s.K, true, reinterpret_cast<double2*>(fr), s.window, s.scale_mul, s.has_scale != 0)))
     return rc;

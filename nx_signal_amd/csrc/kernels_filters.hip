@@ -505,7 +505,7 @@ int launch_wiener(Ctx* c, const void* x, bool f64, const int64_t* shape, int ran
   };
   if (!has_noise) {   // pass 1, the reduction, then the formula with the estimate
     void* sc = nullptr;
-    int rc = ctx_scratch(c, 28, (size_t)(blocks + 1) * sizeof(double), &sc);
+    int rc = ctx_scratch(c, kScratchWienerSums, (size_t)(blocks + 1) * sizeof(double), &sc);
     if (rc) return rc;
     double* noise_cell = static_cast<double*>(sc);
     WienerTail p = a;

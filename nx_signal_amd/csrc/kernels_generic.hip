@@ -791,14 +791,14 @@ __global__ __launch_bounds__(kThreads) void k_fir_poison(int* __restrict__ flags
 
 int fir_row_flags(Ctx* c, int32_t batch, int** out) {
   const size_t need = (size_t)batch * sizeof(int);
-  if (c->scratch_bytes[22] < need) {
+  if (c->scratch_bytes[kScratchFirRowFlags] < need) {
     void* p = nullptr;
     const size_t bytes = need < 4096 ? 4096 : need * 2;
-    int rc = ctx_scratch(c, 22, bytes, &p);
+    int rc = ctx_scratch(c, kScratchFirRowFlags, bytes, &p);
     if (rc) return rc;
     NXSIG_HIP_TRY(hipMemsetAsync(p, 0, bytes, c->stream));   // zero between calls: the poison pass clears what it consumes
   }
-  *out = reinterpret_cast<int*>(c->scratch[22]);
+  *out = reinterpret_cast<int*>(c->scratch[kScratchFirRowFlags]);
   return NXSIG_OK;
 }
 
@@ -1517,7 +1517,7 @@ int launch_stft_c64(Ctx* c, const StftLaunch& s) {
   const int n_use = s.fr.N < s.K ? s.fr.N : s.K;
   const int64_t rows = (int64_t)s.batch * s.fr.M;
   void* frames = nullptr;
-  if ((rc = ctx_scratch(c, 26, (size_t)rows * n_use * sizeof(float2), &frames))) return rc;
+  if ((rc = ctx_scratch(c, kScratchStftC64Frames, (size_t)rows * n_use * sizeof(float2), &frames))) return rc;
   const int64_t blocks = (s.fr.M * n_use + kThreads - 1) / kThreads;
   if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "stft: too many frames for one launch");
   dispatch_note("stft_c64.frames");
@@ -1534,7 +1534,7 @@ int launch_istft_generic(Ctx* c, const IstftLaunch& s) {
   if (s.M == 0 || s.batch == 0) return NXSIG_OK;
   void* frames = nullptr;
   const size_t fbytes = (size_t)s.batch * s.M * s.N * sizeof(float2);
-  int rc = ctx_scratch(c, 0, fbytes, &frames);
+  int rc = ctx_scratch(c, kScratchMultiStage, fbytes, &frames);
   if (rc) return rc;
   rc = launch_fft_rows(c, s.z, false, (int64_t)s.batch * s.M, s.K, s.K, true, s.window, s.scale_mul, s.has_scale != 0,
                        reinterpret_cast<float2*>(frames));
@@ -1701,16 +1701,16 @@ int launch_fir_generic(Ctx* c, const FirLaunch& s) {
 // non-empty list puts them back (no per-call memset).
 int istft_nf_list(Ctx* c, int64_t capacity, int** list) {
   if (capacity > 0x7fffffffLL) capacity = 0x7fffffffLL;
-  if (c->scratch_bytes[23] < (size_t)(capacity + 2) * 8) {
+  if (c->scratch_bytes[kScratchIstftNfList] < (size_t)(capacity + 2) * 8) {
     // (re)allocation: the header is written once, synchronously (it describes the buffer, not the call)
     const int64_t cap = capacity < 4096 ? 4096 : capacity * 2;
     void* p = nullptr;
-    int rc = ctx_scratch(c, 23, (size_t)(cap + 2) * 8, &p);
+    int rc = ctx_scratch(c, kScratchIstftNfList, (size_t)(cap + 2) * 8, &p);
     if (rc) return rc;
     const int hdr[4] = {0, 0, 0, (int)(cap > 0x7fffffffLL ? 0x7fffffffLL : cap)};
     NXSIG_HIP_TRY(hipMemcpy(p, hdr, sizeof(hdr), hipMemcpyHostToDevice));
   }
-  *list = reinterpret_cast<int*>(c->scratch[23]) + 2;
+  *list = reinterpret_cast<int*>(c->scratch[kScratchIstftNfList]) + 2;
   return NXSIG_OK;
 }
 
@@ -1883,7 +1883,7 @@ int launch_fftconvolve_c64(Ctx* c, const float2* a, int64_t n1, const float2* b,
   while (P < full) P <<= 1;
   if (full > ((int64_t)1 << 26)) return set_error(NXSIG_ERR_UNSUPPORTED, "fftconvolve (complex): n1 + n2 - 1 > 2^26 is not supported");
   void* sc = nullptr;
-  int rc = ctx_scratch(c, 0, (size_t)3 * P * sizeof(float2), &sc);
+  int rc = ctx_scratch(c, kScratchMultiStage, (size_t)3 * P * sizeof(float2), &sc);
   if (rc) return rc;
   float2* A = reinterpret_cast<float2*>(sc);
   float2* B = A + P;
@@ -1942,7 +1942,7 @@ int launch_stft_to_mel(Ctx* c, const float2* z, int64_t rows, int32_t K, int32_t
   rc = ctx_table(c, 0x3E1BA2Dull, band.data(), band.size() * sizeof(int2), &bd);
   if (rc) return rc;
   void* gm = nullptr;
-  rc = ctx_scratch(c, 5, 256, &gm);
+  rc = ctx_scratch(c, kScratchReductionCells, 256, &gm);
   if (rc) return rc;
   static const int init[2] = {(int)0x80000000, 0};  // {below every ordered-int value, no non-finite |z|^2 seen}
   NXSIG_HIP_TRY(hipMemcpyAsync(gm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
@@ -2125,7 +2125,7 @@ int launch_mag_from_spectrum(Ctx* c, const float2* z, int64_t rows, int32_t K, i
 // shared by the fused stft->mel kernel: running-maximum cell and the clamp pass
 int launch_mel_init(Ctx* c, int** gmax) {
   void* gm = nullptr;
-  int rc = ctx_scratch(c, 5, 256, &gm);
+  int rc = ctx_scratch(c, kScratchReductionCells, 256, &gm);
   if (rc) return rc;
   static const int init[2] = {(int)0x80000000, 0};
   NXSIG_HIP_TRY(hipMemcpyAsync(gm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));

@@ -228,8 +228,8 @@ static int fft_fourstep(Ctx* c, const void* in, bool in_is_real, int64_t rows, i
   if (rc) return rc;
   void *s1 = nullptr, *s2 = nullptr;
   const size_t bytes = (size_t)rows * K * sizeof(float2);
-  if ((rc = ctx_scratch(c, 6, bytes, &s1))) return rc;
-  if ((rc = ctx_scratch(c, 7, bytes, &s2))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFourStepA, bytes, &s1))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFourStepB, bytes, &s2))) return rc;
   float2* A = reinterpret_cast<float2*>(s1);
   float2* B = reinterpret_cast<float2*>(s2);
   // (a) [K1][K2] -> [K2][K1]   (zero-pad / truncate / real -> complex on the way in)
@@ -443,7 +443,7 @@ static int fft_fourstep_tiled(Ctx* c, const void* in, bool in_is_real, int64_t r
   if ((rc = ctx_twiddles(c, K1, &tw1))) return rc;
   if ((rc = ctx_twiddles(c, K2, &tw2))) return rc;
   void* s1 = nullptr;
-  if ((rc = ctx_scratch(c, 6, (size_t)rows * K * sizeof(float2), &s1))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFourStepA, (size_t)rows * K * sizeof(float2), &s1))) return rc;
   float2* Y = reinterpret_cast<float2*>(s1);
   auto tile_lg = [&](int n, int64_t nseq) {
     int l = 0;
@@ -545,8 +545,8 @@ static int fft_bluestein_big(Ctx* c, const void* in, bool in_is_real, int64_t ro
   void *s1 = nullptr, *s2 = nullptr;
   const size_t bytes = (size_t)rows * P * sizeof(float2);
   int rc;
-  if ((rc = ctx_scratch(c, 8, bytes, &s1))) return rc;
-  if ((rc = ctx_scratch(c, 9, bytes, &s2))) return rc;
+  if ((rc = ctx_scratch(c, kScratchBluesteinA, bytes, &s1))) return rc;
+  if ((rc = ctx_scratch(c, kScratchBluesteinB, bytes, &s2))) return rc;
   float2* A = reinterpret_cast<float2*>(s1);
   float2* B = reinterpret_cast<float2*>(s2);
   dispatch_note("fft.big.blue");
@@ -620,9 +620,9 @@ int launch_fft_nd(Ctx* c, const void* in, bool in_is_real, const int64_t* shape,
   void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
   int rc;
   const size_t bytes = (size_t)max_total * sizeof(float2);
-  if ((rc = ctx_scratch(c, 10, bytes, &p0))) return rc;
-  if ((rc = ctx_scratch(c, 11, bytes, &p1))) return rc;
-  if ((rc = ctx_scratch(c, 12, bytes, &p2))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFftNdA, bytes, &p0))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFftNdB, bytes, &p1))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFftNdC, bytes, &p2))) return rc;
   float2* bufs[3] = {reinterpret_cast<float2*>(p0), reinterpret_cast<float2*>(p1), reinterpret_cast<float2*>(p2)};
   const void* src = in;
   bool src_real = in_is_real;
@@ -742,9 +742,9 @@ int launch_fftconvolve_nd(Ctx* c, const void* a, bool a_is_real, const int64_t* 
   }
   void *pa = nullptr, *pb = nullptr, *pc = nullptr;
   int rc;
-  if ((rc = ctx_scratch(c, 13, (size_t)(n1 > no ? n1 : no) * sizeof(float2), &pa))) return rc;  // A, later the inverse transform's result
-  if ((rc = ctx_scratch(c, 14, (size_t)n2 * sizeof(float2), &pb))) return rc;
-  if ((rc = ctx_scratch(c, 15, (size_t)no * sizeof(float2), &pc))) return rc;
+  if ((rc = ctx_scratch(c, kScratchConvNdA, (size_t)(n1 > no ? n1 : no) * sizeof(float2), &pa))) return rc;  // A, later the inverse transform's result
+  if ((rc = ctx_scratch(c, kScratchConvNdB, (size_t)n2 * sizeof(float2), &pb))) return rc;
+  if ((rc = ctx_scratch(c, kScratchConvNdC, (size_t)no * sizeof(float2), &pc))) return rc;
   float2 *A = reinterpret_cast<float2*>(pa), *B = reinterpret_cast<float2*>(pb), *C = reinterpret_cast<float2*>(pc);
   if ((rc = launch_fft_nd(c, a, a_is_real, s1, rank, axes.data(), lens.data(), (int)axes.size(), false, A))) return rc;
   if ((rc = launch_fft_nd(c, b, b_is_real, s2, rank, axes.data(), lens.data(), (int)axes.size(), false, B))) return rc;
@@ -1050,7 +1050,7 @@ __global__ __launch_bounds__(kT) void k_frames_windowed(const float* __restrict_
 int launch_stft_big(Ctx* c, const StftLaunch& s) {
   if (s.fr.M == 0 || s.batch == 0) return NXSIG_OK;
   void* fr = nullptr;
-  int rc = ctx_scratch(c, 16, (size_t)s.batch * s.fr.M * s.fr.N * sizeof(float), &fr);
+  int rc = ctx_scratch(c, kScratchLongStftFrames, (size_t)s.batch * s.fr.M * s.fr.N * sizeof(float), &fr);
   if (rc) return rc;
   const int64_t per_row = s.fr.M * s.fr.N;
   if ((per_row + kT - 1) / kT > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "stft: too many frames for one launch");

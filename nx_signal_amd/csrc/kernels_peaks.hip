@@ -282,7 +282,7 @@ int mark_typed(Ctx* c, const void* xv, const Line& L, int family, uint64_t ntile
   const T *g = nullptr, *h = nullptr;
   if (family == kStrided && L.shifts > kBruteMax) {
     void* sc = nullptr;
-    int rc = ctx_scratch(c, 30, (size_t)L.total * 2 * sizeof(T), &sc);
+    int rc = ctx_scratch(c, kScratchPeakExtremes, (size_t)L.total * 2 * sizeof(T), &sc);
     if (rc) return rc;
     T* gw = static_cast<T*>(sc);
     T* hw = gw + L.total;
@@ -319,7 +319,7 @@ int mark_cmp(Ctx* c, const void* x, int comparator, const Line& L, int family, u
 
 size_t elem_size(int dtype) { return dtype == NXSIG_DT_F64 || dtype == NXSIG_DT_S64 || dtype == NXSIG_DT_U64 ? 8 : 4; }
 
-// passes 2 and 3 over the words and counts pass 1 left in slot 29
+// passes 2 and 3 over the words and counts pass 1 left in the kScratchPeakTiles slot
 int compact(Ctx* c, uint64_t total, const int64_t* shape, int rank, uint64_t ntiles, const uint64_t* words, const uint32_t* counts,
             uint64_t* offsets, int32_t* indices, uint32_t* valid) {
   hipLaunchKernelGGL(k_peaks_scan, dim3(1), dim3(1024), 0, c->stream, counts, ntiles, offsets, valid);
@@ -338,7 +338,7 @@ int compact(Ctx* c, uint64_t total, const int64_t* shape, int rank, uint64_t nti
 int workspace(Ctx* c, uint64_t total, uint64_t ntiles, uint64_t** words, uint32_t** counts, uint64_t** offsets) {
   const uint64_t nwords = (total + 63) / 64;
   void* sc = nullptr;
-  int rc = ctx_scratch(c, 29, (size_t)(ntiles * 8 + nwords * 8 + ntiles * 4), &sc);
+  int rc = ctx_scratch(c, kScratchPeakTiles, (size_t)(ntiles * 8 + nwords * 8 + ntiles * 4), &sc);
   if (rc) return rc;
   *offsets = static_cast<uint64_t*>(sc);
   *words = *offsets + ntiles;

@@ -1242,7 +1242,7 @@ static int launch_istft_wave_R(Ctx* c, const IstftLaunch& s, const float* window
     a.zeros = reinterpret_cast<const v2f*>(dz);
   }
   void* dummy = nullptr;
-  { int rc2 = ctx_scratch(c, 3, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
+  { int rc2 = ctx_scratch(c, kScratchWaveSink, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
   a.dummy = reinterpret_cast<v2f*>(dummy);
   const int64_t total_segs = a.segs_per_row * s.batch;
   // Two-frames-ahead prefetch (DEEP, round 3): 8 resident waves per CU with 16 KB of loads in flight each instead of 12 with 8 KB.
@@ -1348,7 +1348,7 @@ static int launch_istft_wave_quad(Ctx* c, const IstftLaunch& s, const float* win
   { int rc3 = istft_den_table(c, R, s.hop, window_host, &a.den); if (rc3) return rc3; }
   a.y = reinterpret_cast<v2f*>(s.y);
   void* dummy = nullptr;
-  { int rc2 = ctx_scratch(c, 3, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
+  { int rc2 = ctx_scratch(c, kScratchWaveSink, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
   a.dummy = reinterpret_cast<v2f*>(dummy);
   const int64_t units_per_row = (a.segs_per_row + J - 1) / J;
   const int64_t total_units = units_per_row * s.batch;
@@ -1395,7 +1395,7 @@ static int launch_istft_wave_4k(Ctx* c, const IstftLaunch& s, const float* windo
   { int rc3 = istft_den_table(c, R, s.hop, window_host, &a.den); if (rc3) return rc3; }
   a.y = reinterpret_cast<v2f*>(s.y);
   void* dummy = nullptr;
-  { int rc2 = ctx_scratch(c, 3, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
+  { int rc2 = ctx_scratch(c, kScratchWaveSink, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
   a.dummy = reinterpret_cast<v2f*>(dummy);
   {
     const void* d4 = nullptr;

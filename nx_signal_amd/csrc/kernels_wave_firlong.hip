@@ -377,7 +377,7 @@ int launch_fir_dline(Ctx* c, const FirLaunch& s, bool* handled) {
   if (seg > nblk_total) seg = nblk_total;
   void* scratch = nullptr;
   const size_t zbytes = (size_t)s.batch * (size_t)(seg + P - 1) * 8192, wbytes = fused ? 0 : (size_t)s.batch * (size_t)seg * 8192;
-  if ((rc = ctx_scratch(c, 21, zbytes + wbytes, &scratch))) return rc;
+  if ((rc = ctx_scratch(c, kScratchFirLong, zbytes + wbytes, &scratch))) return rc;
   a.Z = reinterpret_cast<v2f*>(scratch);
   a.Wt = reinterpret_cast<v2f*>(static_cast<char*>(scratch) + zbytes);
   constexpr int W = 4;

@@ -193,7 +193,7 @@ static int launch_istft_mask_R(Ctx* c, const IstftLaunch& s, const float* window
     a.zeros = reinterpret_cast<const v2f*>(dz);
   }
   void* dummy = nullptr;
-  { int rc = ctx_scratch(c, 3, (size_t)8192 * sizeof(float2), &dummy); if (rc) return rc; }
+  { int rc = ctx_scratch(c, kScratchWaveSink, (size_t)8192 * sizeof(float2), &dummy); if (rc) return rc; }
   a.dummy = reinterpret_cast<v2f*>(dummy);
   const int64_t total_segs = a.segs_per_row * s.batch;
   const int waves_per_cu = tune(c, kT_ISTFT_RUNS_PER_CU, 8);   // two waves per SIMD

@@ -186,7 +186,7 @@ static int launch_istft_packed_R(Ctx* c, const IstftLaunch& s, const float* wind
   { int rc = istft_den_table(c, R, s.hop, window_host, &a.den); if (rc) return rc; }
   a.y = reinterpret_cast<float*>(s.y);
   void* dummy = nullptr;
-  { int rc = ctx_scratch(c, 3, (size_t)8192 * sizeof(float2), &dummy); if (rc) return rc; }
+  { int rc = ctx_scratch(c, kScratchWaveSink, (size_t)8192 * sizeof(float2), &dummy); if (rc) return rc; }
   a.dummy = reinterpret_cast<float*>(dummy);
   {
     const void* dh = nullptr;

@@ -5,8 +5,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <exception>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -32,6 +34,14 @@ const char* dispatch_cstr();
       return ::nxsig::set_error(_e == hipErrorOutOfMemory ? NXSIG_ERR_OOM : NXSIG_ERR_HIP,           \
                                 std::string(#expr) + ": " + hipGetErrorString(_e));                  \
   } while (0)
+
+// ---- every extern "C" entry point runs between these two: no C++ exception leaves the library
+#define NXSIG_API_BEGIN try {
+#define NXSIG_API_END                                                                   \
+  }                                                                                     \
+  catch (const std::bad_alloc&) { return ::nxsig::set_error(NXSIG_ERR_OOM, "host out of memory"); } \
+  catch (const std::exception& e) { return ::nxsig::set_error(NXSIG_ERR_INVALID_ARG, std::string("internal error: ") + e.what()); } \
+  catch (...) { return ::nxsig::set_error(NXSIG_ERR_INVALID_ARG, "internal error"); }
 
 // ---- Nx.fft / Nx.ifft clean-up (SURVEY App. A rule 7; call sites lib/nx_signal.ex:102, :609, convolution.ex:282): the
 // BinaryBackend zeroes every component of a transform's result whose magnitude is <= eps (1e-10, the default of the :eps
@@ -96,6 +106,43 @@ bool tuning_value_ok(int key, long value, long* lo, long* hi);   // the admissib
 int tuning_index(const char* name);    // "NXSIG_FOO" or "FOO" -> TuneKey, -1 when there is no such switch
 const char* tuning_name(int key);      // "NXSIG_FOO"
 
+// ---- scratch slots of a context (Ctx::scratch): every user of ctx_scratch owns the slot it names here.  Two users of one slot that are
+// live in the same call overwrite each other silently, so a new temporary takes a new enumerator, never a number.
+enum ScratchSlot : int {
+  kScratchMultiStage = 0,        // generic istft's frames tensor; the three transforms of nxsig_fftconvolve_c64 (kernels_generic.hip)
+  kScratchStageIn = 1,           // host staging: the first input of a NXSIG_HOST call (HostIo, api.cpp)
+  kScratchStageOut = 2,          // host staging: the result of a NXSIG_HOST call; nxsig_fftconvolve_c64's second input (HostIo, api.cpp)
+  kScratchWaveSink = 3,          // dummy sink the wave kernels' unused output pointers aim at (kernels_wave*.hip, wave_stft.hpp, wave_rab.hpp)
+  kScratchFusedSpectrum = 4,     // spectrum of the two-step fall-back of the fused sinks; staged result of nxsig_fftconvolve_c64 (api.cpp)
+  kScratchReductionCells = 5,    // running maximum + non-finite flag of the log-mel / dBFS paths (kernels_generic.hip, group.cpp)
+  kScratchFourStepA = 6,         // four-step rows: first buffer, also the tiled form's only one (kernels_nd.hip)
+  kScratchFourStepB = 7,         // four-step rows: second buffer (kernels_nd.hip)
+  kScratchBluesteinA = 8,        // Bluestein rows: chirped input / product (kernels_nd.hip)
+  kScratchBluesteinB = 9,        // Bluestein rows: its transform (kernels_nd.hip)
+  kScratchFftNdA = 10,           // fft_nd ping-pong buffers (kernels_nd.hip)
+  kScratchFftNdB = 11,
+  kScratchFftNdC = 12,
+  kScratchConvNdA = 13,          // n-D fftconvolve: padded A, later the inverse transform's result (kernels_nd.hip)
+  kScratchConvNdB = 14,          // n-D fftconvolve: padded B (kernels_nd.hip)
+  kScratchConvNdC = 15,          // n-D fftconvolve: the product (kernels_nd.hip)
+  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip)
+  kScratchNdStageA = 17,         // host staging of the n-D / filter / peak / waveform calls: first input; the mask of the masked istft (api.cpp)
+  kScratchNdStageB = 18,         // the same: second input; peak finding's `valid` cell (api.cpp)
+  kScratchNdStageOut = 19,       // the same: results, several packed at a 256-byte stride (api.cpp)
+  kScratchIstftProduct = 20,     // z * H / z * mask of the filtered and masked istft's two-step fall-back (launch_istft, api.cpp)
+  kScratchFirLong = 21,          // long FIR: full convolution row, partition outputs, delay-line spectra (api.cpp, kernels_wave_firlong.hip)
+  kScratchFirRowFlags = 22,      // per-row non-finite flags of the FIR kernels (fir_row_flags, kernels_generic.hip)
+  kScratchIstftNfList = 23,      // units with a non-finite bin reported by the multi-frame inverse kernels (istft_nf_list, kernels_generic.hip)
+  kScratchPackedSpectrum = 24,   // packed istft fall-back: the Hermitian rows written out (launch_istft, api.cpp)
+  kScratchPackedSignal = 25,     // packed istft fall-back: the complex signal before its real part is kept (launch_istft, api.cpp)
+  kScratchStftC64Frames = 26,    // windowed frames of the generic complex-input stft (launch_stft_c64, kernels_generic.hip)
+  kScratchIstftF64Frames = 27,   // frames of the f64 istft (kernels_f64.hip)
+  kScratchWienerSums = 28,       // wiener's noise cell + per-workgroup partial sums (kernels_filters.hip)
+  kScratchPeakTiles = 29,        // peak finding: mask words + tile counts / offsets (kernels_peaks.hip)
+  kScratchPeakExtremes = 30,     // peak finding over a strided axis: window extremes (kernels_peaks.hip)
+  kScratchSlots = 32             // (31 is free)
+};
+
 // ---- device tables cached per context ----
 struct DeviceTable {
   void* ptr = nullptr;
@@ -120,14 +167,10 @@ struct Ctx {
   std::map<uint64_t, DeviceTable> tables;
   // f64 tier (kernels_f64.hip): device pointers of its twiddle / chirp tables by (kind << 32 | length); the storage belongs to `tables`
   std::map<int64_t, const void*> f64_tables;
-  // scratch buffer reused by multi-stage paths (generic istft, host staging)
-  // slots: 0 multi-stage temporaries, 1/2 host staging in/out, 3 wave-kernel dummy sink, 4 fused-path spectrum, 5 reduction cells,
-  // 6-9 four-step / Bluestein rows, 10-12 fft_nd ping-pong, 13-15 n-D fftconvolve, 16 long-transform stft frames, 17-19 host staging of n-D calls
-  // 20 istft filter fallback, 21 long FIR, 22 FIR row flags, 23 istft non-finite unit list, 24/25 packed istft fallback,
-  // 27 frames of the f64 istft, 28 wiener noise cell + per-workgroup partial sums, 29 peak-finding mask words + tile counts / offsets,
-  // 30 peaks.strided window extremes
-  void* scratch[32] = {};
-  size_t scratch_bytes[32] = {};
+  // device scratch buffers reused from call to call, one per ScratchSlot (the enum names every slot and its owner); grown on demand
+  // by ctx_scratch, freed with the context
+  void* scratch[kScratchSlots] = {};
+  size_t scratch_bytes[kScratchSlots] = {};
   // per-K tables of the tuned wave kernels (pass-B / pass-C twiddles), built once
   struct WaveTables { const void* twB = nullptr; const void* twC = nullptr; const void* twI = nullptr;
                       const void* twBi = nullptr; const void* twCi = nullptr;    // ...i = conjugated (inverse transform)
@@ -196,7 +239,7 @@ bool mel_deferred(const Ctx* c);
 
 int ctx_twiddles(Ctx* c, int K, const float2** out);
 int ctx_table(Ctx* c, uint64_t tag, const void* host, size_t bytes, const void** out);
-int ctx_scratch(Ctx* c, int slot, size_t bytes, void** out);
+int ctx_scratch(Ctx* c, ScratchSlot slot, size_t bytes, void** out);
 // device copies of a host window: raw f32[N] and the K-point table (Nx.fft(length: K) pads / truncates rows)
 int ctx_window(Ctx* c, const float* window_host, int N, int K, const float** dev, const float** devK);
 uint64_t fnv1a(uint64_t seed, const void* data, size_t bytes);

@@ -1460,7 +1460,7 @@ static int launch_wave(Ctx* c, const StftLaunch& s, const MelLaunch* mel = nullp
   a.twR = reinterpret_cast<const v2f*>(MODE == kModeQuad ? wt.twQ[J == 2 ? 0 : (J == 4 ? 1 : 2)] : wt.twI);
   a.wtab = s.window_padK;
   void* dummy = nullptr;
-  { int rc2 = ctx_scratch(c, 3, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
+  { int rc2 = ctx_scratch(c, kScratchWaveSink, (size_t)8192 * sizeof(float2), &dummy); if (rc2) return rc2; }
   a.dummy = reinterpret_cast<v2f*>(dummy);
 
   size_t lds = (size_t)KOUT * 4 + 256 * 8 + (size_t)R3 * 256 * 8 +

@@ -1,11 +1,14 @@
 """Interleaved A/B of the SAME launch through TWO builds of libnxsig.so in one process (tools only): both libraries are loaded side by
 side (separate contexts and streams on the same GPU), rounds alternate, so box-to-box and warm-up drift cancel and a code change is
 separated from the box it happened to be measured on.
-    usage: python tools/ab_libs.py tools/_ab/libnxsig_base.so nx_signal_amd/libnxsig.so [stft[N]|istft[N]|fir] [rounds]   (stft2048 = config 4's shard, fir = config 5's)"""
+    usage: python tools/ab_libs.py tools/_ab/libnxsig_base.so nx_signal_amd/libnxsig.so [stft[N]|istft[N]|fir] [rounds]   (stft2048 = config 4's shard, fir = config 5's)
+`latency` instead of a case: the three small device-resident calls of tools/bench_latency.py (1 s mono 48 kHz), host time to issue one call in
+microseconds per round — where the entry points' own overhead shows."""
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -117,7 +120,49 @@ def make(side):
     return (lambda: lib.nxsig_fir_f32(ctx, x, L, B, L, h.ctypes.data_as(C.c_void_p), 257, 1, y, 1)), B * L * 8
 
 
+def latency_calls(side):
+    lib, ctx = side.lib, side.ctx
+    N, hop, L = 1024, 256, SR
+    M = (L - N) // hop + 1
+    x = side.alloc(L * 4); z = side.alloc(M * N * 8); y = side.alloc((M * hop + N - hop) * 8); f = side.alloc(L * 4)
+    side.upload_rows(x, 1, L, rng.standard_normal(L, dtype=np.float32))
+    w = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / N)).astype(np.float32)
+    h = np.zeros(257, np.float32)
+    assert lib.nxsig_firwin_f32(257, (C.c_double * 1)(4000.0), 1, 4, 0.0, 1, 1, float(SR), h.ctypes.data_as(C.c_void_p)) == 0
+    p = _lib.StftParams(N, hop, N, 0, 0, 0, 0, 0, float(SR))
+    side.keep = (w, h, p)
+    wp, hp = w.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p)
+    return {"stft": lambda: lib.nxsig_stft_f32(ctx, x, L, 1, L, wp, C.byref(p), z, None, 1),
+            "istft": lambda: lib.nxsig_istft_c64(ctx, z, M, 1, wp, C.byref(p), y, 1),
+            "fir": lambda: lib.nxsig_fir_f32(ctx, x, L, 1, L, hp, 257, 1, f, 1)}
+
+
+def latency(sides):
+    calls = [latency_calls(s) for s in sides]
+    res = [{k: [] for k in c} for c in calls]
+    for r in range(rounds):
+        for i, s in enumerate(sides):
+            for name, fn in calls[i].items():
+                for _ in range(20):
+                    assert fn() == 0, s.lib.nxsig_last_error()
+                s.lib.nxsig_sync(s.ctx)
+                n = 2000
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    fn()
+                res[i][name].append((time.perf_counter() - t0) / n * 1e6)
+                s.lib.nxsig_sync(s.ctx)
+    for pth, rr in zip(paths, res):
+        for name, v in rr.items():
+            v2 = sorted(v[1:]) if len(v) > 2 else sorted(v)
+            print(json.dumps({"lib": pth, "case": "latency." + name, "host_issue_us_rounds": [round(a, 2) for a in v],
+                              "median_after_first": round(v2[len(v2) // 2], 2), "min_after_first": round(v2[0], 2), "max_after_first": round(v2[-1], 2)}))
+
+
 sides = [Side(p) for p in paths]
+if which == "latency":
+    latency(sides)
+    sys.exit(0)
 jobs = [make(s) for s in sides]
 res = [[] for _ in sides]
 for r in range(rounds):

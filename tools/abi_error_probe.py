@@ -1,0 +1,371 @@
+"""Error table of the C ABI: every compute entry point of include/nxsig.h is called with small valid arguments and then with ONE
+argument broken at a time; the return code, nxsig_last_error() and what landed in *num_frames_out are recorded per case.
+
+    python tools/abi_error_probe.py [--lib PATH] [--real] [--write tests/golden/abi_error_table.json]
+
+Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
+that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
+before anything is launched (the probe refuses a broken case that returns 0), and the valid row of each entry point runs once with
+NXSIG_HOST and once with NXSIG_DEVICE, the two results compared bit for bit.  The golden file holds both tables; regenerate it from
+the build whose behaviour is the reference (tests/test_abi_errors_host.py and tests/test_gpu_abi_errors.py compare against it)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+from nx_signal_amd import _lib  # noqa: E402  (signature table + structs only)
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_error_table.json")
+NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
+NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
+
+_rng = np.random.Generator(np.random.PCG64(7))
+
+
+def _f32(*shape):
+    return _rng.standard_normal(shape).astype(np.float32)
+
+
+def _c64(*shape):
+    return (_rng.standard_normal(shape) + 1j * _rng.standard_normal(shape)).astype(np.complex64)
+
+
+def _i64(*v):
+    return np.array(v, dtype=np.int64)
+
+
+def bind(path):
+    lib = C.CDLL(os.path.abspath(path))
+    for name, (res, args) in _lib.SIGNATURES.items():
+        try:
+            f = getattr(lib, name)
+        except AttributeError:
+            continue
+        f.restype, f.argtypes = res, args
+    return lib
+
+
+# ---- the table.  An entry: (symbol, [(arg, kind, value)], [(label, {arg: broken value}[, NULL_ONLY])]).  Kinds:
+#   in / out    tensor operand: a host array with NXSIG_HOST, a device copy with NXSIG_DEVICE        (+ "?": may be NULL)
+#   host / hout array that is always read / written on the host (window, taps, shapes, noise_used)   (+ "?": may be NULL)
+#   p           nxsig_stft_params as a dict; a case breaks one field as "p.<field>"
+#   nf          int64_t* num_frames_out          v  scalar          mem  NXSIG_HOST / NXSIG_DEVICE
+# Every required pointer gets a "null <arg>" case and every entry a "mem=7" case on top of the listed ones.
+N, HOP, K, L, B, M = 8, 4, 8, 20, 2, 4
+WIN = (0.54 - 0.46 * np.cos(2 * np.pi * np.arange(N) / N)).astype(np.float32)   # no zero sample: the OLA normaliser stays finite
+PARAMS = dict(frame_length=N, hop=HOP, fft_length=K, pad_mode=_lib.PAD_VALID, pad_lo=0, pad_hi=0, scaling=_lib.SCALE_NONE, reserved=0,
+              sampling_rate=48000.0)
+
+
+def _stft_cases(bounded, min_fft, odd_ok=True):
+    return [("batch=0", {"batch": 0}), ("batch=65536", {"batch": 65536}) + (() if bounded else (NULL_ONLY,)),
+            ("batch_stride=length-1", {"batch_stride": L - 1}), ("fft_length=0", {"p.fft_length": 0}),
+            ("fft_length=1", {"p.fft_length": 1}) + (() if min_fft >= 2 else (NULL_ONLY,)),
+            ("fft_length=7", {"p.fft_length": 7}) + ((NULL_ONLY,) if odd_ok else ()),
+            ("scaling=9", {"p.scaling": 9}), ("hop=0", {"p.hop": 0}), ("frame_length>length", {"p.frame_length": 32}),
+            ("frame_length=0", {"p.frame_length": 0}), ("pad_mode=9", {"p.pad_mode": 9}), ("length=0", {"length": 0})]
+
+
+def _stft(name, x, out, bounded, min_fft, odd_ok=True, extra=(), more=(), window=WIN, wflag=()):
+    args = [("x", "in", x), ("length", "v", L), ("batch", "v", B), ("batch_stride", "v", L), ("window", "host", window), *wflag,
+            ("p", "p", PARAMS), *extra, ("out", "out", out), ("nf", "nf", None), ("mem", "mem", None)]
+    return (name, args, _stft_cases(bounded, min_fft, odd_ok) + list(more))
+
+
+_ISTFT_CASES = [("batch=0", {"batch": 0}), ("num_frames=0", {"num_frames": 0}), ("scaling=9", {"p.scaling": 9}),
+                ("frame_length=0", {"p.frame_length": 0}), ("hop=0", {"p.hop": 0}), ("hop>frame_length", {"p.hop": 9}),
+                ("fft_length!=frame_length", {"p.fft_length": 16})]
+
+
+def _istft(name, z, y, bounded, extra=(), more=(), window=WIN, wflag=()):
+    args = [("z", "in", z), ("num_frames", "v", M), ("batch", "v", B), ("window", "host", window), *wflag, ("p", "p", PARAMS), *extra,
+            ("y", "out", y), ("mem", "mem", None)]
+    return (name, args, _ISTFT_CASES + [("batch=65536", {"batch": 65536}) + (() if bounded else (NULL_ONLY,))] + list(more))
+
+
+_MASK_CASES = [("mask_kind=9", {"mask_kind": 9}), ("z_rows=0", {"z_rows": 0}), ("z_rows=2 mask_rows=3", {"mask_rows": 3}),
+               ("z_rows=65536", {"z_rows": 65536, "mask_rows": 1})]
+_OLA_CASES = [("components=3", {"components": 3}), ("batch=0", {"batch": 0}), ("batch=65536", {"batch": 65536}),
+              ("num_frames=0", {"num_frames": 0}), ("frame_length=0", {"frame_length": 0}), ("overlap=frame_length", {"overlap_length": N}),
+              ("overlap=-1", {"overlap_length": -1})]
+_FRAMING_CASES = [("batch=0", {"batch": 0}), ("batch=65536", {"batch": 65536}), ("batch_stride=length-1", {"batch_stride": L - 1}),
+                  ("window_length=0", {"window_length": 0}), ("stride=0", {"stride": 0}), ("window_length>length", {"window_length": 32}),
+                  ("pad_mode=9", {"pad_mode": 9}), ("length=0", {"length": 0})]
+
+
+def _framing(name, dt):
+    return (name, [("x", "in", _f32(B, L).astype(dt)), ("length", "v", L), ("batch", "v", B), ("batch_stride", "v", L), ("window_length", "v", N),
+                   ("stride", "v", HOP), ("pad_mode", "v", _lib.PAD_VALID), ("pad_lo", "v", 0), ("pad_hi", "v", 0),
+                   ("out", "out", np.zeros((B, M, N), dt)), ("nf", "nf", None), ("mem", "mem", None)], _FRAMING_CASES)
+
+
+def _ola(name, dt):
+    return (name, [("frames", "in", _f32(B, M, N).astype(dt)), ("num_frames", "v", M), ("batch", "v", B), ("frame_length", "v", N),
+                   ("overlap_length", "v", N - HOP), ("components", "v", 1), ("out", "out", np.zeros((B, M * HOP + N - HOP), dt)),
+                   ("mem", "mem", None)], _OLA_CASES)
+
+
+FL, TAPS = 16, 3
+
+
+def _fir(name, dt, bounded, slice_):
+    tail = [("out_start", "v", 1), ("out_len", "v", FL)] if slice_ else [("mode", "v", _lib.CONV_SAME)]
+    cases = [("batch=0", {"batch": 0}), ("batch=65536", {"batch": 65536}) + (() if bounded else (NULL_ONLY,)),
+             ("batch_stride=length-1", {"batch_stride": FL - 1}), ("length=0", {"length": 0}), ("num_taps=0", {"num_taps": 0})]
+    cases += [("out_start=-1", {"out_start": -1}), ("out_len=0", {"out_len": 0}), ("slice past the end", {"out_start": 3})] if slice_ else [("mode=9", {"mode": 9})]
+    return (name, [("x", "in", _f32(B, FL).astype(dt)), ("length", "v", FL), ("batch", "v", B), ("batch_stride", "v", FL),
+                   ("h", "host", _f32(TAPS).astype(dt)), ("num_taps", "v", TAPS), *tail, ("y", "out", np.zeros((B, FL), dt)), ("mem", "mem", None)], cases)
+
+
+def _fft(name, dt, cdt):
+    return (name, [("in", "in", _f32(2, 8).astype(dt)), ("in_is_real", "v", 1), ("rows", "v", 2), ("n_in", "v", 8), ("fft_length", "v", 8),
+                   ("inverse", "v", 0), ("out", "out", np.zeros((2, 8), cdt)), ("mem", "mem", None)],
+            [("rows=0", {"rows": 0}), ("n_in=0", {"n_in": 0}), ("fft_length=0", {"fft_length": 0})])
+
+
+def _conv_nd(name):
+    return (name, [("a", "in", _f32(4, 4)), ("a_is_real", "v", 1), ("a_shape", "host", _i64(4, 4)), ("b", "in", _f32(2, 4)), ("b_is_real", "v", 1),   # (2, 2) of it
+                   ("b_shape", "host", _i64(2, 2)), ("rank", "v", 2), ("mode", "v", _lib.CONV_FULL), ("out", "out", np.zeros((5, 5), np.float32)),
+                   ("out_shape", "hout?", _i64(0, 0)), ("mem", "mem", None)],
+            [("rank=0", {"rank": 0}), ("rank=9", {"rank": 9}), ("empty dimension", {"a_shape": _i64(4, 0)}), ("mode=9", {"mode": 9}),
+             ("valid mode, neither contains the other", {"mode": _lib.CONV_VALID, "b_shape": _i64(1, 5)})])
+
+
+def _wave(name, mid, cases, out=None):
+    return (name, [("t", "in", np.linspace(0, 1, 8, dtype=np.float32)), ("is_f64", "v", 0), ("n", "v", 8), *mid,
+                   ("out", "out", np.zeros(8, np.float32) if out is None else out), ("mem", "mem", None)], [("n=-1", {"n": -1})] + cases)
+
+
+_PEAK_SHAPE_CASES = [("rank=0", {"rank": 0}), ("rank=9", {"rank": 9}), ("empty dimension", {"shape": _i64(0)}),
+                     ("dimension 2^31", {"shape": _i64(1 << 31)}), ("2^32 elements", {"shape": _i64(1 << 30, 4), "rank": 2})]
+_X8 = np.array([0, 2, 1, 3, 0, 5, 4, 4], np.float32)
+
+ENTRIES = [
+    _stft("nxsig_stft_f32", _f32(B, L), np.zeros((B, M, K), np.complex64), False, 1),
+    _stft("nxsig_stft_c64", _c64(B, L), np.zeros((B, M, K), np.complex64), False, 1),
+    _stft("nxsig_stft_onesided_f32", _f32(B, L), np.zeros((B, M, K // 2), np.complex64), True, 2),
+    _stft("nxsig_stft_packed_f32", _f32(B, L), np.zeros((B, M, K // 2), np.complex64), True, 2, odd_ok=False),
+    _stft("nxsig_stft_magnitude_f32", _f32(B, L), np.zeros((B, M, K // 2), np.float32), True, 2, extra=[("kind", "v", _lib.MAG_POWER)],
+          more=[("kind=9", {"kind": 9})]),
+    _stft("nxsig_stft_mel_f32", _f32(B, L), np.zeros((B, M, 4), np.float32), True, 2,
+          extra=[("mel_bins", "v", 4), ("filters", "host", np.abs(_f32(K, 4)))], more=[("mel_bins=0", {"mel_bins": 0})]),
+    _istft("nxsig_istft_c64", _c64(B, M, K), np.zeros((B, M * HOP + N - HOP), np.complex64), False),
+    _istft("nxsig_istft_packed_f32", _c64(B, M, K // 2), np.zeros((B, M * HOP + N - HOP), np.float32), True,
+           more=[("fft_length=7", {"p.fft_length": 7, "p.frame_length": 7})]),
+    _istft("nxsig_istft_filtered_c64", _c64(B, M, K), np.zeros((B, M * HOP + N - HOP), np.complex64), True, extra=[("h", "host", _c64(K))]),
+    ("nxsig_istft_masked_c64",
+     [("z", "in", _c64(B, M, K)), ("z_rows", "v", B), ("num_frames", "v", M), ("window", "host", WIN), ("p", "p", PARAMS),
+      ("mask", "in", np.abs(_f32(B, M, K))), ("mask_kind", "v", 0), ("mask_rows", "v", B), ("y", "out", np.zeros((B, M * HOP + N - HOP), np.complex64)),
+      ("mem", "mem", None)],
+     _MASK_CASES + [("one-sided mask, fft_length=7", {"mask_kind": 1, "p.fft_length": 7, "p.frame_length": 7})] +
+     [c for c in _ISTFT_CASES if c[0] != "batch=0"]),
+    ("nxsig_spectrum_mask_c64",
+     [("z", "in", _c64(B, M, K)), ("z_rows", "v", B), ("mask", "in", np.abs(_f32(B, M, K))), ("mask_kind", "v", 0), ("mask_rows", "v", B),
+      ("num_frames", "v", M), ("fft_length", "v", K), ("out", "out", np.zeros((B, M, K), np.complex64)), ("mem", "mem", None)],
+     _MASK_CASES + [("one-sided mask, fft_length=7", {"mask_kind": 1, "fft_length": 7}), ("num_frames=0", {"num_frames": 0}),
+                    ("fft_length=0", {"fft_length": 0})]),
+    _framing("nxsig_as_windowed_f32", np.float32),
+    _ola("nxsig_overlap_and_add", np.float32),
+    _fft("nxsig_fft", np.float32, np.complex64),
+    _fir("nxsig_fir_f32", np.float32, False, False),
+    _fir("nxsig_fir_slice_f32", np.float32, False, True),
+    ("nxsig_fftconvolve_c64",
+     [("a", "in", _c64(8)), ("n1", "v", 8), ("b", "in", _c64(3)), ("n2", "v", 3), ("mode", "v", _lib.CONV_FULL), ("out", "out", np.zeros(10, np.complex64)),
+      ("mem", "mem", None)], [("n1=0", {"n1": 0}), ("n2=0", {"n2": 0}), ("mode=9", {"mode": 9})]),
+    ("nxsig_stft_to_mel",
+     [("z", "in", _c64(M, K)), ("rows", "v", M), ("fft_length", "v", K), ("mel_bins", "v", 4), ("filters", "host", np.abs(_f32(K, 4))),
+      ("out", "out", np.zeros((M, 4), np.float32)), ("mem", "mem", None)],
+     [("rows=0", {"rows": 0}), ("fft_length=1", {"fft_length": 1}), ("mel_bins=0", {"mel_bins": 0}), ("fft_length=16386", {"fft_length": 16386})]),
+    ("nxsig_spectrum_mul_c64",
+     [("z", "in", _c64(M, K)), ("rows", "v", M), ("fft_length", "v", K), ("h", "host", _c64(K)), ("out", "out", np.zeros((M, K), np.complex64)),
+      ("mem", "mem", None)], [("rows=-1", {"rows": -1}), ("fft_length=0", {"fft_length": 0})]),
+    ("nxsig_fft_nd",
+     [("in", "in", _f32(4, 4)), ("in_is_real", "v", 1), ("shape", "host", _i64(4, 4)), ("rank", "v", 2), ("axes", "host", np.array([0, 1], np.int32)),
+      ("lengths", "host", _i64(4, 4)), ("n_axes", "v", 2), ("inverse", "v", 0), ("out", "out", np.zeros((4, 4), np.complex64)), ("mem", "mem", None)],
+     [("rank=0", {"rank": 0}), ("rank=9", {"rank": 9}), ("n_axes=17", {"n_axes": 17}), ("empty dimension", {"shape": _i64(4, 0)}),
+      ("axis=5", {"axes": np.array([0, 5], np.int32)}), ("lengths=0", {"lengths": _i64(4, 0)})]),
+    _conv_nd("nxsig_fftconvolve_nd"),
+    _conv_nd("nxsig_convolve_direct"),
+    ("nxsig_median_filter",
+     [("x", "in", _f32(4, 4)), ("is_f64", "v", 0), ("shape", "host", _i64(4, 4)), ("rank", "v", 2), ("kernel_shape", "host", _i64(3, 3)),
+      ("out", "out", np.zeros((4, 4), np.float32)), ("mem", "mem", None)],
+     [("rank=0", {"rank": 0}), ("rank=9", {"rank": 9}), ("empty dimension", {"shape": _i64(4, 0)}), ("kernel_shape=0", {"kernel_shape": _i64(3, 0)}),
+      ("kernel_shape>dimension", {"kernel_shape": _i64(3, 5)})]),
+    ("nxsig_wiener",
+     [("x", "in", _f32(4, 4)), ("is_f64", "v", 0), ("shape", "host", _i64(4, 4)), ("rank", "v", 2), ("kernel_size", "host", _i64(3, 3)),
+      ("has_noise", "v", 0), ("noise", "v", 0.0), ("out", "out", np.zeros((4, 4), np.float32)), ("noise_used", "hout?", np.zeros(1, np.float64)),
+      ("mem", "mem", None)],
+     [("rank=0", {"rank": 0}), ("rank=9", {"rank": 9}), ("empty dimension", {"shape": _i64(4, 0)}), ("kernel_size=0", {"kernel_size": _i64(3, 0)})]),
+    ("nxsig_argrelextrema",
+     [("x", "in", _X8), ("dtype", "v", _lib.DT_F32), ("shape", "host", _i64(8)), ("rank", "v", 1), ("axis", "v", 0), ("shifts", "v", 1),
+      ("comparator", "v", _lib.CMP_GREATER), ("indices", "out", np.zeros((8, 1), np.int32)), ("valid", "out", np.zeros(1, np.uint32)), ("mem", "mem", None)],
+     _PEAK_SHAPE_CASES + [("axis=1", {"axis": 1}), ("axis=-1", {"axis": -1}), ("dtype=9", {"dtype": 9}), ("comparator=9", {"comparator": 9})]),
+    ("nxsig_nonzero",
+     [("mask", "in", (_X8 > 2).astype(np.uint8)), ("shape", "host", _i64(8)), ("rank", "v", 1), ("indices", "out", np.zeros((8, 1), np.int32)),
+      ("valid", "out", np.zeros(1, np.uint32)), ("mem", "mem", None)], _PEAK_SHAPE_CASES),
+    _wave("nxsig_sawtooth", [("width", "v", 0.5)], [("width=2", {"width": 2.0}), ("width=nan", {"width": float("nan")})]),
+    _wave("nxsig_square", [("duty", "v", 0.5), ("duty_tensor", "in?", None)], [], out=np.zeros(8, np.int32)),
+    ("nxsig_gaussian_pulse",
+     [("t", "in", np.linspace(-1, 1, 8, dtype=np.float32)), ("is_f64", "v", 0), ("n", "v", 8), ("center_frequency", "v", 1.0), ("bandwidth", "v", 0.5),
+      ("bandwidth_reference_level", "v", -6.0), ("envelope", "out", np.zeros(8, np.float32)), ("in_phase", "out", np.zeros(8, np.float32)),
+      ("quadrature", "out", np.zeros(8, np.float32)), ("mem", "mem", None)],
+     [("n=-1", {"n": -1}), ("center_frequency=-1", {"center_frequency": -1.0}), ("bandwidth=0", {"bandwidth": 0.0}),
+      ("bandwidth_reference_level=0", {"bandwidth_reference_level": 0.0})]),
+    _wave("nxsig_chirp", [("f0", "v", 1.0), ("t1", "v", 1.0), ("f1", "v", 4.0), ("method", "v", _lib.CHIRP_LINEAR), ("vertex_zero", "v", 1), ("phi", "v", 0.0)],
+          [("method=9", {"method": 9})]),
+    _wave("nxsig_polynomial_sweep", [("coefs", "host", np.array([1.0, 2.0, 3.0])), ("ncoefs", "v", 3), ("phi", "v", 0.0), ("phi_degrees", "v", 0)],
+          [("ncoefs=0", {"ncoefs": 0}), ("ncoefs=33", {"ncoefs": 33})]),
+    ("nxsig_unit_impulse",
+     [("dtype", "v", _lib.DT_F32), ("shape", "host?", _i64(8)), ("rank", "v", 1), ("index", "host?", _i64(3)), ("out", "out?", np.zeros(8, np.float32)),
+      ("mem", "mem", None)],
+     [("dtype=9", {"dtype": 9}), ("rank=-1", {"rank": -1}), ("rank=9", {"rank": 9}), ("null shape", {"shape": None}), ("null index", {"index": None}),
+      ("negative dimension", {"shape": _i64(-8)}), ("shape too large", {"shape": _i64(1 << 40, 1 << 40), "rank": 2, "index": _i64(0, 0)}),
+      ("null out", {"out": None}), ("index=8", {"index": _i64(8)})]),
+    # f64 / c128 tier
+    _stft("nxsig_stft_f64", _f32(B, L).astype(np.float64), np.zeros((B, M, K), np.complex128), True, 1, window=WIN.astype(np.float64),
+          wflag=[("window_is_f64", "v", 1)]),
+    _stft("nxsig_stft_c128", _c64(B, L).astype(np.complex128), np.zeros((B, M, K), np.complex128), True, 1, window=WIN.astype(np.float64),
+          wflag=[("window_is_f64", "v", 1)]),
+    _istft("nxsig_istft_c128", _c64(B, M, K).astype(np.complex128), np.zeros((B, M * HOP + N - HOP), np.complex128), True, window=WIN.astype(np.float64),
+           wflag=[("window_is_f64", "v", 1)]),
+    _fft("nxsig_fft_c128", np.float64, np.complex128),
+    _framing("nxsig_as_windowed_f64", np.float64),
+    _ola("nxsig_overlap_and_add_f64", np.float64),
+    _fir("nxsig_fir_f64", np.float64, True, False),
+    _fir("nxsig_fir_slice_f64", np.float64, True, True),
+]
+
+
+def _cases(args, listed):
+    out = [("valid", {})]
+    out += [("null " + a, {a: None}) for a, kind, _ in args if kind in ("in", "out", "host", "hout", "p")]
+    out.append(("mem=7", {"mem": 7}))
+    return [c if len(c) == 3 else (*c, None) for c in out + list(listed)]
+
+
+class Probe:
+    def __init__(self, lib, ctx):
+        self.lib, self.ctx = lib, ctx
+
+    def _dev(self, arr):
+        p = C.c_void_p()
+        assert self.lib.nxsig_alloc(self.ctx, max(arr.nbytes, 4), C.byref(p)) == 0, self.lib.nxsig_last_error()
+        assert self.lib.nxsig_upload(self.ctx, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes) == 0, self.lib.nxsig_last_error()
+        return p
+
+    def call(self, name, args, broken, mem):
+        """one call; returns (record, {out arg: bytes})"""
+        fn = getattr(self.lib, name)
+        argtypes = _lib.SIGNATURES[name][1][1:]
+        params = dict(PARAMS)
+        for k, v in broken.items():
+            if k.startswith("p."):
+                params[k[2:]] = v
+        nf = C.c_int64(NF_SENTINEL)
+        keep, call, outs, devs = [], [], [], []
+        for (a, kind, val), at in zip(args, argtypes):
+            if a in broken:
+                val = broken[a]
+            if kind == "mem":
+                call.append(val if val is not None else mem)
+            elif kind == "v":
+                call.append(val)
+            elif kind == "nf":
+                call.append(C.byref(nf))
+            elif val is None:
+                call.append(None)
+            elif kind == "p":
+                st = _lib.StftParams(*[params[f] for f, _ in _lib.StftParams._fields_])
+                keep.append(st)
+                call.append(C.byref(st))
+            else:
+                arr = np.array(val, copy=True)
+                keep.append(arr)
+                tensor = kind.rstrip("?") in ("in", "out")
+                if tensor and mem == _lib.DEVICE:
+                    d = self._dev(arr)
+                    devs.append((d, arr, kind.startswith("out")))
+                    call.append(d if at is C.c_void_p else C.cast(d, at))
+                else:
+                    call.append(arr.ctypes.data_as(at))
+                if kind.rstrip("?") in ("out", "hout"):
+                    outs.append((a, arr))
+        rc = fn(self.ctx, *call)
+        err = self.lib.nxsig_last_error().decode("utf-8", "replace") if rc != 0 else ""
+        for d, arr, is_out in devs:
+            if is_out and rc == 0:
+                assert self.lib.nxsig_download(self.ctx, arr.ctypes.data_as(C.c_void_p), d, arr.nbytes) == 0, self.lib.nxsig_last_error()
+            assert self.lib.nxsig_free(self.ctx, d) == 0
+        if devs:
+            assert self.lib.nxsig_sync(self.ctx) == 0
+        rec = {"rc": rc, "err": err}
+        if any(kind == "nf" for _, kind, _ in args):
+            rec["num_frames_out"] = nf.value
+        return rec, {a: arr.tobytes() for a, arr in outs}
+
+    def run(self):
+        """{entry point: {case: record}}; with a context the valid row also carries "host_equals_device" """
+        real = self.ctx is not None
+        table = {}
+        for name, args, listed in ENTRIES:
+            rows = {}
+            for label, broken, only in _cases(args, listed):
+                if real and only == NULL_ONLY:
+                    continue
+                rec, host_out = self.call(name, args, broken, _lib.HOST)
+                if real and label == "valid":
+                    assert rec["rc"] == 0, (name, rec)
+                    rec_d, dev_out = self.call(name, args, broken, _lib.DEVICE)
+                    assert rec_d == rec, (name, rec, rec_d)
+                    rec["host_equals_device"] = host_out == dev_out
+                elif real:
+                    assert rec["rc"] != 0, f"{name} [{label}]: a broken argument was accepted (and something was launched)"
+                rows[label] = rec
+            table[name] = rows
+        return table
+
+
+def probe(lib_path, real):
+    lib = bind(lib_path)
+    ctx = None
+    if real:
+        ctx = C.c_void_p()
+        rc = lib.nxsig_ctx_create(0, C.byref(ctx))
+        assert rc == 0, lib.nxsig_last_error()
+    try:
+        return Probe(lib, ctx).run()
+    finally:
+        if real:
+            lib.nxsig_ctx_destroy(ctx)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--lib", default=_lib.LIB_PATH)
+    ap.add_argument("--real", action="store_true", help="use a context on device 0 (needs the GPU) instead of ctx = NULL")
+    ap.add_argument("--write", metavar="JSON", default=None, help="merge the table into this golden file (default: print it)")
+    a = ap.parse_args()
+    key = "real_ctx" if a.real else "null_ctx"
+    table = probe(a.lib, a.real)
+    if not a.write:
+        print(json.dumps({key: table}, indent=1))
+        return
+    doc = {}
+    if os.path.exists(a.write):
+        with open(a.write) as f:
+            doc = json.load(f)
+    doc[key] = table
+    with open(a.write, "w") as f:
+        json.dump(doc, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{a.write}: {key}: {sum(len(v) for v in table.values())} cases of {len(table)} entry points")
+
+
+if __name__ == "__main__":
+    main()
