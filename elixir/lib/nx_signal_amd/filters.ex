@@ -3,7 +3,8 @@ defmodule NxSignalAMD.Filters do
   `NxSignal.Filters.median/2`, `wiener/2` (lib/nx_signal/filters.ex:17-110, :281-303) on the GPU kernels of DESIGN.md section 3.9,
   `firwin/3` (:147-279) and the streaming `fir/3` the reference lacks:
   `fir(x, taps, mode: :same)` == `NxSignal.Convolution.convolve(x, taps, method: :fft, mode: :same)` to fp32
-  rounding, computed by overlap-save block FFT convolution on the GPU.
+  rounding, computed by overlap-save block FFT convolution on the GPU; `resample_poly/4`, polyphase rational resampling
+  (`scipy.signal.resample_poly` with `padtype="constant"`, DESIGN.md section 3.11), which the reference lacks as well.
   """
   alias NxSignalAMD.NIF
 
@@ -149,6 +150,95 @@ defmodule NxSignalAMD.Filters do
       |> NxSignalAMD.unwrap!()
 
     Nx.from_binary(y, type) |> Nx.reshape(Nx.shape(t))
+  end
+
+  @doc """
+  Resamples the last axis of real f32 or complex c64 rows by `up / down` with a polyphase FIR on the GPU, like
+  `scipy.signal.resample_poly(x, up, down, padtype="constant")`: `n` samples give `ceil(n * up / down)`.  With the reduced ratio,
+  the taps `h` (gain included) and `half = div(length(h) - 1, 2)`: `y[m] = sum_j x[j] * h[m * down + half - j * up]` over the taps
+  that exist.  `:window` — any window `firwin/3` takes; the default filter is
+  `up * firwin(20 * max(up, down) + 1, [1 / max(up, down)], window: w, sampling_rate: 2.0, type: {:f, 64})` rounded once to f32.
+  `:taps` — a 1-D real tensor instead (scipy's array form of `window=`, without the gain: `h = up * taps`).  `up == down` after
+  reduction returns the input.  A `DeviceTensor` gives a `DeviceTensor`.  An Inf / NaN sample reaches the outputs whose taps cover
+  it and nothing else.
+  """
+  def resample_poly(x, up, down, opts \\ []) do
+    opts = Keyword.validate!(opts, window: {:kaiser, 5.0}, taps: nil, padtype: :constant)
+
+    if not (is_integer(up) and is_integer(down) and up >= 1 and down >= 1) do
+      raise ArgumentError, "resample_poly: up and down must be integers >= 1, got: #{inspect(up)}, #{inspect(down)}"
+    end
+
+    if opts[:padtype] != :constant do
+      raise ArgumentError, "resample_poly: only padtype :constant is built, got: #{inspect(opts[:padtype])}"
+    end
+
+    g = Integer.gcd(up, down)
+    {up, down} = {div(up, g), div(down, g)}
+    hb =
+      if up == down and is_nil(opts[:taps]) do
+        # no filter is applied, as in scipy: the window is still validated, and one unused tap travels with the call
+        firwin(3, [0.5], window: opts[:window])
+        <<1.0::float-32-native>>
+      else
+        resample_taps(up, down, opts[:taps], opts[:window])
+      end
+
+    resample_rows(x, up, down, hb)
+  end
+
+  defp resample_taps(up, _down, %Nx.Tensor{} = taps, _window) do
+    if Nx.rank(taps) != 1 or match?({:c, _}, Nx.type(taps)) do
+      raise ArgumentError, "resample_poly: taps must be a 1-D real tensor"
+    end
+
+    taps |> Nx.as_type(:f64) |> Nx.multiply(up) |> Nx.as_type(:f32) |> Nx.to_binary()
+  end
+
+  defp resample_taps(_up, _down, taps, _window) when not is_nil(taps) do
+    raise ArgumentError, "resample_poly: taps must be a 1-D real tensor, got: #{inspect(taps)}"
+  end
+
+  defp resample_taps(up, down, nil, window) do
+    big = max(up, down)
+
+    firwin(20 * big + 1, [1.0 / big], window: window, sampling_rate: 2.0, type: {:f, 64})
+    |> Nx.multiply(up)
+    |> Nx.as_type(:f32)
+    |> Nx.to_binary()
+  end
+
+  defp resample_rows(%NxSignalAMD.DeviceTensor{type: type} = x, up, down, hb) do
+    r = tuple_size(x.shape)
+    length = elem(x.shape, r - 1)
+    batch_shape = Tuple.delete_at(x.shape, r - 1)
+    is_complex = if type == {:c, 64}, do: 1, else: 0
+
+    {:ok, yref, n_out} =
+      NIF.resample_poly_dev(x.ctx, x.ref, is_complex, length, Tuple.product(batch_shape), hb, up, down) |> NxSignalAMD.unwrap!()
+
+    %NxSignalAMD.DeviceTensor{ref: yref, ctx: x.ctx, shape: Tuple.insert_at(batch_shape, r - 1, n_out), type: type}
+  end
+
+  defp resample_rows(x, up, down, hb) do
+    {type, is_complex} =
+      case Nx.type(x) do
+        {:f, 32} -> {:f32, 0}
+        {:c, 64} -> {:c64, 1}
+        other -> raise ArgumentError, "resample_poly: f32 and c64 tensors are built, got: #{inspect(other)}"
+      end
+
+    shape = Nx.shape(x)
+    r = tuple_size(shape)
+    if r < 1, do: raise(ArgumentError, "resample_poly: the tensor must have at least one axis")
+    length = elem(shape, r - 1)
+    batch_shape = Tuple.delete_at(shape, r - 1)
+
+    {:ok, y, n_out} =
+      NIF.resample_poly(NxSignalAMD.context(), Nx.to_binary(x), is_complex, length, Tuple.product(batch_shape), hb, up, down)
+      |> NxSignalAMD.unwrap!()
+
+    Nx.from_binary(y, type) |> Nx.reshape(Tuple.insert_at(batch_shape, r - 1, n_out))
   end
 
   defp b(true), do: 1

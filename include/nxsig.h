@@ -147,6 +147,11 @@ int64_t nxsig_num_frames(int64_t length, int32_t frame_length, int32_t hop, int3
 int64_t nxsig_ola_length(int64_t num_frames, int32_t frame_length, int32_t hop);
 /* output length of convolve for a mode — lib/nx_signal/convolution.ex:300-347 */
 int64_t nxsig_conv_length(int64_t n1, int64_t n2, int32_t mode);
+/* rows of nxsig_resample_poly: ceil(length * up / down) (the ratio need not be reduced); negative status when length < 0 or
+ * up, down < 1 */
+int64_t nxsig_resample_length(int64_t length, int32_t up, int32_t down);
+/* outputs of one row a workgroup of the resample.poly.lds tier owns (the tile whose edges the tests straddle) */
+int32_t nxsig_resample_tile(void);
 
 /* ------------------------------------------ host-side generators (BinaryBackend rounding) */
 /* NxSignal.Windows.* (n, is_periodic:, type: f32) — lib/nx_signal/windows.ex; beta/eps: kaiser only */
@@ -249,6 +254,26 @@ int nxsig_convolve_direct(nxsig_ctx* ctx, const void* a, int32_t a_is_real, cons
  */
 int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int64_t* shape, int32_t rank, const int64_t* kernel_shape,
                         float* out, int32_t mem);
+
+/*
+ * Filters.resample_poly: the last axis of real f32 (or c64 when is_complex) rows resampled by the rational factor up / down with a
+ * polyphase FIR — scipy.signal.resample_poly(x, up, down, window: h / up, padtype: "constant").  The reference has no resampler.
+ * Definition: the ratio is reduced first (g = gcd(up, down), up /= g, down /= g); a row of n = length samples gives
+ * n_out = nxsig_resample_length(n, up, down) = ceil(n up / down) outputs; with the taps h[0 .. L), real, GAIN INCLUDED (scipy's
+ * up * window), and half = (L - 1) / 2,
+ *     y[m] = sum_j x[j] h[m down + half - j up]      over every j in [0, n) whose tap index lies in [0, L), and nothing else
+ * — with c = m down + half, q = c div up, r = c mod up:  y[m] = sum_{t >= 0} x[q - t] h[r + t up], one polyphase branch r of at
+ * most T = ceil(L / up) taps per output, accumulated from +0.0 by one fmaf per term in ascending t (c64: each component on its
+ * own).  Samples outside the row and taps outside [0, L) are never multiplied in: an Inf / NaN reaches exactly the outputs whose
+ * branch covers it, and no other row (this is NOT nxsig_fir_f32's whole-row rule).  up == down after reduction: y is a copy of x,
+ * no filter applied (dispatch resample.copy).
+ *   x [batch][length] rows batch_stride >= length elements apart, h f32[num_taps] HOST, y [batch][n_out] dense.
+ * Dispatch: resample.poly.lds while the phase table up x T floats is at most 64 KiB (and it fits the LDS next to a tile's input
+ * span), resample.poly.generic otherwise and under NXSIG_DISABLE_RESAMPLE_LDS — the same bits from both.  NXSIG_ERR_UNSUPPORTED:
+ * 2^31 or more tiles in one call.
+ */
+int nxsig_resample_poly(nxsig_ctx* ctx, const void* x, int32_t is_complex, int64_t length, int32_t batch, int64_t batch_stride,
+                        const float* h, int32_t num_taps, int32_t up, int32_t down, void* y, int32_t mem);
 
 /*
  * Filters.wiener/2 — lib/nx_signal/filters.ex:81-110, :281-303, computed in f64: S1 / S2 = correlate(t, ones(kernel_size)) and

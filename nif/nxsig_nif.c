@@ -776,6 +776,62 @@ static ERL_NIF_TERM nif_median(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
   return mk_ok(env, enif_make_binary(env, &ob));
 }
 
+/* the scalar arguments the two resample_poly NIFs share: argv[2 ...] = is_complex, length, batch, taps_bin (f32, gain included), up, down */
+static int resample_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], int* is_complex, ErlNifSInt64* length, int* batch, ErlNifBinary* h, int* up,
+                         int* down) {
+  return enif_get_int(env, argv[2], is_complex) && enif_get_int64(env, argv[3], length) && enif_get_int(env, argv[4], batch) &&
+         enif_inspect_binary(env, argv[5], h) && enif_get_int(env, argv[6], up) && enif_get_int(env, argv[7], down) && *batch >= 1 &&
+         *length >= 1 && h->size % 4 == 0 && h->size / 4 <= 0x7fffffff;
+}
+
+/* resample_poly(ctx, x_bin, is_complex, length, batch, taps_bin, up, down) -> {:ok, y_bin, out_length}
+   (Filters.resample_poly/4: polyphase resampling of f32 / c64 rows by up / down, include/nxsig.h: nxsig_resample_poly) */
+static ERL_NIF_TERM nif_resample_poly(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary x, h, yb;
+  ErlNifSInt64 length;
+  int is_complex, batch, up, down;
+  if (argc != 8 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) ||
+      !resample_args(env, argv, &is_complex, &length, &batch, &h, &up, &down))
+    return enif_make_badarg(env);
+  const size_t es = is_complex ? 8 : 4;
+  size_t xbytes = es;
+  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x.size != xbytes) return enif_make_badarg(env);
+  int64_t n = nxsig_resample_length(length, up, down);
+  if (n < 0) return mk_error(env, (int)n);
+  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, es)) return mk_oom(env);
+  int rc = nxsig_resample_poly(c->ctx, x.data, is_complex, length, batch, length, (const float*)h.data, (int)(h.size / 4), up, down, yb.data,
+                               NXSIG_HOST);
+  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
+  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &yb), enif_make_int64(env, n));
+}
+
+/* resample_poly_dev(ctx, x_buf, is_complex, length, batch, taps_bin, up, down) -> {:ok, y_buf, out_length} */
+static ERL_NIF_TERM nif_resample_poly_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  buf_res_t* x;
+  ErlNifBinary h;
+  ErlNifSInt64 length;
+  int is_complex, batch, up, down;
+  if (argc != 8 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &x) ||
+      !resample_args(env, argv, &is_complex, &length, &batch, &h, &up, &down))
+    return enif_make_badarg(env);
+  const size_t es = is_complex ? 8 : 4;
+  size_t xbytes = es;
+  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x->owner != c || x->bytes < xbytes)
+    return enif_make_badarg(env);
+  int64_t n = nxsig_resample_length(length, up, down);
+  if (n < 0) return mk_error(env, (int)n);
+  size_t ybytes = es;
+  if (!mul_size(&ybytes, (uint64_t)batch) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
+  void* y = NULL;
+  int rc = nxsig_alloc(c->ctx, ybytes, &y);
+  if (rc) return mk_error(env, rc);
+  rc = nxsig_resample_poly(c->ctx, x->dptr, is_complex, length, batch, length, (const float*)h.data, (int)(h.size / 4), up, down, y, NXSIG_DEVICE);
+  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
+  return enif_make_tuple3(env, mk_atom(env, "ok"), make_buf(env, c, y, ybytes), enif_make_int64(env, n));
+}
+
 /* wiener(ctx, x_bin, is_f64, shape, kernel_size, has_noise, noise) -> {:ok, binary of x's type}   (Filters.wiener/2, filters.ex:81-110) */
 static ERL_NIF_TERM nif_wiener(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
@@ -1819,6 +1875,8 @@ static ErlNifFunc funcs[] = {
     {"convolve_direct", 8, nif_convolve_direct, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"median", 5, nif_median, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"wiener", 7, nif_wiener, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"resample_poly", 8, nif_resample_poly, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"resample_poly_dev", 8, nif_resample_poly_dev, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"argrelextrema", 7, nif_argrelextrema, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"nonzero", 3, nif_nonzero, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"sawtooth", 4, nif_sawtooth, ERL_NIF_DIRTY_JOB_IO_BOUND},

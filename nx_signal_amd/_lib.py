@@ -60,6 +60,21 @@ _p = C.c_void_p
 _i32, _i64, _f64, _sz = C.c_int32, C.c_int64, C.c_double, C.c_size_t
 _pf = C.POINTER(C.c_float)
 
+
+class NxsigCtx(C.Structure):
+    """the opaque nxsig_ctx of include/nxsig.h"""
+
+
+# nxsig_ctx* as a typed pointer (None, or ctx_ptr(handle)).  The entry points older than nxsig_resample_poly take their context as a plain
+# void pointer, and tests/test_abi_errors_host.py holds exactly those to the recorded table of tests/golden/abi_error_table.json; the error
+# table of an entry point added since lives with its own tests (tests/test_resample_host.py, tests/test_gpu_resample.py).
+_ctx = C.POINTER(NxsigCtx)
+
+
+def ctx_ptr(handle):
+    """a context handle (c_void_p, int or None) as the typed pointer of the signatures that declare one"""
+    return None if handle is None else C.cast(handle, _ctx)
+
 # name -> (restype, argtypes); every symbol include/nxsig.h declares is listed here (tests check both ways)
 SIGNATURES = {
     "nxsig_abi_version": (C.c_int, []),
@@ -114,6 +129,9 @@ SIGNATURES = {
     "nxsig_convolve_direct": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _p, _i32, C.POINTER(_i64), _i32, _i32, _p, C.POINTER(_i64), _i32]),
     "nxsig_fir_slice_f32": (C.c_int, [_p, _p, _i64, _i32, _i64, _p, _i32, _i64, _i64, _p, _i32]),
     "nxsig_median_filter": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _p, _i32]),
+    "nxsig_resample_length": (_i64, [_i64, _i32, _i32]),
+    "nxsig_resample_tile": (_i32, []),
+    "nxsig_resample_poly": (C.c_int, [_ctx, _p, _i32, _i64, _i32, _i64, _p, _i32, _i32, _i32, _p, _i32]),
     "nxsig_wiener": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _i32, _f64, _p, C.POINTER(_f64), _i32]),
     "nxsig_argrelextrema": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, _i32, _i64, _i32, _p, _p, _i32]),
     "nxsig_nonzero": (C.c_int, [_p, _p, C.POINTER(_i64), _i32, _p, _p, _i32]),

@@ -52,6 +52,7 @@ UNITS = [
     ("kernels_filters.hip", []),  # Filters.median / wiener (no FMA contraction: the file says so itself)
     ("kernels_peaks.hip", []),  # PeakFinding.argrelextrema / nonzero: mark, scan, compact
     ("kernels_waveforms.hip", []),  # Waveforms.* elementwise (no FMA contraction: the file says so itself)
+    ("kernels_resample.hip", []),  # Filters.resample_poly: polyphase rational resampling
 ]
 
 

@@ -1470,6 +1470,19 @@ int64_t nxsig_conv_length(int64_t n1, int64_t n2, int32_t mode) {
   }
 }
 
+static int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+
+int64_t nxsig_resample_length(int64_t length, int32_t up, int32_t down) {
+  if (length < 0) return set_error(NXSIG_ERR_INVALID_ARG, "resample_length: length must be >= 0");
+  if (up < 1 || down < 1) return set_error(NXSIG_ERR_INVALID_ARG, "resample_length: up and down must be >= 1");
+  const int64_t g = gcd64(up, down);
+  const unsigned __int128 v = ((unsigned __int128)length * (uint64_t)(up / g) + (uint64_t)(down / g) - 1) / (uint64_t)(down / g);
+  if (v > (unsigned __int128)INT64_MAX) return set_error(NXSIG_ERR_INVALID_ARG, "resample_length: the result does not fit 64 bits");
+  return (int64_t)v;
+}
+
+int32_t nxsig_resample_tile(void) { return kResampleTile; }
+
 /* ---------------------------------------------------------------- host generators */
 int nxsig_window_f32(int32_t kind, int32_t n, int32_t is_periodic, double beta, double eps, float* out) {
   NXSIG_API_BEGIN
@@ -1671,6 +1684,36 @@ int nxsig_median_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, const int
   HostIo io(c, mem);
   if ((rc = io.open({{x, (size_t)n * (is_f64 ? 8 : 4), kScratchNdStageA}}, {{out, (size_t)n * 4, kScratchNdStageOut}}))) return rc;
   if ((rc = launch_median(c, io.in[0], is_f64 != 0, shape, rank, kernel_shape, static_cast<float*>(io.out[0])))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+int nxsig_resample_poly(nxsig_ctx* ctx, const void* x, int32_t is_complex, int64_t length, int32_t batch, int64_t batch_stride,
+                        const float* h, int32_t num_taps, int32_t up, int32_t down, void* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !h || !y) return set_error(NXSIG_ERR_INVALID_ARG, "resample_poly: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (batch < 1 || length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "resample_poly: batch and length must be >= 1");
+  if (batch_stride < length) return set_error(NXSIG_ERR_INVALID_ARG, "resample_poly: batch_stride < length");
+  if (up < 1 || down < 1) return set_error(NXSIG_ERR_INVALID_ARG, "resample_poly: up and down must be >= 1");
+  if (num_taps < 1) return set_error(NXSIG_ERR_INVALID_ARG, "resample_poly: the tap vector is empty");
+  const int32_t g = (int32_t)gcd64(up, down);
+  const int64_t n_out = nxsig_resample_length(length, up, down);
+  if (n_out < 0) return (int)n_out;
+  if (n_out > INT64_MAX / batch / 8) return set_error(NXSIG_ERR_UNSUPPORTED, "resample_poly: the result is too large");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  const size_t elem = is_complex ? sizeof(float2) : sizeof(float);
+  ResampleLaunch a;
+  a.is_complex = is_complex != 0; a.n = length; a.batch_stride = batch_stride; a.n_out = n_out; a.batch = batch;
+  a.h_host = h; a.taps = num_taps; a.up = up / g; a.down = down / g;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, elem), kScratchStageIn}},
+                    {{y, (size_t)batch * n_out * elem, kScratchStageOut}}))) return rc;
+  a.x = io.in[0]; a.y = io.out[0];
+  if ((rc = a.up == a.down ? launch_resample_copy(c, a) : launch_resample_poly(c, a))) return rc;
   return io.close();
   NXSIG_API_END
 }

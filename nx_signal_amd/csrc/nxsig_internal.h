@@ -90,7 +90,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(STORE_POLICY) X(WAVE_NO_SPLIT) X(NO_AL8) X(NO_STAGE) X(WAVE_UNITS_PER_WAVE) X(STAGE_PAD) X(NO_HOP4) X(WAVE_SMALL_W) X(WAVE_SMALL_CHUNK) \
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
-  X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES)
+  X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -358,6 +358,20 @@ int launch_stft_big(Ctx* c, const StftLaunch& s);
 int launch_median(Ctx* c, const void* x, bool f64, const int64_t* shape, int rank, const int64_t* ks, float* out);
 int launch_wiener(Ctx* c, const void* x, bool f64, const int64_t* shape, int rank, const int64_t* ks, bool has_noise, double noise, void* out,
                   const double** noise_dev);
+// kernels_resample.hip: Filters.resample_poly (include/nxsig.h states the definition).  up / down are REDUCED, up != down; h_host are
+// the taps with the gain included; y is dense [batch][n_out].  The phase table goes through ctx_table; nothing waits
+struct ResampleLaunch {
+  const void* x;               // device f32 / c64 [batch][n], rows batch_stride elements apart
+  bool is_complex;
+  int64_t n, batch_stride, n_out;
+  int32_t batch;
+  const float* h_host;
+  int32_t taps, up, down;
+  void* y;
+};
+constexpr int kResampleTile = 1024;   // outputs of one row per workgroup of the LDS tier
+int launch_resample_poly(Ctx* c, const ResampleLaunch& a);
+int launch_resample_copy(Ctx* c, const ResampleLaunch& a);
 // kernels_peaks.hip: PeakFinding.argrelextrema over a device tensor (dtype: nxsig_dtype; the shape checks are the caller's) and the
 // nonzero compaction of a u8 mask; indices [size][rank] and *valid on the device, nothing waits
 int launch_argrelextrema(Ctx* c, const void* x, int dtype, const int64_t* shape, int rank, int axis, int64_t shifts, int comparator,

@@ -153,3 +153,90 @@ def wiener(t, ctx=None, return_noise=False, **opts):
         _lib.check(lib.nxsig_wiener(c.handle, x.ctypes.data_as(C.c_void_p), int(is_f64), sh, rank, kc, *args, out.ctypes.data_as(C.c_void_p),
                                     C.byref(used) if return_noise else None, _lib.HOST))
     return (out, used.value) if return_noise else out
+
+
+_RESAMPLE_KEYS = ("ctx", "axis", "window", "taps", "padtype")
+
+
+def resample_poly_taps(up, down, window=("kaiser", 5.0)):
+    """The default anti-alias filter of resample_poly with its gain, f32: `up * firwin(20 * max(up, down) + 1, [1 / max(up, down)],
+    window: w, sampling_rate: 2.0, type: f64)` of the REDUCED up / down, formed in f64 and rounded once (scipy.signal.resample_poly's
+    design, on this project's firwin)."""
+    up, down = _resample_ratio(up, down)
+    big = max(up, down)
+    h = firwin(20 * big + 1, [1.0 / big], window=window, sampling_rate=2.0, type="f64")
+    return (np.float64(up) * h).astype(np.float32)
+
+
+def _resample_ratio(up, down):
+    for name, v in (("up", up), ("down", down)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ArgumentError(f"resample_poly: {name} must be an integer >= 1, got: {v!r}")
+    up, down = int(up), int(down)
+    if up < 1 or down < 1:
+        raise ArgumentError(f"resample_poly: up and down must be >= 1, got: {up}, {down}")
+    if up >= 2 ** 31 or down >= 2 ** 31:
+        raise ArgumentError("resample_poly: up and down must fit 32 bits")
+    g = int(np.gcd(up, down))
+    return up // g, down // g
+
+
+def resample_poly(x, up, down, ctx=None, axis=-1, window=("kaiser", 5.0), taps=None, padtype="constant", **opts):
+    """Extension (the reference has no resampler): resample `axis` of real f32 or complex c64 rows by the rational factor up / down
+    with a polyphase FIR on the GPU — scipy.signal.resample_poly(x, up, down, padtype="constant").  n samples give ceil(n up / down);
+    with the reduced ratio, taps h (gain included) and half = (len(h) - 1) // 2:  y[m] = sum_j x[j] h[m down + half - j up] over the
+    taps that exist (include/nxsig.h: nxsig_resample_poly).  window: any window firwin accepts, the default
+    filter is resample_poly_taps(up, down, window); taps: a 1-D real array instead (scipy's array form of `window=`, WITHOUT the
+    gain: h = up * taps).  up == down after reduction returns a copy.  Host arrays: any axis, numpy out; a device tensor: the last
+    axis only, a DeviceBuffer out.  An Inf / NaN sample reaches the outputs whose taps cover it and nothing else."""
+    _unknown(opts, _RESAMPLE_KEYS, "resample_poly")
+    up, down = _resample_ratio(up, down)
+    if padtype != "constant":
+        raise ArgumentError(f"resample_poly: only padtype \"constant\" is built, got: {padtype!r}")
+    if taps is not None:
+        t = np.asarray(taps)
+        if t.ndim != 1 or t.dtype.kind not in "fiu":
+            raise ArgumentError("resample_poly: taps must be a 1-D real array")
+        if t.shape[0] < 1:
+            raise ArgumentError("resample_poly: the tap vector is empty")
+        h = (np.float64(up) * t.astype(np.float64)).astype(np.float32)
+    elif up != down:
+        h = resample_poly_taps(up, down, window)
+    else:
+        firwin(3, [0.5], window=window)   # the window is validated although nothing is filtered
+        h = np.ones(1, np.float32)
+    host, dev = _tensor(x)
+    shape = tuple(host.shape) if dev is None else tuple(dev[1])
+    dtype = host.dtype if dev is None else np.dtype(dev[2])
+    if dtype not in (np.float32, np.complex64):
+        raise NxSignalUnsupported(f"resample_poly: f32 and c64 tensors are built, got {dtype}")
+    rank = len(shape)
+    if rank < 1:
+        raise ArgumentError("resample_poly: the tensor must have at least one axis")
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not -rank <= axis < rank:
+        raise ArgumentError(f"resample_poly: axis {axis!r} is out of bounds for a tensor of rank {rank}")
+    axis = int(axis) % rank
+    if any(s < 1 for s in shape):
+        raise ArgumentError("resample_poly: empty dimension")
+    lib = _lib.load()
+    is_c = int(dtype == np.complex64)
+    if dev is not None:
+        if axis != rank - 1:
+            raise ArgumentError("resample_poly: device tensors are resampled along their last axis only")
+        n = shape[-1]
+        n_out = _lib.check(lib.nxsig_resample_length(n, up, down))
+        batch = int(np.prod(shape[:-1], dtype=np.int64))
+        c = x.ctx if isinstance(x, DeviceBuffer) else (ctx or default_context())
+        out = DeviceBuffer.empty(c, shape[:-1] + (n_out,), dtype)
+        _lib.check(lib.nxsig_resample_poly(_lib.ctx_ptr(c.handle), C.c_void_p(dev[0]), is_c, n, batch, n, h.ctypes.data_as(C.c_void_p), h.shape[0],
+                                           up, down, C.c_void_p(out.ptr), _lib.DEVICE))
+        return out
+    xs = np.ascontiguousarray(np.moveaxis(host, axis, -1))
+    n = xs.shape[-1]
+    n_out = _lib.check(lib.nxsig_resample_length(n, up, down))
+    batch = int(np.prod(xs.shape[:-1], dtype=np.int64))
+    out = np.empty(xs.shape[:-1] + (n_out,), dtype)
+    c = ctx or default_context()
+    _lib.check(lib.nxsig_resample_poly(_lib.ctx_ptr(c.handle), xs.ctypes.data_as(C.c_void_p), is_c, n, batch, n, h.ctypes.data_as(C.c_void_p), h.shape[0],
+                                       up, down, out.ctypes.data_as(C.c_void_p), _lib.HOST))
+    return np.ascontiguousarray(np.moveaxis(out, -1, axis))

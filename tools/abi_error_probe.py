@@ -2,12 +2,17 @@
 argument broken at a time; the return code, nxsig_last_error() and what landed in *num_frames_out are recorded per case.
 
     python tools/abi_error_probe.py [--lib PATH] [--real] [--write tests/golden/abi_error_table.json]
+    python tools/abi_error_probe.py --own [--real] [--write tests/golden/abi_error_table_resample.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
 before anything is launched (the probe refuses a broken case that returns 0), and the valid row of each entry point runs once with
 NXSIG_HOST and once with NXSIG_DEVICE, the two results compared bit for bit.  The golden file holds both tables; regenerate it from
-the build whose behaviour is the reference (tests/test_abi_errors_host.py and tests/test_gpu_abi_errors.py compare against it)."""
+the build whose behaviour is the reference (tests/test_abi_errors_host.py and tests/test_gpu_abi_errors.py compare against it).
+
+ENTRIES and that golden file are the recorded table of the entry points that existed when it was made.  An entry point added since
+keeps its rows in OWN_TABLE_ENTRIES and a golden file of its own (--own; tests/test_resample_host.py and tests/test_gpu_resample.py
+compare against it): the same probe, the same kinds of cases."""
 import argparse
 import ctypes as C
 import json
@@ -22,6 +27,7 @@ if ROOT not in sys.path:
 from nx_signal_amd import _lib  # noqa: E402  (signature table + structs only)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_error_table.json")
+GOLDEN_OWN = os.path.join(ROOT, "tests", "golden", "abi_error_table_resample.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -242,6 +248,18 @@ ENTRIES = [
 ]
 
 
+# entry points younger than the recorded table (their context is the typed pointer _lib._ctx)
+OWN_TABLE_ENTRIES = [
+    ("nxsig_resample_poly",
+     [("x", "in", _f32(B, FL)), ("is_complex", "v", 0), ("length", "v", FL), ("batch", "v", B), ("batch_stride", "v", FL), ("h", "host", _f32(5)),
+      ("num_taps", "v", 5), ("up", "v", 2), ("down", "v", 3), ("y", "out", np.zeros((B, 11), np.float32)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": FL - 1}), ("up=0", {"up": 0}),
+      ("down=0", {"down": 0}), ("num_taps=0", {"num_taps": 0}),
+      ("result past 64 bits", {"length": 1 << 62, "batch_stride": 1 << 62, "up": 1 << 20, "down": 1}),
+      ("result too large", {"length": 1 << 58, "batch_stride": 1 << 58, "batch": 16, "up": 3, "down": 2})]),
+]
+
+
 def _cases(args, listed):
     out = [("valid", {})]
     out += [("null " + a, {a: None}) for a, kind, _ in args if kind in ("in", "out", "host", "hout", "p")]
@@ -296,7 +314,7 @@ class Probe:
                     call.append(arr.ctypes.data_as(at))
                 if kind.rstrip("?") in ("out", "hout"):
                     outs.append((a, arr))
-        rc = fn(self.ctx, *call)
+        rc = fn(_lib.ctx_ptr(self.ctx) if _lib.SIGNATURES[name][1][0] is _lib._ctx else self.ctx, *call)
         err = self.lib.nxsig_last_error().decode("utf-8", "replace") if rc != 0 else ""
         for d, arr, is_out in devs:
             if is_out and rc == 0:
@@ -309,11 +327,11 @@ class Probe:
             rec["num_frames_out"] = nf.value
         return rec, {a: arr.tobytes() for a, arr in outs}
 
-    def run(self):
+    def run(self, entries=None):
         """{entry point: {case: record}}; with a context the valid row also carries "host_equals_device" """
         real = self.ctx is not None
         table = {}
-        for name, args, listed in ENTRIES:
+        for name, args, listed in (ENTRIES if entries is None else entries):
             rows = {}
             for label, broken, only in _cases(args, listed):
                 if real and only == NULL_ONLY:
@@ -331,7 +349,7 @@ class Probe:
         return table
 
 
-def probe(lib_path, real):
+def probe(lib_path, real, entries=None):
     lib = bind(lib_path)
     ctx = None
     if real:
@@ -339,7 +357,7 @@ def probe(lib_path, real):
         rc = lib.nxsig_ctx_create(0, C.byref(ctx))
         assert rc == 0, lib.nxsig_last_error()
     try:
-        return Probe(lib, ctx).run()
+        return Probe(lib, ctx).run(entries)
     finally:
         if real:
             lib.nxsig_ctx_destroy(ctx)
@@ -350,9 +368,10 @@ def main():
     ap.add_argument("--lib", default=_lib.LIB_PATH)
     ap.add_argument("--real", action="store_true", help="use a context on device 0 (needs the GPU) instead of ctx = NULL")
     ap.add_argument("--write", metavar="JSON", default=None, help="merge the table into this golden file (default: print it)")
+    ap.add_argument("--own", action="store_true", help="the entry points of OWN_TABLE_ENTRIES instead of the recorded table's")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real)
+    table = probe(a.lib, a.real, OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
