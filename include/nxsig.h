@@ -113,7 +113,11 @@ const char* nxsig_last_error(void); /* thread-local, valid until the next call o
  * valid until the next compute call on this thread; "" before the first one.  Diagnostic only: nothing in the library reads it. */
 const char* nxsig_last_dispatch(void);
 /* the same record of the last compute call made on THIS CONTEXT by any thread, copied into buf (truncated to buflen - 1 characters): what a
- * host whose calls hop between threads (the BEAM's dirty schedulers) reads */
+ * host whose calls hop between threads (the BEAM's dirty schedulers) reads.
+ * A GROUP MEMBER's context (nxsig_group_ctx): after a *_sharded call the record names the families the member's OWN part of that call ran
+ * on — the record of the compute entry point the group called on it — and is "" for a member whose part was empty (more members than
+ * rows).  The helper passes the group itself adds afterwards (the row poisoning of sample-sharded FIR, the clamp of the sharded log-mel)
+ * are not noted.  The thread-local record after a *_sharded call is that of the last member the calling thread served: read the members'. */
 int nxsig_ctx_last_dispatch(nxsig_ctx* ctx, char* buf, size_t buflen);
 /* human readable device line ("AMD Instinct MI355X gfx950 256 CUs") into buf */
 int nxsig_device_name(nxsig_ctx* ctx, char* buf, size_t buflen);

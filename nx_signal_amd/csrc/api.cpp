@@ -50,6 +50,11 @@ struct DispatchScope {
   explicit DispatchScope(Ctx* ctx) : c(ctx) { dispatch_reset(); }
   ~DispatchScope() { c->last_dispatch = g_dispatch; }
 };
+void dispatch_member_begin(Ctx* c) {
+  std::lock_guard<std::mutex> lock(c->mu);
+  dispatch_reset();
+  c->last_dispatch.clear();
+}
 
 // In-process cache key (never persisted): FNV-1a over the tail bytes, and for the bulk four independent multiply-xor lanes over
 // 8-byte words — a byte-at-a-time FNV costs one dependent multiply per byte, 0.7 ms for the 512 KB mel filterbank that
@@ -417,9 +422,10 @@ struct DeviceGuard {
     ok = (hipSetDevice(c->device) == hipSuccess);
     // bound the content-addressed table cache.  Done at API entry only, never while a call holds table pointers, and never
     // while the stream is being captured (a captured graph bakes table pointers in).  A graph captured EARLIER stays valid as
-    // long as its context sees fewer than 1024 distinct tables afterwards; beyond that re-capture it (streams).
+    // long as its context sees fewer than 1024 (NXSIG_TABLE_CACHE_MAX) distinct tables afterwards; beyond that re-capture it
+    // (DESIGN.md section 3.0).  Every cache of pointers into `tables` is dropped with it: DESIGN.md lists them next to that sentence.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (ok && c->tables.size() > 1024 && hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
+    if (ok && c->tables.size() > (size_t)tune(c, kT_TABLE_CACHE_MAX, kTableCacheMax) && hipStreamIsCapturing(c->stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
       (void)hipStreamSynchronize(c->stream);
       for (auto& kv : c->tables) (void)hipFree(kv.second.ptr);
       c->tables.clear();
@@ -459,7 +465,9 @@ struct Staged {
     unsigned hw = std::thread::hardware_concurrency();
     const int knob = tune(c, kT_HOST_PIPE, 0);   // >= 2: that many copy threads (sweeps)
     const unsigned T = knob >= 2 ? (unsigned)knob : (hw >= 16 ? kCopyThreads : (hw >= 4 ? 2 : 1));
-    const size_t per = ((bytes / T) + 4095) & ~(size_t)4095;
+    // whole pages per thread, ROUNDED UP from bytes / T: rounded down, a chunk shorter than T bytes had per = 0 and was not copied at
+    // all, and one whose bytes / T is a whole number of pages lost its last bytes % T bytes (32 MiB + 4 bytes of f32: the last sample)
+    const size_t per = (((bytes + T - 1) / T) + 4095) & ~(size_t)4095;
     std::vector<std::thread> th;
     for (unsigned t = 1; t < T; ++t) {
       const size_t o = (size_t)t * per;
@@ -491,7 +499,10 @@ struct Staged {
     for (size_t off = 0; off < bytes; off += kPinChunk, ++k) {
       const size_t len = bytes - off < kPinChunk ? bytes - off : kPinChunk;
       const int sl = 2 + (k & 1);
-      if (k >= 2) NXSIG_HIP_TRY(hipEventSynchronize(c->xfer_ev[sl]));   // the DMA that last read this slot is done
+      // the DMA that last read this slot is done — whichever in() queued it: a call's SECOND host operand starts at k = 0 again while
+      // the first operand's last chunk may still be on its way out of the same slot (waiting only from k = 2 on let the host copy below
+      // overwrite it).  An event nothing was recorded on yet counts as complete.
+      NXSIG_HIP_TRY(hipEventSynchronize(c->xfer_ev[sl]));
       parallel_memcpy(static_cast<char*>(c->pin[sl]), h + off, len);
       NXSIG_HIP_TRY(hipMemcpyAsync(dd + off, c->pin[sl], len, hipMemcpyHostToDevice, c->xfer_stream));
       NXSIG_HIP_TRY(hipEventRecord(c->xfer_ev[sl], c->xfer_stream));
@@ -686,6 +697,7 @@ static bool tuning_in_range(int k, long v, long* lo, long* hi) {
     case kT_FFT_TILED_MIN: a = 2; break;
     case kT_STORE_POLICY: a = 0; b = 2; break;
     case kT_FIR_R2K: a = 0; b = 2; break;
+    case kT_TABLE_CACHE_MAX: a = 1; b = 1 << 20; break;       // tables a context keeps before the trim of DeviceGuard
     default: break;
   }
   if (lo) *lo = a;

@@ -672,6 +672,7 @@ int run_sharded(Group* g, const Plan& pl, const void* const* x, int64_t batch_st
     for (size_t i = 0; i < nl; ++i) {
       const Part& p = pl.part[g->m[i].rank];
       send[i] = nullptr;
+      dispatch_member_begin(reinterpret_cast<Ctx*>(g->m[i].ctx));   // the member's record: this call's part, "" when it has none
       if (!out[i] || (!x[i] && p.rows > 0 && p.out_len > 0)) { note(set_error(NXSIG_ERR_INVALID_ARG, "sharded: null shard pointer")); continue; }
       char* dst = static_cast<char*>(out[i]);
       if (by_row_segments) {
@@ -740,6 +741,7 @@ int run_sharded(Group* g, const Plan& pl, const void* const* x, int64_t batch_st
     auto fail = [&](int code) { rcs[i] = code; msgs[i] = nxsig_last_error(); };
     int r;
     const int64_t shard_bytes = pl.count[mb.rank];
+    dispatch_member_begin(reinterpret_cast<Ctx*>(mb.ctx));   // the member's record: this call's part, "" when it has none
     if ((r = nxsig_alloc(mb.ctx, (size_t)(gather ? full_bytes : shard_bytes), &dout[i]))) return fail(r);
     char* dst = static_cast<char*>(dout[i]);
     if (by_row_segments) {   // the dense shard; the full buffer receives it row by row (assemble_rows_locked)
@@ -1097,6 +1099,7 @@ int nxsig_stft_mel_sharded_f32(nxsig_group* grp, const float* const* x, int64_t 
     }
     q.count = q.rows * q.frames * mel_bins;
     Ctx* c = reinterpret_cast<Ctx*>(mb.ctx);
+    dispatch_member_begin(c);   // the member's record: this call's part, "" when it has none
     NXSIG_HIP_TRY(hipSetDevice(mb.device));
     if (q.count == 0) {  // an empty shard still takes part in the reduction: identity elements
       std::lock_guard<std::mutex> cl(c->mu);

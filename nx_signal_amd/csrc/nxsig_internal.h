@@ -26,6 +26,11 @@ const char* last_error_cstr();
 void dispatch_reset();
 void dispatch_note(const char* family);
 const char* dispatch_cstr();
+struct Ctx;
+// group.cpp, where a member's part of a sharded call starts: empties the calling thread's record AND the member context's copy.  The
+// compute entry point the group then calls on the member fills both again; a member whose part is empty keeps the empty record
+// instead of whatever ran on its context before (include/nxsig.h, nxsig_ctx_last_dispatch).
+void dispatch_member_begin(Ctx* c);
 
 #define NXSIG_HIP_TRY(expr)                                                                          \
   do {                                                                                               \
@@ -90,7 +95,8 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(STORE_POLICY) X(WAVE_NO_SPLIT) X(NO_AL8) X(NO_STAGE) X(WAVE_UNITS_PER_WAVE) X(STAGE_PAD) X(NO_HOP4) X(WAVE_SMALL_W) X(WAVE_SMALL_CHUNK) \
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
-  X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS)
+  X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
+  X(TABLE_CACHE_MAX)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -144,6 +150,10 @@ enum ScratchSlot : int {
 };
 
 // ---- device tables cached per context ----
+// The content-addressed cache (Ctx::tables) is bounded by COUNT: once a context holds more tables than this, the next API entry frees
+// them all and forgets every pointer into them (DeviceGuard, api.cpp; DESIGN.md lists those pointer caches).  NXSIG_TABLE_CACHE_MAX
+// overrides the bound of one context (tests cross it with a few dozen tables).
+constexpr int kTableCacheMax = 1024;
 struct DeviceTable {
   void* ptr = nullptr;
   size_t bytes = 0;
