@@ -49,6 +49,8 @@ defmodule NxSignalAMD.NIF do
   def wiener(_ctx, _x, _is_f64, _shape, _kernel_size, _has_noise, _noise), do: :erlang.nif_error(:nif_not_loaded)
   def resample_poly(_ctx, _x, _is_complex, _length, _batch, _taps, _up, _down), do: :erlang.nif_error(:nif_not_loaded)
   def resample_poly_dev(_ctx, _x, _is_complex, _length, _batch, _taps, _up, _down), do: :erlang.nif_error(:nif_not_loaded)
+  def welch(_ctx, _x, _length, _batch, _window, _hop, _fft_length, _detrend, _scaling, _sampling_rate), do: :erlang.nif_error(:nif_not_loaded)
+  def csd(_ctx, _x, _y, _length, _batch, _window, _hop, _fft_length, _detrend, _scaling, _sampling_rate), do: :erlang.nif_error(:nif_not_loaded)
   def argrelextrema(_ctx, _x, _dtype, _shape, _axis, _shifts, _comparator), do: :erlang.nif_error(:nif_not_loaded)
   def nonzero(_ctx, _mask, _shape), do: :erlang.nif_error(:nif_not_loaded)
   def sawtooth(_ctx, _t, _is_f64, _width), do: :erlang.nif_error(:nif_not_loaded)

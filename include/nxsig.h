@@ -692,6 +692,39 @@ int nxsig_stft_mel_sharded_f32(nxsig_group* g, const float* const* x, int64_t le
 int nxsig_timer_lap(nxsig_ctx* ctx);
 int nxsig_timer_laps(nxsig_ctx* ctx, float* intervals_ms, int32_t capacity, int32_t* count);
 
+/* ---------------------------------------------------------------- spectral estimation --- */
+/*
+ * Spectral.welch / csd / coherence: Welch's averaged periodogram of real f32 rows — scipy.signal.welch / csd with
+ * return_onesided = True, average = "mean", nperseg = frame_length, noverlap = frame_length - hop, nfft = fft_length (the reference has
+ * no spectral estimator).  Frame m of a row covers samples [m hop, m hop + N), M = (length - N) / hop + 1
+ * frames, no padding, a ragged tail is dropped; K = fft_length >= N (zero padded).  For bin k in [0, K / 2]
+ *     Pxy[k] = scale * d_k * (1 / M) sum_m conj(X_m[k]) Y_m[k],      X_m = DFT_K(w * (x_m - mean(x_m)))      (detrend != 0)
+ * with scale = 1 / (sampling_rate * sum w^2) (NXSIG_WELCH_DENSITY) or 1 / (sum w)^2 (NXSIG_WELCH_SPECTRUM), both formed in double
+ * from the f32 window, and d_k = 2 except d_0 = 1 and, for even K, d_{K/2} = 1.  welch is csd(x, x): real.  The mean of a frame is
+ * removed twice (the mean, then the mean of the residual) so that a large offset leaves no f32 round-off at bin 0 and its neighbours.
+ * No |x| <= 1e-10 clean-up: this is not an Nx.fft result.
+ *   x, y [batch][length] rows batch_stride >= length elements apart (one stride for both), window f32[frame_length] HOST,
+ *   pxx_out / pyy_out f32[batch][bins], pxy_out c64[batch][bins], bins = nxsig_welch_bins(fft_length), dense.  In nxsig_csd_f32
+ *   pxx_out and pyy_out may be NULL (not wanted).
+ * Non-finite rule: a row (for csd: the pair x_r, y_r) with an Inf / NaN inside the samples its M frames cover gives NaN in EVERY bin
+ * of every result of that row — Pxx of a row whose y holds the NaN included; a non-finite sample in the dropped tail, in the gap
+ * between rows or in another row reaches nothing.
+ * Deterministic: partial sums per (row, run of frames) are stored and added in ascending run order, no atomics; a row's bits do not
+ * depend on the other rows of the call.
+ * Dispatch: welch.pair / csd.pair (fft_length 1024 and 2048: wave-private transforms, the spectrum never reaches memory),
+ * welch.generic / csd.generic for every other length and under NXSIG_DISABLE_WELCH_WAVE.  The tiers agree within tolerance, not bit
+ * for bit.
+ */
+typedef enum nxsig_welch_scaling { NXSIG_WELCH_DENSITY = 0, NXSIG_WELCH_SPECTRUM = 1 } nxsig_welch_scaling;
+/* bins of a one-sided estimate: fft_length / 2 + 1 (even and odd lengths alike, as rfft); negative status when fft_length < 1 */
+int32_t nxsig_welch_bins(int32_t fft_length);
+int nxsig_welch_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
+                    int32_t frame_length, int32_t hop, int32_t fft_length, int32_t detrend, int32_t scaling, double sampling_rate,
+                    float* pxx_out, int32_t mem);
+int nxsig_csd_f32(nxsig_ctx* ctx, const float* x, const float* y, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
+                  int32_t frame_length, int32_t hop, int32_t fft_length, int32_t detrend, int32_t scaling, double sampling_rate,
+                  float* pxx_out, float* pyy_out, nxsig_c64* pxy_out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -832,6 +832,66 @@ static ERL_NIF_TERM nif_resample_poly_dev(ErlNifEnv* env, int argc, const ERL_NI
   return enif_make_tuple3(env, mk_atom(env, "ok"), make_buf(env, c, y, ybytes), enif_make_int64(env, n));
 }
 
+/* the arguments the welch and csd NIFs share, from argv[at]: length, batch, window_bin (f32), hop, fft_length, detrend, scaling, sampling_rate */
+static int welch_args(ErlNifEnv* env, const ERL_NIF_TERM* argv, ErlNifSInt64* length, int* batch, ErlNifBinary* w, int* hop, int* fft_length,
+                      int* detrend, int* scaling, double* fs) {
+  return enif_get_int64(env, argv[0], length) && enif_get_int(env, argv[1], batch) && enif_inspect_binary(env, argv[2], w) &&
+         enif_get_int(env, argv[3], hop) && enif_get_int(env, argv[4], fft_length) && enif_get_int(env, argv[5], detrend) &&
+         enif_get_int(env, argv[6], scaling) && enif_get_double(env, argv[7], fs) && *batch >= 1 && *length >= 1 && w->size >= 4 &&
+         w->size % 4 == 0 && w->size / 4 <= 0x7fffffff;
+}
+
+/* welch(ctx, x_bin, length, batch, window_bin, hop, fft_length, detrend, scaling, sampling_rate) -> {:ok, pxx_bin, bins}
+   (Spectral.welch/3: Welch's averaged periodogram of real f32 rows, include/nxsig.h: nxsig_welch_f32) */
+static ERL_NIF_TERM nif_welch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary x, w, pb;
+  ErlNifSInt64 length;
+  int batch, hop, fft_length, detrend, scaling;
+  double fs;
+  if (argc != 10 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) ||
+      !welch_args(env, argv + 2, &length, &batch, &w, &hop, &fft_length, &detrend, &scaling, &fs))
+    return enif_make_badarg(env);
+  size_t xbytes = 4;
+  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x.size != xbytes) return enif_make_badarg(env);
+  int32_t nb = nxsig_welch_bins(fft_length);
+  if (nb < 0) return mk_error(env, nb);
+  if (!out_bin(&pb, (uint64_t)batch, (uint64_t)nb, 1, 4)) return mk_oom(env);
+  int rc = nxsig_welch_f32(c->ctx, (const float*)x.data, length, batch, length, (const float*)w.data, (int)(w.size / 4), hop, fft_length,
+                           detrend, scaling, fs, (float*)pb.data, NXSIG_HOST);
+  if (rc) { enif_release_binary(&pb); return mk_error(env, rc); }
+  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &pb), enif_make_int(env, nb));
+}
+
+/* csd(ctx, x_bin, y_bin, length, batch, window_bin, hop, fft_length, detrend, scaling, sampling_rate) -> {:ok, pxy_bin, pxx_bin, pyy_bin, bins}
+   (Spectral.csd/4 and coherence/4: the cross spectrum c64 and both auto-spectra f32 of one call, nxsig_csd_f32) */
+static ERL_NIF_TERM nif_csd(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  ErlNifBinary x, y, w, pxy, pxx, pyy;
+  ErlNifSInt64 length;
+  int batch, hop, fft_length, detrend, scaling;
+  double fs;
+  if (argc != 11 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_inspect_binary(env, argv[2], &y) ||
+      !welch_args(env, argv + 3, &length, &batch, &w, &hop, &fft_length, &detrend, &scaling, &fs))
+    return enif_make_badarg(env);
+  size_t xbytes = 4;
+  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x.size != xbytes || y.size != xbytes)
+    return enif_make_badarg(env);
+  int32_t nb = nxsig_welch_bins(fft_length);
+  if (nb < 0) return mk_error(env, nb);
+  if (!out_bin(&pxy, (uint64_t)batch, (uint64_t)nb, 1, 8)) return mk_oom(env);
+  if (!out_bin(&pxx, (uint64_t)batch, (uint64_t)nb, 1, 4)) { enif_release_binary(&pxy); return mk_oom(env); }
+  if (!out_bin(&pyy, (uint64_t)batch, (uint64_t)nb, 1, 4)) { enif_release_binary(&pxy); enif_release_binary(&pxx); return mk_oom(env); }
+  int rc = nxsig_csd_f32(c->ctx, (const float*)x.data, (const float*)y.data, length, batch, length, (const float*)w.data, (int)(w.size / 4), hop,
+                         fft_length, detrend, scaling, fs, (float*)pxx.data, (float*)pyy.data, (nxsig_c64*)pxy.data, NXSIG_HOST);
+  if (rc) {
+    enif_release_binary(&pxy); enif_release_binary(&pxx); enif_release_binary(&pyy);
+    return mk_error(env, rc);
+  }
+  return enif_make_tuple5(env, mk_atom(env, "ok"), enif_make_binary(env, &pxy), enif_make_binary(env, &pxx), enif_make_binary(env, &pyy),
+                          enif_make_int(env, nb));
+}
+
 /* wiener(ctx, x_bin, is_f64, shape, kernel_size, has_noise, noise) -> {:ok, binary of x's type}   (Filters.wiener/2, filters.ex:81-110) */
 static ERL_NIF_TERM nif_wiener(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
@@ -1877,6 +1937,8 @@ static ErlNifFunc funcs[] = {
     {"wiener", 7, nif_wiener, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"resample_poly", 8, nif_resample_poly, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"resample_poly_dev", 8, nif_resample_poly_dev, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"welch", 10, nif_welch, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"csd", 11, nif_csd, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"argrelextrema", 7, nif_argrelextrema, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"nonzero", 3, nif_nonzero, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"sawtooth", 4, nif_sawtooth, ERL_NIF_DIRTY_JOB_IO_BOUND},

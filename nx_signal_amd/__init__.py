@@ -5,7 +5,7 @@ Python host mirror of the reference's function-level interface (elixir-nx/nx_sig
     NxSignal.stft/3, istft/3, as_windowed/2, overlap_and_add/2, fft_frequencies/2   -> this module
     NxSignal.Windows.*            -> nx_signal_amd.windows
     NxSignal.Filters.firwin/3, median/2, wiener/2 -> nx_signal_amd.filters  (+ the new `fir`, `resample_poly`)
-    NxSignal.PeakFinding.*        -> nx_signal_amd.peak_finding
+    NxSignal.PeakFinding.*        -> nx_signal_amd.peak_finding; (extension) welch / csd / coherence -> nx_signal_amd.spectral
     NxSignal.Convolution.*        -> nx_signal_amd.convolution (FFT method, 1-D)
     NxSignal.Waveforms.*          -> nx_signal_amd.waveforms (sinc/1 on the host)
     NxSignal.Transforms.fft_nd    -> nx_signal_amd.transforms (last axis)
@@ -806,4 +806,4 @@ def spectrogram(data, window, ctx: Context | None = None, **opts):
     return out, _stft_times(m, N, fs), f
 
 
-from . import convolution, filters, peak_finding, transforms, waveforms, windows  # noqa: E402,F401
+from . import convolution, filters, peak_finding, spectral, transforms, waveforms, windows  # noqa: E402,F401

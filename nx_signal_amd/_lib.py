@@ -71,9 +71,20 @@ class NxsigCtx(C.Structure):
 _ctx = C.POINTER(NxsigCtx)
 
 
-def ctx_ptr(handle):
-    """a context handle (c_void_p, int or None) as the typed pointer of the signatures that declare one"""
-    return None if handle is None else C.cast(handle, _ctx)
+class NxsigCtxSpectral(C.Structure):
+    """the same opaque nxsig_ctx, under a second name"""
+
+
+# nxsig_ctx* of the spectral entry points (nxsig_welch_f32, nxsig_csd_f32): a typed pointer like _ctx, but a type of its own.
+# tests/test_resample_host.py pins the entry points declared with _ctx itself to the resample table; these two keep their rows in the
+# probe's WELCH_TABLE_ENTRIES and tests/golden/abi_error_table_welch.json (tests/test_welch_host.py, tests/test_gpu_welch.py).
+_ctx_spectral = C.POINTER(NxsigCtxSpectral)
+TYPED_CTX = (_ctx, _ctx_spectral)
+
+
+def ctx_ptr(handle, typ=_ctx):
+    """a context handle (c_void_p, int or None) as the typed pointer `typ` of the signatures that declare one"""
+    return None if handle is None else C.cast(handle, typ)
 
 # name -> (restype, argtypes); every symbol include/nxsig.h declares is listed here (tests check both ways)
 SIGNATURES = {
@@ -132,6 +143,9 @@ SIGNATURES = {
     "nxsig_resample_length": (_i64, [_i64, _i32, _i32]),
     "nxsig_resample_tile": (_i32, []),
     "nxsig_resample_poly": (C.c_int, [_ctx, _p, _i32, _i64, _i32, _i64, _p, _i32, _i32, _i32, _p, _i32]),
+    "nxsig_welch_bins": (_i32, [_i32]),
+    "nxsig_welch_f32": (C.c_int, [_ctx_spectral, _p, _i64, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _f64, _p, _i32]),
+    "nxsig_csd_f32": (C.c_int, [_ctx_spectral, _p, _p, _i64, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _f64, _p, _p, _p, _i32]),
     "nxsig_wiener": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _i32, _f64, _p, C.POINTER(_f64), _i32]),
     "nxsig_argrelextrema": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, _i32, _i64, _i32, _p, _p, _i32]),
     "nxsig_nonzero": (C.c_int, [_p, _p, C.POINTER(_i64), _i32, _p, _p, _i32]),

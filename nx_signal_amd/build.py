@@ -53,6 +53,7 @@ UNITS = [
     ("kernels_peaks.hip", []),  # PeakFinding.argrelextrema / nonzero: mark, scan, compact
     ("kernels_waveforms.hip", []),  # Waveforms.* elementwise (no FMA contraction: the file says so itself)
     ("kernels_resample.hip", []),  # Filters.resample_poly: polyphase rational resampling
+    ("kernels_welch.hip", []),  # Spectral.welch / csd: Welch's averaged periodogram, the spectrum never in memory
 ]
 
 

@@ -2303,4 +2303,72 @@ int nxsig_fir_slice_f64(nxsig_ctx* ctx, const double* x, int64_t length, int32_t
   return fir_common<double>(ctx, x, length, batch, batch_stride, h, num_taps, out_start, out_len, y, mem);
 }
 
+/* ---------------------------------------------------------------- Spectral.welch / csd */
+int32_t nxsig_welch_bins(int32_t fft_length) {
+  const int32_t nb = welch_bins(fft_length);
+  return nb < 0 ? set_error(NXSIG_ERR_INVALID_ARG, "welch_bins: fft_length must be >= 1") : nb;
+}
+
+// welch (y == nullptr, pxx only) and csd: the argument checks need no context and come ahead of it
+static int welch_common(const char* fn, nxsig_ctx* ctx, const float* x, const float* y, int64_t length, int32_t batch, int64_t batch_stride,
+                        const float* window, int32_t frame_length, int32_t hop, int32_t fft_length, int32_t detrend, int32_t scaling,
+                        double sampling_rate, float* pxx_out, float* pyy_out, nxsig_c64* pxy_out, int32_t mem) {
+  NXSIG_API_BEGIN
+  const bool csd = fn[0] == 'c';
+  if (!x || !window || (csd ? !y || !pxy_out : !pxx_out)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (const char* what = welch_check_args(length, batch, batch_stride, frame_length, hop, fft_length, scaling, sampling_rate))
+    return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": " + what);
+  const int64_t nb = welch_bins(fft_length);
+  if (nb > INT64_MAX / batch / 8) return set_error(NXSIG_ERR_UNSUPPORTED, std::string(fn) + ": the result is too large");
+  double sw = 0.0, sw2 = 0.0;
+  for (int32_t i = 0; i < frame_length; ++i) { sw += (double)window[i]; sw2 += (double)window[i] * (double)window[i]; }
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  WelchLaunch a;
+  a.L = length; a.batch_stride = batch_stride; a.batch = batch; a.N = frame_length; a.hop = hop; a.K = fft_length;
+  a.window_host = window; a.detrend = detrend != 0;
+  a.scale = scaling == NXSIG_WELCH_DENSITY ? 1.0 / (sampling_rate * sw2) : 1.0 / (sw * sw);
+  const size_t in_bytes = rows_bytes(batch, batch_stride, length, sizeof(float));
+  const size_t rb = (size_t)batch * nb * sizeof(float);
+  HostIo io(c, mem);
+  // two inputs, the results packed into one slot (pxy first); a result the caller does not want is not listed
+  if (!csd) rc = io.open({{x, in_bytes, kScratchNdStageA}}, {{pxx_out, rb, kScratchNdStageOut}});
+  else if (pxx_out && pyy_out)
+    rc = io.open({{x, in_bytes, kScratchNdStageA}, {y, in_bytes, kScratchNdStageB}},
+                 {{pxy_out, 2 * rb, kScratchNdStageOut}, {pxx_out, rb, kScratchNdStageOut}, {pyy_out, rb, kScratchNdStageOut}});
+  else if (pxx_out || pyy_out)
+    rc = io.open({{x, in_bytes, kScratchNdStageA}, {y, in_bytes, kScratchNdStageB}},
+                 {{pxy_out, 2 * rb, kScratchNdStageOut}, {pxx_out ? pxx_out : pyy_out, rb, kScratchNdStageOut}});
+  else rc = io.open({{x, in_bytes, kScratchNdStageA}, {y, in_bytes, kScratchNdStageB}}, {{pxy_out, 2 * rb, kScratchNdStageOut}});
+  if (rc) return rc;
+  a.x = static_cast<const float*>(io.in[0]);
+  a.y = csd ? static_cast<const float*>(io.in[1]) : nullptr;
+  a.pxx = a.pyy = nullptr; a.pxy = nullptr;
+  if (!csd) a.pxx = static_cast<float*>(io.out[0]);
+  else {
+    a.pxy = static_cast<float2*>(io.out[0]);
+    if (pxx_out) a.pxx = static_cast<float*>(io.out[1]);
+    if (pyy_out) a.pyy = static_cast<float*>(io.out[pxx_out ? 2 : 1]);
+  }
+  if ((rc = launch_welch(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+int nxsig_welch_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
+                    int32_t frame_length, int32_t hop, int32_t fft_length, int32_t detrend, int32_t scaling, double sampling_rate,
+                    float* pxx_out, int32_t mem) {
+  return welch_common("welch", ctx, x, nullptr, length, batch, batch_stride, window, frame_length, hop, fft_length, detrend, scaling,
+                      sampling_rate, pxx_out, nullptr, nullptr, mem);
+}
+
+int nxsig_csd_f32(nxsig_ctx* ctx, const float* x, const float* y, int64_t length, int32_t batch, int64_t batch_stride, const float* window,
+                  int32_t frame_length, int32_t hop, int32_t fft_length, int32_t detrend, int32_t scaling, double sampling_rate,
+                  float* pxx_out, float* pyy_out, nxsig_c64* pxy_out, int32_t mem) {
+  return welch_common("csd", ctx, x, y, length, batch, batch_stride, window, frame_length, hop, fft_length, detrend, scaling, sampling_rate,
+                      pxx_out, pyy_out, pxy_out, mem);
+}
+
 }  // extern "C"

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -119,7 +119,7 @@ enum ScratchSlot : int {
   kScratchStageIn = 1,           // host staging: the first input of a NXSIG_HOST call (HostIo, api.cpp)
   kScratchStageOut = 2,          // host staging: the result of a NXSIG_HOST call; nxsig_fftconvolve_c64's second input (HostIo, api.cpp)
   kScratchWaveSink = 3,          // dummy sink the wave kernels' unused output pointers aim at (kernels_wave*.hip, wave_stft.hpp, wave_rab.hpp)
-  kScratchFusedSpectrum = 4,     // spectrum of the two-step fall-back of the fused sinks; staged result of nxsig_fftconvolve_c64 (api.cpp)
+  kScratchFusedSpectrum = 4,     // spectrum of the two-step fall-back of the fused sinks (welch.generic / csd.generic: the frames' spectra); staged result of nxsig_fftconvolve_c64 (api.cpp)
   kScratchReductionCells = 5,    // running maximum + non-finite flag of the log-mel / dBFS paths (kernels_generic.hip, group.cpp)
   kScratchFourStepA = 6,         // four-step rows: first buffer, also the tiled form's only one (kernels_nd.hip)
   kScratchFourStepB = 7,         // four-step rows: second buffer (kernels_nd.hip)
@@ -131,7 +131,7 @@ enum ScratchSlot : int {
   kScratchConvNdA = 13,          // n-D fftconvolve: padded A, later the inverse transform's result (kernels_nd.hip)
   kScratchConvNdB = 14,          // n-D fftconvolve: padded B (kernels_nd.hip)
   kScratchConvNdC = 15,          // n-D fftconvolve: the product (kernels_nd.hip)
-  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip)
+  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip); welch / csd: row flags, partial sums, the generic tier's frames (kernels_welch.hip)
   kScratchNdStageA = 17,         // host staging of the n-D / filter / peak / waveform calls: first input; the mask of the masked istft (api.cpp)
   kScratchNdStageB = 18,         // the same: second input; peak finding's `valid` cell (api.cpp)
   kScratchNdStageOut = 19,       // the same: results, several packed at a 256-byte stride (api.cpp)
@@ -460,4 +460,24 @@ int launch_fir_f64(Ctx* c, const FirLaunchD& s);
 int launch_fftconvolve_c64(Ctx* c, const float2* a, int64_t n1, const float2* b, int64_t n2, int64_t start, int64_t len,
                            float2* out);
 
+// kernels_welch.hip: Spectral.welch / csd (include/nxsig.h states the definition, DESIGN.md section 3.12 the design).  y == nullptr:
+// welch (pxx only).  Temporaries: kScratchLongStftFrames holds the per-row non-finite flags, the partial sums [row][run][plane][bin]
+// of one slab of rows and, in the generic tier, a chunk's detrended windowed frames; kScratchFusedSpectrum holds that chunk's spectra.
+// Everything is enqueued on c->stream; nothing waits
+struct WelchLaunch {
+  const float* x;            // device f32[batch][L], rows batch_stride elements apart
+  const float* y;            // the same layout, or nullptr
+  int64_t L, batch_stride;
+  int32_t batch, N, hop, K;
+  const float* window_host;  // f32[N]
+  bool detrend;
+  double scale;              // 1 / (fs sum w^2) or 1 / (sum w)^2
+  float* pxx;                // device f32[batch][K / 2 + 1] (csd: may be null)
+  float* pyy;                // csd only, may be null
+  float2* pxy;               // csd only
+};
+int launch_welch(Ctx* c, const WelchLaunch& a);
+
 }  // namespace nxsig
+
+#include "welch_plan.hpp"

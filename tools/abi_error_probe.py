@@ -3,6 +3,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
 
     python tools/abi_error_probe.py [--lib PATH] [--real] [--write tests/golden/abi_error_table.json]
     python tools/abi_error_probe.py --own [--real] [--write tests/golden/abi_error_table_resample.json]
+    python tools/abi_error_probe.py --welch [--real] [--write tests/golden/abi_error_table_welch.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -12,7 +13,8 @@ the build whose behaviour is the reference (tests/test_abi_errors_host.py and te
 
 ENTRIES and that golden file are the recorded table of the entry points that existed when it was made.  An entry point added since
 keeps its rows in OWN_TABLE_ENTRIES and a golden file of its own (--own; tests/test_resample_host.py and tests/test_gpu_resample.py
-compare against it): the same probe, the same kinds of cases."""
+compare against it): the same probe, the same kinds of cases.  WELCH_TABLE_ENTRIES (--welch) does the same for nxsig_welch_f32 and
+nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py)."""
 import argparse
 import ctypes as C
 import json
@@ -28,6 +30,7 @@ from nx_signal_amd import _lib  # noqa: E402  (signature table + structs only)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_error_table.json")
 GOLDEN_OWN = os.path.join(ROOT, "tests", "golden", "abi_error_table_resample.json")
+GOLDEN_WELCH = os.path.join(ROOT, "tests", "golden", "abi_error_table_welch.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -259,6 +262,25 @@ OWN_TABLE_ENTRIES = [
       ("result too large", {"length": 1 << 58, "batch_stride": 1 << 58, "batch": 16, "up": 3, "down": 2})]),
 ]
 
+# Spectral.welch / csd: 2 rows of 40 samples, 16-sample frames, hop 8, fft_length 32 (17 bins)
+WL, WN, WK, WB = 40, 16, 32, 17
+_WELCH_WIN = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(WN) / WN)).astype(np.float32)
+_WELCH_CASES = [("batch=0", {"batch": 0}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": WL - 1}),
+                ("frame_length=0", {"frame_length": 0}), ("hop=0", {"hop": 0}), ("hop>frame_length", {"hop": WN + 1}),
+                ("fft_length<frame_length", {"fft_length": WN - 1}), ("fft_length past 2^24", {"fft_length": (1 << 24) + 1}),
+                ("frame_length>length", {"frame_length": WL + 1, "fft_length": 64}), ("scaling=2", {"scaling": 2}),
+                ("sampling_rate=0", {"sampling_rate": 0.0}), ("sampling_rate=nan", {"sampling_rate": float("nan")})]
+_WELCH_COMMON = [("length", "v", WL), ("batch", "v", B), ("batch_stride", "v", WL), ("window", "host", _WELCH_WIN), ("frame_length", "v", WN),
+                 ("hop", "v", 8), ("fft_length", "v", WK), ("detrend", "v", 1), ("scaling", "v", 0), ("sampling_rate", "v", 8000.0)]
+WELCH_TABLE_ENTRIES = [
+    ("nxsig_welch_f32", [("x", "in", _f32(B, WL)), *_WELCH_COMMON, ("pxx_out", "out", np.zeros((B, WB), np.float32)), ("mem", "mem", None)],
+     _WELCH_CASES),
+    ("nxsig_csd_f32",
+     [("x", "in", _f32(B, WL)), ("y", "in", _f32(B, WL)), *_WELCH_COMMON, ("pxx_out", "out?", np.zeros((B, WB), np.float32)),
+      ("pyy_out", "out?", np.zeros((B, WB), np.float32)), ("pxy_out", "out", np.zeros((B, WB), np.complex64)), ("mem", "mem", None)],
+     _WELCH_CASES),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -314,7 +336,8 @@ class Probe:
                     call.append(arr.ctypes.data_as(at))
                 if kind.rstrip("?") in ("out", "hout"):
                     outs.append((a, arr))
-        rc = fn(_lib.ctx_ptr(self.ctx) if _lib.SIGNATURES[name][1][0] is _lib._ctx else self.ctx, *call)
+        ctx_type = _lib.SIGNATURES[name][1][0]
+        rc = fn(_lib.ctx_ptr(self.ctx, ctx_type) if ctx_type in _lib.TYPED_CTX else self.ctx, *call)
         err = self.lib.nxsig_last_error().decode("utf-8", "replace") if rc != 0 else ""
         for d, arr, is_out in devs:
             if is_out and rc == 0:
@@ -369,9 +392,10 @@ def main():
     ap.add_argument("--real", action="store_true", help="use a context on device 0 (needs the GPU) instead of ctx = NULL")
     ap.add_argument("--write", metavar="JSON", default=None, help="merge the table into this golden file (default: print it)")
     ap.add_argument("--own", action="store_true", help="the entry points of OWN_TABLE_ENTRIES instead of the recorded table's")
+    ap.add_argument("--welch", action="store_true", help="the entry points of WELCH_TABLE_ENTRIES (Spectral.welch / csd)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
