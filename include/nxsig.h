@@ -725,6 +725,43 @@ int nxsig_csd_f32(nxsig_ctx* ctx, const float* x, const float* y, int64_t length
                   int32_t frame_length, int32_t hop, int32_t fft_length, int32_t detrend, int32_t scaling, double sampling_rate,
                   float* pxx_out, float* pyy_out, nxsig_c64* pxy_out, int32_t mem);
 
+/* ---------------------------------------------------------------- recursive filters --- */
+/*
+ * Filters.sosfilt / sosfilt_zi / sosfiltfilt: cascades of second-order sections over real f32 rows — scipy.signal 1.15's definition
+ * (the reference has no recursive filter).  sos is f64[n_sections][6] = b0 b1 b2 a0 a1 a2 per section with
+ * a0 == 1, always a HOST pointer.  Each section runs in transposed direct form II on its predecessor's output,
+ *     y = b0 x + z0;   z0 = b1 x - a1 y + z1;   z1 = b2 x - a2 y
+ * and (z0, z1) per section is scipy's state.  Coefficients, states and the recurrence are double on the device; a sample is widened
+ * on load and an output rounded to f32 once.
+ *   x [batch][length] rows batch_stride >= length elements apart, y f32[batch][length] dense; x and y must not overlap.
+ *   zi   f64[zi_rows][n_sections][2] HOST or NULL (zero state); zi_rows is 1 (every row starts alike) or batch; a call that brings it
+ *        synchronises (it is uploaded through scratch, never cached: feeding zf back as zi block after block keeps no table)
+ *   zf_out f64[batch][n_sections][2] HOST or NULL: the states after the last sample; a call that asks for it synchronises
+ *   direction 0: samples in order; 1: the same filter run from the end of each row towards its start (y[i] still belongs to x[i])
+ *   n_sections 1 .. 16; more returns NXSIG_ERR_UNSUPPORTED (run the cascade in groups)
+ * nxsig_sosfiltfilt_f32: scipy.signal.sosfiltfilt in one call, device resident: each row is extended by `edge` samples per side
+ * (padlen < 0: scipy's default 3 * (2 n_sections + 1 - min(#(b2 == 0), #(a2 == 0))); NXSIG_SOS_PAD_NONE: 0), filtered forward from
+ * the state sosfilt_zi * x_ext[0], filtered backward from sosfilt_zi * y_fwd[last], and the middle `length` samples are kept.  The
+ * extension and the forward result are f32 rows.  padlen >= length is an error, worded as scipy's.
+ * Non-finite rule: outputs ahead of the first Inf / NaN sample of a row are bit for bit those of the row with that sample and
+ * everything after it zeroed; every output from it on is non-finite.  Other rows and the gaps between strided rows are untouched.
+ * A zi row with a non-finite entry counts as a non-finite sample 0.  Under sosfiltfilt such a row is non-finite everywhere.
+ * Deterministic: no atomics, one order of additions; chunk and tile depend on n_sections only, a row's bits do not depend on the
+ * batch.  Dispatch: sosfilt.scan (a time-parallel scan: chunks of nxsig_sosfilt_chunk samples per lane, tiles of nxsig_sosfilt_tile
+ * samples per workgroup), sosfilt.generic (one lane per row) for rows of at most one chunk and under NXSIG_DISABLE_SOSFILT_SCAN.  The
+ * tiers agree within tolerance, not bit for bit.
+ */
+typedef enum nxsig_sos_padtype { NXSIG_SOS_PAD_NONE = 0, NXSIG_SOS_PAD_ODD = 1, NXSIG_SOS_PAD_EVEN = 2, NXSIG_SOS_PAD_CONSTANT = 3 } nxsig_sos_padtype;
+/* samples per lane / per workgroup tile of sosfilt.scan for a cascade of n_sections (1 .. 16); negative status otherwise */
+int32_t nxsig_sosfilt_chunk(int32_t n_sections);
+int32_t nxsig_sosfilt_tile(int32_t n_sections);
+/* scipy.signal.sosfilt_zi: the state of a settled step response, f64[n_sections][2]; host only */
+int nxsig_sosfilt_zi(const double* sos, int32_t n_sections, double* zi_out);
+int nxsig_sosfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* sos,
+                      int32_t n_sections, const double* zi, int32_t zi_rows, double* zf_out, int32_t direction, float* y, int32_t mem);
+int nxsig_sosfiltfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* sos,
+                          int32_t n_sections, int32_t padtype, int64_t padlen, float* y, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ Python host mirror of the reference's function-level interface (elixir-nx/nx_sig
 
     NxSignal.stft/3, istft/3, as_windowed/2, overlap_and_add/2, fft_frequencies/2   -> this module
     NxSignal.Windows.*            -> nx_signal_amd.windows
-    NxSignal.Filters.firwin/3, median/2, wiener/2 -> nx_signal_amd.filters  (+ the new `fir`, `resample_poly`)
+    NxSignal.Filters.firwin/3, median/2, wiener/2 -> nx_signal_amd.filters  (+ the new `fir`, `resample_poly`, `sosfilt`, `sosfilt_zi`, `sosfiltfilt`)
     NxSignal.PeakFinding.*        -> nx_signal_amd.peak_finding; (extension) welch / csd / coherence -> nx_signal_amd.spectral
     NxSignal.Convolution.*        -> nx_signal_amd.convolution (FFT method, 1-D)
     NxSignal.Waveforms.*          -> nx_signal_amd.waveforms (sinc/1 on the host)

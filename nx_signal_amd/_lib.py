@@ -79,7 +79,17 @@ class NxsigCtxSpectral(C.Structure):
 # tests/test_resample_host.py pins the entry points declared with _ctx itself to the resample table; these two keep their rows in the
 # probe's WELCH_TABLE_ENTRIES and tests/golden/abi_error_table_welch.json (tests/test_welch_host.py, tests/test_gpu_welch.py).
 _ctx_spectral = C.POINTER(NxsigCtxSpectral)
-TYPED_CTX = (_ctx, _ctx_spectral)
+
+
+class NxsigCtxIir(C.Structure):
+    """the same opaque nxsig_ctx, under a third name"""
+
+
+# nxsig_ctx* of the recursive filters (nxsig_sosfilt_f32, nxsig_sosfiltfilt_f32): the welch host test pins the entry points declared
+# with _ctx_spectral to its table in turn, so these two keep their rows in the probe's IIR_TABLE_ENTRIES and
+# tests/golden/abi_error_table_iir.json (tests/test_iir_host.py, tests/test_gpu_iir.py).
+_ctx_iir = C.POINTER(NxsigCtxIir)
+TYPED_CTX = (_ctx, _ctx_spectral, _ctx_iir)
 
 
 def ctx_ptr(handle, typ=_ctx):
@@ -146,6 +156,11 @@ SIGNATURES = {
     "nxsig_welch_bins": (_i32, [_i32]),
     "nxsig_welch_f32": (C.c_int, [_ctx_spectral, _p, _i64, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _f64, _p, _i32]),
     "nxsig_csd_f32": (C.c_int, [_ctx_spectral, _p, _p, _i64, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _f64, _p, _p, _p, _i32]),
+    "nxsig_sosfilt_chunk": (_i32, [_i32]),
+    "nxsig_sosfilt_tile": (_i32, [_i32]),
+    "nxsig_sosfilt_zi": (C.c_int, [C.POINTER(_f64), _i32, C.POINTER(_f64)]),   # host only: no tensor operand, no context
+    "nxsig_sosfilt_f32": (C.c_int, [_ctx_iir, _p, _i64, _i32, _i64, _p, _i32, _p, _i32, _p, _i32, _p, _i32]),
+    "nxsig_sosfiltfilt_f32": (C.c_int, [_ctx_iir, _p, _i64, _i32, _i64, _p, _i32, _i32, _i64, _p, _i32]),
     "nxsig_wiener": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _i32, _f64, _p, C.POINTER(_f64), _i32]),
     "nxsig_argrelextrema": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, _i32, _i64, _i32, _p, _p, _i32]),
     "nxsig_nonzero": (C.c_int, [_p, _p, C.POINTER(_i64), _i32, _p, _p, _i32]),

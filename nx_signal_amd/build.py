@@ -54,6 +54,7 @@ UNITS = [
     ("kernels_waveforms.hip", []),  # Waveforms.* elementwise (no FMA contraction: the file says so itself)
     ("kernels_resample.hip", []),  # Filters.resample_poly: polyphase rational resampling
     ("kernels_welch.hip", []),  # Spectral.welch / csd: Welch's averaged periodogram, the spectrum never in memory
+    ("kernels_iir.hip", []),  # Filters.sosfilt / sosfiltfilt: biquad cascades in double, an exact scan over time
 ]
 
 

@@ -2371,4 +2371,87 @@ int nxsig_csd_f32(nxsig_ctx* ctx, const float* x, const float* y, int64_t length
                       pxx_out, pyy_out, pxy_out, mem);
 }
 
+/* ---------------------------------------------------------------- Filters.sosfilt / sosfiltfilt */
+int32_t nxsig_sosfilt_chunk(int32_t n_sections) {
+  const int32_t v = iir_chunk(n_sections);
+  return v ? v : set_error(NXSIG_ERR_INVALID_ARG, "sosfilt_chunk: n_sections must be in [1, 16]");
+}
+
+int32_t nxsig_sosfilt_tile(int32_t n_sections) {
+  const int32_t v = iir_tile(n_sections);
+  return v ? v : set_error(NXSIG_ERR_INVALID_ARG, "sosfilt_tile: n_sections must be in [1, 16]");
+}
+
+// what the two entry points check alike, ahead of the context: pointers, mem, the cascade, the rows
+static int sos_check_common(const char* fn, const void* x, const void* y, const double* sos, int32_t n_sections, int32_t mem, int64_t length,
+                            int32_t batch, int64_t batch_stride) {
+  if (!x || !sos || !y) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (n_sections > kIirMaxSections)
+    return set_error(NXSIG_ERR_UNSUPPORTED, std::string(fn) + ": more than 16 sections in one call (split the cascade)");
+  if (const char* what = iir_check_sos(sos, n_sections)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": " + what);
+  if (const char* what = iir_check_args(length, batch, batch_stride, 1, false, 0)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": " + what);
+  if (length > INT64_MAX / batch / 16) return set_error(NXSIG_ERR_UNSUPPORTED, std::string(fn) + ": the rows are too large");
+  return NXSIG_OK;
+}
+
+int nxsig_sosfilt_zi(const double* sos, int32_t n_sections, double* zi_out) {
+  NXSIG_API_BEGIN
+  if (!sos || !zi_out) return set_error(NXSIG_ERR_INVALID_ARG, "sosfilt_zi: null pointer argument");
+  if (n_sections > (1 << 20)) return set_error(NXSIG_ERR_INVALID_ARG, "sosfilt_zi: too many sections");
+  if (const char* what = iir_check_sos(sos, n_sections)) return set_error(NXSIG_ERR_INVALID_ARG, std::string("sosfilt_zi: ") + what);
+  if (!iir_sosfilt_zi(sos, n_sections, zi_out))
+    return set_error(NXSIG_ERR_INVALID_ARG, "sosfilt_zi: singular matrix (a section has a pole at z = 1)");
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
+int nxsig_sosfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* sos,
+                      int32_t n_sections, const double* zi, int32_t zi_rows, double* zf_out, int32_t direction, float* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  int rc = sos_check_common("sosfilt", x, y, sos, n_sections, mem, length, batch, batch_stride);
+  if (rc) return rc;
+  if (const char* what = iir_check_args(length, batch, batch_stride, zi_rows, zi != nullptr, direction))
+    return set_error(NXSIG_ERR_INVALID_ARG, std::string("sosfilt: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(float)), kScratchNdStageA}},
+                    {{y, (size_t)batch * length * sizeof(float), kScratchNdStageOut}}))) return rc;
+  IirLaunch a;
+  a.x = static_cast<const float*>(io.in[0]); a.n = length; a.x_stride = batch_stride; a.batch = batch;
+  a.sos_host = sos; a.n_sections = n_sections; a.zi_host = zi; a.zi_rows = zi ? zi_rows : 1; a.zi_times_first = false;
+  a.zf_host = zf_out; a.direction = direction;
+  a.y = static_cast<float*>(io.out[0]); a.y_stride = length; a.out_off = 0; a.out_len = length;
+  if ((rc = launch_sosfilt(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+int nxsig_sosfiltfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* sos,
+                          int32_t n_sections, int32_t padtype, int64_t padlen, float* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  int rc = sos_check_common("sosfiltfilt", x, y, sos, n_sections, mem, length, batch, batch_stride);
+  if (rc) return rc;
+  const int64_t edge = iir_edge(sos, n_sections, padtype, padlen, length);
+  if (edge == -1) return set_error(NXSIG_ERR_INVALID_ARG, "sosfiltfilt: padtype must be NXSIG_SOS_PAD_NONE, _ODD, _EVEN or _CONSTANT");
+  if (edge == -2)
+    return set_error(NXSIG_ERR_INVALID_ARG, "sosfiltfilt: the length of the input vector x must be greater than padlen, which is " +
+                                                std::to_string(padlen < 0 ? iir_default_padlen(sos, n_sections) : padlen));
+  if (length + 2 * edge > INT64_MAX / batch / 16) return set_error(NXSIG_ERR_UNSUPPORTED, "sosfiltfilt: the rows are too large");
+  double zi_probe[2 * kIirMaxSections];
+  if (!iir_sosfilt_zi(sos, n_sections, zi_probe))
+    return set_error(NXSIG_ERR_INVALID_ARG, "sosfiltfilt: singular matrix (a section has a pole at z = 1)");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(float)), kScratchNdStageA}},
+                    {{y, (size_t)batch * length * sizeof(float), kScratchNdStageOut}}))) return rc;
+  if ((rc = launch_sosfiltfilt(c, static_cast<const float*>(io.in[0]), length, batch_stride, batch, sos, n_sections, padtype, edge,
+                               static_cast<float*>(io.out[0])))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"

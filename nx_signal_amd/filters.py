@@ -1,5 +1,5 @@
 """NxSignal.Filters: median/2, wiener/2 (lib/nx_signal/filters.ex:17-110, :281-303), firwin/3 (:147-279) and the new `fir`
-(BASELINE config 5)."""
+(BASELINE config 5), `resample_poly`, `sosfilt`, `sosfilt_zi` and `sosfiltfilt` (extensions in scipy.signal's spelling)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -240,3 +240,144 @@ def resample_poly(x, up, down, ctx=None, axis=-1, window=("kaiser", 5.0), taps=N
     _lib.check(lib.nxsig_resample_poly(_lib.ctx_ptr(c.handle), xs.ctypes.data_as(C.c_void_p), is_c, n, batch, n, h.ctypes.data_as(C.c_void_p), h.shape[0],
                                        up, down, out.ctypes.data_as(C.c_void_p), _lib.HOST))
     return np.ascontiguousarray(np.moveaxis(out, -1, axis))
+
+
+# ---- recursive filters: scipy.signal.sosfilt / sosfilt_zi / sosfiltfilt (include/nxsig.h)
+_SOS_MAX = 16   # sections of one C call; longer cascades run as consecutive groups
+_SOS_PADTYPES = {None: 0, "odd": 1, "even": 2, "constant": 3}
+
+
+def _sos(sos, fn):
+    """sos as a C-contiguous f64 [n_sections, 6] array, validated as scipy's _validate_sos does"""
+    try:
+        s = np.ascontiguousarray(np.asarray(sos), dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"{fn}: sos must be a real array of shape (n_sections, 6)") from None
+    if s.ndim != 2:
+        raise ArgumentError(f"{fn}: sos array must be 2D")
+    if s.shape[1] != 6 or s.shape[0] < 1:
+        raise ArgumentError(f"{fn}: sos array must be shape (n_sections, 6)")
+    if not (s[:, 3] == 1).all():
+        raise ArgumentError(f"{fn}: sos[:, 3] should be all ones")
+    if not np.isfinite(s).all():
+        raise ArgumentError(f"{fn}: sos must be finite")
+    return s
+
+
+def _sos_rows(x, axis, ctx, fn):
+    """(host rows [batch, n] or None, device (ptr, shape, dtype) or None, shape, axis, a function that gives the context) of the tensor a
+    recursive filter runs over; the context is looked up only once every argument has been checked"""
+    host, dev = _tensor(x)
+    shape = tuple(host.shape) if dev is None else tuple(dev[1])
+    dtype = host.dtype if dev is None else np.dtype(dev[2])
+    if dtype != np.float32:
+        raise NxSignalUnsupported(f"{fn}: real f32 tensors are built, got {dtype}")
+    rank = len(shape)
+    if rank < 1:
+        raise ArgumentError(f"{fn}: the tensor must have at least one axis")
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not -rank <= axis < rank:
+        raise ArgumentError(f"{fn}: axis {axis!r} is out of bounds for a tensor of rank {rank}")
+    axis = int(axis) % rank
+    if any(s < 1 for s in shape):
+        raise ArgumentError(f"{fn}: empty dimension")
+    if dev is not None:
+        if axis != rank - 1:
+            raise NxSignalUnsupported(f"{fn}: device tensors are filtered along their last axis only")
+        return None, dev, shape, axis, lambda: x.ctx if isinstance(x, DeviceBuffer) else (ctx or default_context())
+    return np.ascontiguousarray(np.moveaxis(host, axis, -1)), None, shape, axis, lambda: ctx or default_context()
+
+
+def sosfilt_zi(sos):
+    """scipy.signal.sosfilt_zi: the states (n_sections, 2) of the cascade's settled step response."""
+    s = _sos(sos, "sosfilt_zi")
+    zi = np.empty((s.shape[0], 2), np.float64)
+    pd = C.POINTER(C.c_double)
+    _lib.check(_lib.load().nxsig_sosfilt_zi(s.ctypes.data_as(pd), s.shape[0], zi.ctypes.data_as(pd)))
+    return zi
+
+
+def sosfilt(x, sos, zi=None, ctx=None, axis=-1, direction=0):
+    """Extension (the reference has no recursive filter): scipy.signal.sosfilt(sos, x, axis, zi) on the GPU — a cascade of biquads
+    `sos` (n_sections, 6), a0 == 1, in transposed direct form II over `axis` of real f32 rows, computed in double and rounded to f32
+    once.  Returns y, or (y, zf) when `zi` (n_sections, ..., 2) is given, in scipy's layouts; zf is a numpy array.  Host arrays: any
+    axis, numpy out; a device tensor: the last axis only, a DeviceBuffer out.  Cascades of more than 16 sections run as consecutive
+    groups of 16 (f32 rows between the groups).  direction=1 runs the filter from the end of each row towards its start.  Outputs
+    ahead of a row's first Inf / NaN are untouched by it; every output from it on is non-finite."""
+    s = _sos(sos, "sosfilt")
+    rows, dev, shape, axis, get_ctx = _sos_rows(x, axis, ctx, "sosfilt")
+    if direction not in (0, 1):
+        raise ArgumentError(f"sosfilt: direction must be 0 or 1, got: {direction!r}")
+    n, ns = shape[axis], s.shape[0]
+    batch = int(np.prod(shape, dtype=np.int64)) // n
+    zrows = None
+    if zi is not None:
+        z = np.asarray(zi)
+        want = (ns,) + shape[:axis] + (2,) + shape[axis + 1:]
+        if z.shape != want or z.dtype.kind not in "fiu":
+            raise ArgumentError(f"sosfilt: invalid zi shape. With axis={axis - len(shape)}, an input with shape {shape}, and an sos array with "
+                                f"{ns} sections, zi must have shape {want}, got {z.shape}.")
+        # [batch][n_sections][2] for the C ABI
+        zrows = np.ascontiguousarray(np.moveaxis(z.astype(np.float64), axis + 1, -1).reshape(ns, batch, 2).transpose(1, 0, 2))
+    lib, c = _lib.load(), get_ctx()
+    zf = np.empty((batch, ns, 2), np.float64) if zi is not None else None
+    src, out = (dev[0], None) if dev is not None else (rows, None)
+    for g0 in range(0, ns, _SOS_MAX):
+        sg = np.ascontiguousarray(s[g0:g0 + _SOS_MAX])
+        k = sg.shape[0]
+        zig = np.ascontiguousarray(zrows[:, g0:g0 + k]) if zrows is not None else None
+        zfg = np.empty((batch, k, 2), np.float64) if zrows is not None else None
+        args = (sg.ctypes.data_as(C.c_void_p), k, zig.ctypes.data_as(C.c_void_p) if zig is not None else None, batch,
+                zfg.ctypes.data_as(C.c_void_p) if zfg is not None else None, int(direction))
+        if dev is not None:
+            nxt = DeviceBuffer.empty(c, shape, np.float32)
+            _lib.check(lib.nxsig_sosfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), C.c_void_p(src), n, batch, n, *args, C.c_void_p(nxt.ptr), _lib.DEVICE))
+            out = nxt   # the previous group's result is let go only now, behind the call that read it
+            src = out.ptr
+        else:
+            out = np.empty((batch, n), np.float32)
+            _lib.check(lib.nxsig_sosfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), src.ctypes.data_as(C.c_void_p), n, batch, n, *args,
+                                             out.ctypes.data_as(C.c_void_p), _lib.HOST))
+            src = out
+        if zfg is not None:
+            zf[:, g0:g0 + k] = zfg
+    if dev is None:
+        out = np.ascontiguousarray(np.moveaxis(out.reshape(shape[:axis] + shape[axis + 1:] + (n,)), -1, axis))
+    if zi is None:
+        return out
+    zf = np.moveaxis(zf.transpose(1, 0, 2).reshape((ns,) + shape[:axis] + shape[axis + 1:] + (2,)), -1, axis + 1)
+    return out, np.ascontiguousarray(zf)
+
+
+def sosfiltfilt(x, sos, ctx=None, axis=-1, padtype="odd", padlen=None):
+    """Extension: scipy.signal.sosfiltfilt(sos, x, axis, padtype, padlen) in one device-resident call — the rows extended by `padlen`
+    samples per side (default: scipy's), filtered forward and backward from the states sosfilt_zi scaled by the first sample each
+    way, the middle kept.  padtype "odd" (default), "even", "constant" or None.  Real f32 rows; host arrays: any axis, numpy out; a
+    device tensor: the last axis only, a DeviceBuffer out.  At most 16 sections.  A row with an Inf / NaN is non-finite everywhere."""
+    s = _sos(sos, "sosfiltfilt")
+    if isinstance(padtype, (list, dict, set, np.ndarray)) or padtype not in _SOS_PADTYPES:
+        raise ArgumentError(f"sosfiltfilt: unknown value {padtype!r} given to padtype. padtype must be 'even', 'odd', 'constant', or None.")
+    if padlen is not None and (isinstance(padlen, bool) or not isinstance(padlen, (int, np.integer)) or padlen < 0):
+        raise ArgumentError(f"sosfiltfilt: padlen must be a non-negative integer or None, got: {padlen!r}")
+    rows, dev, shape, axis, get_ctx = _sos_rows(x, axis, ctx, "sosfiltfilt")
+    if s.shape[0] > _SOS_MAX:
+        raise NxSignalUnsupported(f"sosfiltfilt: cascades of up to {_SOS_MAX} sections are built, got {s.shape[0]}")
+    n = shape[axis]
+    batch = int(np.prod(shape, dtype=np.int64)) // n
+    if padtype is None:
+        edge = 0
+    elif padlen is None:
+        edge = 3 * (2 * s.shape[0] + 1 - min(int((s[:, 2] == 0).sum()), int((s[:, 5] == 0).sum())))
+    else:
+        edge = int(padlen)
+    if n <= edge:   # scipy's _validate_pad
+        raise ArgumentError(f"sosfiltfilt: the length of the input vector x must be greater than padlen, which is {edge}.")
+    lib, c = _lib.load(), get_ctx()
+    args = (s.ctypes.data_as(C.c_void_p), s.shape[0], _SOS_PADTYPES[padtype], edge)
+    if dev is not None:
+        out = DeviceBuffer.empty(c, shape, np.float32)
+        _lib.check(lib.nxsig_sosfiltfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), C.c_void_p(dev[0]), n, batch, n, *args, C.c_void_p(out.ptr), _lib.DEVICE))
+        return out
+    out = np.empty((batch, n), np.float32)
+    _lib.check(lib.nxsig_sosfiltfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), rows.ctypes.data_as(C.c_void_p), n, batch, n, *args,
+                                         out.ctypes.data_as(C.c_void_p), _lib.HOST))
+    return np.ascontiguousarray(np.moveaxis(out.reshape(shape[:axis] + shape[axis + 1:] + (n,)), -1, axis))

@@ -4,6 +4,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py [--lib PATH] [--real] [--write tests/golden/abi_error_table.json]
     python tools/abi_error_probe.py --own [--real] [--write tests/golden/abi_error_table_resample.json]
     python tools/abi_error_probe.py --welch [--real] [--write tests/golden/abi_error_table_welch.json]
+    python tools/abi_error_probe.py --iir [--real] [--write tests/golden/abi_error_table_iir.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -14,7 +15,8 @@ the build whose behaviour is the reference (tests/test_abi_errors_host.py and te
 ENTRIES and that golden file are the recorded table of the entry points that existed when it was made.  An entry point added since
 keeps its rows in OWN_TABLE_ENTRIES and a golden file of its own (--own; tests/test_resample_host.py and tests/test_gpu_resample.py
 compare against it): the same probe, the same kinds of cases.  WELCH_TABLE_ENTRIES (--welch) does the same for nxsig_welch_f32 and
-nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py)."""
+nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py), IIR_TABLE_ENTRIES (--iir) for nxsig_sosfilt_f32 and
+nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py)."""
 import argparse
 import ctypes as C
 import json
@@ -31,6 +33,7 @@ from nx_signal_amd import _lib  # noqa: E402  (signature table + structs only)
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_error_table.json")
 GOLDEN_OWN = os.path.join(ROOT, "tests", "golden", "abi_error_table_resample.json")
 GOLDEN_WELCH = os.path.join(ROOT, "tests", "golden", "abi_error_table_welch.json")
+GOLDEN_IIR = os.path.join(ROOT, "tests", "golden", "abi_error_table_iir.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -281,6 +284,30 @@ WELCH_TABLE_ENTRIES = [
      _WELCH_CASES),
 ]
 
+# Filters.sosfilt / sosfiltfilt: 2 rows of 40 samples through a two-section low-pass (sos, zi and zf are host arrays whatever `mem` says)
+IL = 40
+_IIR_SOS = np.array([[0.02, 0.04, 0.02, 1.0, -1.2, 0.4], [1.0, -0.5, 0.25, 1.0, -0.9, 0.5]], np.float64)
+_IIR_BAD_A0 = _IIR_SOS.copy()
+_IIR_BAD_A0[1, 3] = 2.0
+_IIR_NAN = _IIR_SOS.copy()
+_IIR_NAN[0, 1] = np.nan
+_IIR_POLE1 = np.array([[1.0, 0.0, 0.0, 1.0, -1.0, 0.0]] * 2, np.float64)
+_IIR_CASES = [("batch=0", {"batch": 0}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": IL - 1}),
+              ("n_sections=0", {"n_sections": 0}), ("n_sections=17", {"n_sections": 17}), ("a0=2", {"sos": _IIR_BAD_A0}),
+              ("sos not finite", {"sos": _IIR_NAN}), ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16})]
+IIR_TABLE_ENTRIES = [
+    ("nxsig_sosfilt_f32",
+     [("x", "in", _f32(B, IL)), ("length", "v", IL), ("batch", "v", B), ("batch_stride", "v", IL), ("sos", "host", _IIR_SOS), ("n_sections", "v", 2),
+      ("zi", "host?", 0.1 * _f32(B, 2, 2).astype(np.float64)), ("zi_rows", "v", B), ("zf_out", "hout?", np.zeros((B, 2, 2), np.float64)),
+      ("direction", "v", 0), ("y", "out", np.zeros((B, IL), np.float32)), ("mem", "mem", None)],
+     _IIR_CASES + [("zi_rows=3", {"zi_rows": 3}), ("direction=2", {"direction": 2})]),
+    ("nxsig_sosfiltfilt_f32",
+     [("x", "in", _f32(B, IL)), ("length", "v", IL), ("batch", "v", B), ("batch_stride", "v", IL), ("sos", "host", _IIR_SOS), ("n_sections", "v", 2),
+      ("padtype", "v", 1), ("padlen", "v", -1), ("y", "out", np.zeros((B, IL), np.float32)), ("mem", "mem", None)],
+     _IIR_CASES + [("padtype=4", {"padtype": 4}), ("padlen=length", {"padlen": IL}), ("default padlen >= length", {"length": 15, "batch_stride": 15}),
+                   ("pole at z=1", {"sos": _IIR_POLE1})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -393,9 +420,10 @@ def main():
     ap.add_argument("--write", metavar="JSON", default=None, help="merge the table into this golden file (default: print it)")
     ap.add_argument("--own", action="store_true", help="the entry points of OWN_TABLE_ENTRIES instead of the recorded table's")
     ap.add_argument("--welch", action="store_true", help="the entry points of WELCH_TABLE_ENTRIES (Spectral.welch / csd)")
+    ap.add_argument("--iir", action="store_true", help="the entry points of IIR_TABLE_ENTRIES (Filters.sosfilt / sosfiltfilt)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
