@@ -24,7 +24,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, NxSignalDeviceError, NxSignalLibraryError, NxSignalUnsupported, StftParams
-from .device import Context, DeviceBuffer, default_context, device_view, is_device
+from ._marshal import Operand, _as_tensor, is_device, ptr, rows_last, validate as _validate
+from .device import Context, DeviceBuffer, default_context
 
 __all__ = [
     "stft", "istft", "as_windowed", "overlap_and_add", "fft_frequencies", "mel_filters", "stft_to_mel", "mel_spectrogram",
@@ -37,42 +38,17 @@ _PAD_ATOMS = {"valid": _lib.PAD_VALID, "reflect": _lib.PAD_REFLECT, "same": _lib
 _SCALING = {None: _lib.SCALE_NONE, "spectrum": _lib.SCALE_SPECTRUM, "psd": _lib.SCALE_PSD}
 
 
-def _validate(opts: dict, allowed: dict, fn: str) -> dict:
-    """Keyword.validate!/keyword! — unknown keys raise ArgumentError."""
-    unknown = [k for k in opts if k not in allowed]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in {fn} options, the allowed keys are: {list(allowed)}")
-    out = dict(allowed)
-    out.update(opts)
-    return out
-
-
-def _as_tensor(x):
-    """What Nx.tensor/1 would make of a host value: numpy arrays keep their dtype (np.float64 IS f64: the f64 tier); plain Python
-    numbers and (nested) lists follow Nx's inference — floats become f32, complex numbers c64, integers stay integers."""
-    if isinstance(x, np.ndarray) or is_device(x):
-        return x
-    a = np.asarray(x)
-    if a.dtype == np.float64:
-        return a.astype(np.float32)
-    if a.dtype == np.complex128:
-        return a.astype(np.complex64)
-    return a
-
-
-def _host_f32(x, what: str) -> np.ndarray:
-    a = np.asarray(x)
-    if a.dtype == np.float32:
-        return np.ascontiguousarray(a)
-    if a.dtype.kind in "iub":  # integer tensors are legal inputs (SURVEY B15)
-        return np.ascontiguousarray(a.astype(np.float32))
-    if a.dtype == np.float64:
+def _host_f32(x: Operand, what: str) -> Operand:
+    """the f32 entry points' rule for a host operand: f32 as it is, integers widened, anything else refused"""
+    if x.dtype == np.float32 or x.dtype.kind in "iub":
+        return x.cast(np.float32)
+    if x.dtype == np.float64:
         raise ArgumentError(
             f"{what}: float64 input would produce an f64 / c128 result in the reference; this entry point computes f32 / c64 — "
             "cast to float32 explicitly (stft, istft, as_windowed, overlap_and_add, fft_nd over the last axis and 1-D fftconvolve "
             "take float64 / complex128 and compute in double)"
         )
-    raise ArgumentError(f"{what}: unsupported dtype {a.dtype}")
+    raise ArgumentError(f"{what}: unsupported dtype {x.dtype}")
 
 
 def _window_host(window) -> np.ndarray:
@@ -106,18 +82,6 @@ def _pad_args(padding, fn="as_windowed"):
     )
 
 
-def _ctx_of(obj, ctx):
-    if ctx is not None:
-        return ctx
-    if isinstance(obj, DeviceBuffer):
-        return obj.ctx
-    return default_context()
-
-
-def _as_ptr(arr: np.ndarray):
-    return arr.ctypes.data_as(C.c_void_p)
-
-
 def _resolve_fft_length(fft_length, n: int) -> int:
     if fft_length in (None, "power_of_two"):
         return int(_lib.load().nxsig_next_pow2(int(n)))
@@ -133,14 +97,12 @@ def fft_frequencies(sampling_rate, **opts):
     if o["fft_length"] is None:
         raise ArgumentError("missing :fft_length option")
     K = int(o["fft_length"])
-    if o["type"] in ("f64", np.float64):
-        out = np.empty(K, dtype=np.float64)
-        _lib.check(_lib.load().nxsig_fft_frequencies_f64(float(sampling_rate), K, int(bool(o["endpoint"])), _as_ptr(out)))
-        return out
-    if o["type"] not in ("f32", np.float32):
+    f64 = o["type"] in ("f64", np.float64)
+    if not f64 and o["type"] not in ("f32", np.float32):
         raise ArgumentError(f"fft_frequencies: type must be f32 or f64, got {o['type']!r}")
-    out = np.empty(K, dtype=np.float32)
-    _lib.check(_lib.load().nxsig_fft_frequencies_f32(float(sampling_rate), K, int(bool(o["endpoint"])), _as_ptr(out)))
+    out = np.empty(K, dtype=np.float64 if f64 else np.float32)
+    entry = _lib.load().nxsig_fft_frequencies_f64 if f64 else _lib.load().nxsig_fft_frequencies_f32
+    _lib.check(entry(float(sampling_rate), K, int(bool(o["endpoint"])), ptr(out)))
     return out
 
 
@@ -156,58 +118,40 @@ def as_windowed(tensor, ctx: Context | None = None, **opts):
     N = int(o["window_length"])
     lib = _lib.load()
     M = C.c_int64()
-    tensor = _as_tensor(tensor)
-    if is_device(tensor):
-        ptr, shape, dt = device_view(tensor)
-        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+    x = Operand(_as_tensor(tensor))
+    src_dtype = x.dtype
+    ints = not x.device and x.dtype.kind in "iub"
+    if x.device:
+        if x.dtype not in (np.float32, np.float64):
             raise ArgumentError("as_windowed: device input must be float32 or float64")
-        c = _ctx_of(tensor, ctx)
-        L = shape[-1]
-        batch = int(np.prod(shape[:-1], dtype=np.int64)) if len(shape) > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, int(stride), mode, lo, hi))
-        out = c.empty(shape[:-1] + (m, N), dt)
-        entry = lib.nxsig_as_windowed_f64 if dt == np.dtype(np.float64) else lib.nxsig_as_windowed_f32
-        _lib.check(entry(c.handle, C.c_void_p(ptr), L, batch, L, N, int(stride), mode, lo, hi, C.c_void_p(out.ptr), C.byref(M), _lib.DEVICE))
-        return out
-    src = np.asarray(tensor)
-    if src.dtype == np.float64:   # f64 tier: 8-byte words through the same gather
-        x = np.ascontiguousarray(src)
-        c = _ctx_of(None, ctx)
-        L = x.shape[-1]
-        batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, int(stride), mode, lo, hi))
-        out = np.empty(x.shape[:-1] + (m, N), dtype=np.float64)
-        _lib.check(lib.nxsig_as_windowed_f64(c.handle, _as_ptr(x), L, batch, L, N, int(stride), mode, lo, hi, _as_ptr(out), C.byref(M),
-                                             _lib.HOST))
-        return out
-    if src.dtype.kind in "iub":
+    elif x.dtype == np.float64:   # f64 tier: 8-byte words through the same gather
+        x.cast()
+    elif ints:
         # framing is a pure gather (doctests :182-246 keep s64): 32-bit words travel through the kernel untouched, so integer
         # tensors stay EXACT (no rounding through f32); wider integers go through int32 when every value fits
-        if src.size and (int(src.min()) < -2 ** 31 or int(src.max()) > 2 ** 31 - 1):
+        if x.host.size and (int(x.host.min()) < -2 ** 31 or int(x.host.max()) > 2 ** 31 - 1):
             raise ArgumentError("as_windowed: integer values beyond 32 bits are not supported by the MI355X path")
-        x = np.ascontiguousarray(src.astype(np.int32)).view(np.float32)
+        x.cast(np.int32)
     else:
-        x = _host_f32(src, "as_windowed")
-    c = _ctx_of(None, ctx)
-    L = x.shape[-1]
-    batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
+        _host_f32(x, "as_windowed")
+    wide = x.dtype == np.float64
+    c = x.context(ctx, caller_first=True)
+    batch, L = rows_last(x.shape)
     m = _lib.check(lib.nxsig_num_frames(L, N, int(stride), mode, lo, hi))
-    out = np.empty(x.shape[:-1] + (m, N), dtype=np.float32)
-    _lib.check(lib.nxsig_as_windowed_f32(c.handle, _as_ptr(x), L, batch, L, N, int(stride), mode, lo, hi, _as_ptr(out),
-                                         C.byref(M), _lib.HOST))
-    if src.dtype.kind in "iub":
-        return out.view(np.int32).astype(src.dtype)
-    return out
+    out = x.result(x.shape[:-1] + (m, N), np.float64 if wide else np.float32)
+    entry = lib.nxsig_as_windowed_f64 if wide else lib.nxsig_as_windowed_f32
+    _lib.check(entry(c.handle, x.ptr, L, batch, L, N, int(stride), mode, lo, hi, ptr(out), C.byref(M), x.mem))
+    return out.view(np.int32).astype(src_dtype) if ints else out
 
 
-def _resolve_stft_opts(window, opts):
-    """option parsing / defaults of NxSignal.stft/3 (lib/nx_signal.ex:71-85) -> (StftParams, N, hop, K)"""
-    o = _validate(
-        opts,
-        {"overlap_length": None, "window": None, "scaling": None, "window_padding": "valid", "sampling_rate": 100,
-         "fft_length": "power_of_two"},
-        "stft",
-    )
+_STFT_OPTS = {"overlap_length": None, "window": None, "scaling": None, "window_padding": "valid", "sampling_rate": 100,
+              "fft_length": "power_of_two"}
+
+
+def _resolve_stft_opts(window, opts, fn="stft"):
+    """option parsing / defaults of NxSignal.stft/3 (lib/nx_signal.ex:71-85) -> (StftParams, N, hop, K); `fn` names the function in
+    the unknown-key message (mel_spectrogram and spectrogram take the same options)"""
+    o = _validate(opts, _STFT_OPTS, fn)
     w = _window_host(window)
     N = int(w.shape[0])
     if o["sampling_rate"] is None:
@@ -220,6 +164,14 @@ def _resolve_stft_opts(window, opts):
     mode, lo, hi = _pad_args(o["window_padding"])
     K = _resolve_fft_length(o["fft_length"], N)
     return StftParams(N, hop, K, mode, lo, hi, _SCALING[o["scaling"]], 0, fs), N, hop, K
+
+
+def _frames(x: Operand, ctx, p):
+    """what every framing call over the last axis of x needs -> (context, rows, row length, frames per row)"""
+    c = x.context(ctx, caller_first=True)
+    batch, L = rows_last(x.shape)
+    m = _lib.check(_lib.load().nxsig_num_frames(L, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi))
+    return c, batch, L, m
 
 
 def stft(data, window, ctx: Context | None = None, **opts):
@@ -263,7 +215,6 @@ def _stft(data, window, ctx, opts, onesided, packed=False):
     p, N, hop, K = _resolve_stft_opts(window, opts)
     w = _window_host(window)
     fs = float(p.sampling_rate)
-    mode, lo, hi = p.pad_mode, p.pad_lo, p.pad_hi
     lib = _lib.load()
     M = C.c_int64()
     Kout = K // 2 if onesided else K
@@ -272,87 +223,54 @@ def _stft(data, window, ctx, opts, onesided, packed=False):
     entry = lib.nxsig_stft_packed_f32 if packed else (lib.nxsig_stft_onesided_f32 if onesided else lib.nxsig_stft_f32)
     if packed and K % 2:
         raise ArgumentError("stft_packed: fft_length must be even")
-    # f64 tier: f64 samples or an f64 window make the reference compute in f64 / c128 (Nx.multiply promotes, :101-102)
-    ddt = np.dtype(device_view(data)[2]) if is_device(data) else np.asarray(data).dtype
-    data_f64 = ddt == np.float64
+    x = Operand(data)
+    # f64 tier: f64 samples or an f64 window make the reference compute in f64 / c128 (Nx.multiply promotes, :101-102);
     # c128 samples, or c64 samples under an f64 window (the product of :101 promotes to c128): nxsig_stft_c128
-    data_c128 = ddt == np.complex128 or (ddt == np.complex64 and w.dtype == np.float64)
-    if data_f64 or data_c128 or w.dtype == np.float64:
+    data_c128 = x.dtype == np.complex128 or (x.dtype == np.complex64 and w.dtype == np.float64)
+    if x.dtype == np.float64 or data_c128 or w.dtype == np.float64:
         if onesided:
             raise ArgumentError("stft_onesided / stft_packed are f32 extensions; the f64 tier returns the full c128 spectrum")
-        return _stft_f64(data, w, ctx, p, N, hop, K, data_f64, cplx=data_c128)
+        return _stft_f64(x, w, ctx, p, cplx=data_c128)
     # complex samples (c64 IQ data): the reference frames, multiplies and transforms whatever tensor it is given (lib/nx_signal.ex:94-102):
     # one transform per frame, nxsig_stft_c64
-    data_c64 = (device_view(data)[2] == np.dtype(np.complex64)) if is_device(data) else (np.asarray(data).dtype == np.complex64)
+    data_c64 = x.dtype == np.complex64
     if data_c64:
         if onesided:
             raise ArgumentError("stft_onesided / stft_packed need real samples (a complex signal's spectrum is not Hermitian)")
         entry = lib.nxsig_stft_c64
-    if is_device(data):
-        ptr, shape, dt = device_view(data)
-        if dt != np.float32 and not data_c64:
+    if x.device:
+        if x.dtype != np.float32 and not data_c64:
             raise ArgumentError("stft: device input must be float32, float64 or complex64")
-        c = _ctx_of(data, ctx)
-        L = shape[-1]
-        batch = int(np.prod(shape[:-1], dtype=np.int64)) if len(shape) > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-        z = c.empty(shape[:-1] + (m, Kout), np.complex64)
-        _lib.check(entry(c.handle, C.c_void_p(ptr), L, batch, L, _as_ptr(w), C.byref(p), C.c_void_p(z.ptr),
-                                      C.byref(M), _lib.DEVICE))
+    elif data_c64:
+        x.cast()
     else:
-        x = np.ascontiguousarray(np.asarray(data)) if data_c64 else _host_f32(data, "stft")
-        if x.ndim < 1:
-            raise ArgumentError("stft expects a tensor of rank >= 1")
-        c = _ctx_of(None, ctx)
-        L = x.shape[-1]
-        batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-        z = np.empty(x.shape[:-1] + (m, Kout), dtype=np.complex64)
-        _lib.check(entry(c.handle, _as_ptr(x), L, batch, L, _as_ptr(w), C.byref(p), _as_ptr(z), C.byref(M),
-                                      _lib.HOST))
-    times = np.empty(m, dtype=np.float32)
-    _lib.check(lib.nxsig_stft_times_f32(N, fs, m, _as_ptr(times)))
+        _host_f32(x, "stft")
+    c, batch, L, m = _frames(x, ctx, p)
+    z = x.result(x.shape[:-1] + (m, Kout), np.complex64)
+    _lib.check(entry(c.handle, x.ptr, L, batch, L, ptr(w), C.byref(p), ptr(z), C.byref(M), x.mem))
     freqs = fft_frequencies(fs, fft_length=K)
-    return z, times, (freqs[:Kout] if onesided else freqs)
+    return z, _stft_times(m, N, fs), (freqs[:Kout] if onesided else freqs)
 
 
-def _stft_f64(data, w, ctx, p, N, hop, K, data_f64, cplx=False):
+def _stft_f64(x, w, ctx, p, cplx=False):
     """stft of f64 samples and / or with an f64 window: c128 spectrum (nxsig_stft_f64; complex samples: nxsig_stft_c128); times /
     frequencies stay f32 like the reference's (their linspace calls do not take the data type, lib/nx_signal.ex:106-111)"""
     lib = _lib.load()
     M = C.c_int64()
     fs = float(p.sampling_rate)
-    mode, lo, hi = p.pad_mode, p.pad_lo, p.pad_hi
-    wflag = int(w.dtype == np.float64)
     entry = lib.nxsig_stft_c128 if cplx else lib.nxsig_stft_f64
     wide_t = np.complex128 if cplx else np.float64
-    if is_device(data):
-        ptr, shape, ddt = device_view(data)
-        if np.dtype(ddt) != np.dtype(wide_t):
+    if x.device:
+        if x.dtype != wide_t:
             raise NxSignalUnsupported("stft: an f64 window with device-resident f32 / c64 samples is not built; widen the samples first")
-        c = _ctx_of(data, ctx)
-        L = shape[-1]
-        batch = int(np.prod(shape[:-1], dtype=np.int64)) if len(shape) > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-        z = c.empty(shape[:-1] + (m, K), np.complex128)
-        _lib.check(entry(c.handle, C.c_void_p(ptr), L, batch, L, _as_ptr(w), wflag, C.byref(p), C.c_void_p(z.ptr),
-                         C.byref(M), _lib.DEVICE))
     else:
-        a = np.asarray(data)
-        if a.dtype.kind not in ("fiubc" if cplx else "fiub"):
-            raise ArgumentError(f"stft: unsupported dtype {a.dtype}")
-        x = np.ascontiguousarray(a.astype(wide_t))   # f32 / c64 / integer samples widen exactly
-        if x.ndim < 1:
-            raise ArgumentError("stft expects a tensor of rank >= 1")
-        c = _ctx_of(None, ctx)
-        L = x.shape[-1]
-        batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-        z = np.empty(x.shape[:-1] + (m, K), dtype=np.complex128)
-        _lib.check(entry(c.handle, _as_ptr(x), L, batch, L, _as_ptr(w), wflag, C.byref(p), _as_ptr(z), C.byref(M), _lib.HOST))
-    times = np.empty(m, dtype=np.float32)
-    _lib.check(lib.nxsig_stft_times_f32(N, fs, m, _as_ptr(times)))
-    return z, times, fft_frequencies(fs, fft_length=K)
+        if x.dtype.kind not in ("fiubc" if cplx else "fiub"):
+            raise ArgumentError(f"stft: unsupported dtype {x.dtype}")
+        x.cast(wide_t)   # f32 / c64 / integer samples widen exactly
+    c, batch, L, m = _frames(x, ctx, p)
+    z = x.result(x.shape[:-1] + (m, p.fft_length), np.complex128)
+    _lib.check(entry(c.handle, x.ptr, L, batch, L, ptr(w), int(w.dtype == np.float64), C.byref(p), ptr(z), C.byref(M), x.mem))
+    return z, _stft_times(m, p.frame_length, fs), fft_frequencies(fs, fft_length=p.fft_length)
 
 
 def istft(data, window, ctx: Context | None = None, **opts):
@@ -401,52 +319,41 @@ def _istft(data, window, ctx, opts, hh, packed=False):
     data, window = _as_tensor(data), _as_tensor(window)
     o, w, N, hop, fs = _istft_options(window, opts)
     lib = _lib.load()
-    wide = False   # f64 tier: a c128 spectrum is inverted in c128 (Nx.ifft :609)
-    if is_device(data):
-        ptr, shape, dt = device_view(data)
-        if dt not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+    x = Operand(data)
+    if x.device:
+        if x.dtype not in (np.complex64, np.complex128):
             raise ArgumentError("istft: device input must be complex64 or complex128")
-        wide = dt == np.dtype(np.complex128)
-        c = _ctx_of(data, ctx)
+        wide = x.dtype == np.complex128   # f64 tier: a c128 spectrum is inverted in c128 (Nx.ifft :609)
     else:
-        zin = np.asarray(data)
-        wide = zin.dtype in (np.complex128, np.float64)
-        zin = np.ascontiguousarray(zin.astype(np.complex128 if wide else np.complex64))
-        shape = zin.shape
-        c = _ctx_of(None, ctx)
+        wide = x.dtype in (np.complex128, np.float64)
+        x.cast(np.complex128 if wide else np.complex64)
     if wide and (packed or hh is not None):
         raise ArgumentError("istft_packed / istft_filtered are f32 extensions; the f64 tier takes the full c128 spectrum")
     if w.dtype == np.float64 and not wide:
         # the reference would invert in c64 (Nx.ifft rounds to c64) and only then promote the frames to c128: not modelled
         raise NxSignalUnsupported("istft: a c64 spectrum with an f64 window is not built; pass the spectrum as complex128")
-    if len(shape) < 2:
+    if len(x.shape) < 2:
         raise ArgumentError("istft expects a tensor of shape {..., frames, frequencies}")
-    Mf, Kin = int(shape[-2]), int(shape[-1])
+    (batch, Mf), Kin = rows_last(x.shape[:-1]), int(x.shape[-1])
     if packed:
         Kin *= 2   # the packed rows hold fft_length / 2 complex values
     K = _istft_fft_length(o, Kin)
     if hh is not None and int(hh.shape[0]) != K:
         raise ArgumentError("istft_filtered: h must have fft_length bins")
-    batch = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
     p = StftParams(N, hop, K, 0, 0, 0, _SCALING[o["scaling"]], 0, fs)
+    c = x.context(ctx, caller_first=True)
     out_len = _lib.check(lib.nxsig_ola_length(Mf, N, hop))
-
-    def call(zp, yp, mem):
-        if wide:
-            return lib.nxsig_istft_c128(c.handle, zp, Mf, batch, _as_ptr(w), int(w.dtype == np.float64), C.byref(p), yp, mem)
-        if packed:
-            return lib.nxsig_istft_packed_f32(c.handle, zp, Mf, batch, _as_ptr(w), C.byref(p), yp, mem)
-        if hh is None:
-            return lib.nxsig_istft_c64(c.handle, zp, Mf, batch, _as_ptr(w), C.byref(p), yp, mem)
-        return lib.nxsig_istft_filtered_c64(c.handle, zp, Mf, batch, _as_ptr(w), C.byref(p), _as_ptr(hh), yp, mem)
-
-    odt = np.complex128 if wide else (np.float32 if packed else np.complex64)
-    if is_device(data):
-        y = c.empty(tuple(shape[:-2]) + (out_len,), odt)
-        _lib.check(call(C.c_void_p(ptr), C.c_void_p(y.ptr), _lib.DEVICE))
-        return y
-    y = np.empty(tuple(shape[:-2]) + (out_len,), dtype=odt)
-    _lib.check(call(_as_ptr(zin), _as_ptr(y), _lib.HOST))
+    y = x.result(x.shape[:-2] + (out_len,), np.complex128 if wide else (np.float32 if packed else np.complex64))
+    head = (c.handle, x.ptr, Mf, batch, ptr(w))
+    if wide:
+        rc = lib.nxsig_istft_c128(*head, int(w.dtype == np.float64), C.byref(p), ptr(y), x.mem)
+    elif packed:
+        rc = lib.nxsig_istft_packed_f32(*head, C.byref(p), ptr(y), x.mem)
+    elif hh is None:
+        rc = lib.nxsig_istft_c64(*head, C.byref(p), ptr(y), x.mem)
+    else:
+        rc = lib.nxsig_istft_filtered_c64(*head, C.byref(p), ptr(hh), ptr(y), x.mem)
+    _lib.check(rc)
     return y
 
 
@@ -457,47 +364,34 @@ def overlap_and_add(tensor, ctx: Context | None = None, **opts):
         raise ArgumentError("missing :overlap_length option")
     overlap = int(o["overlap_length"])
     lib = _lib.load()
-    tensor = _as_tensor(tensor)
-    dev = is_device(tensor)
-    if dev:
-        ptr, shape, dt = device_view(tensor)
-        c = _ctx_of(tensor, ctx)
-        src_dtype = dt
+    x = Operand(_as_tensor(tensor))
+    src = x.host
+    src_dtype = x.dtype
+    if x.device or x.dtype in (np.float64, np.complex128):
+        x.cast()   # f64 tier
+    elif x.dtype.kind == "c":
+        x.cast(np.complex64)
     else:
-        src = np.asarray(tensor)
-        src_dtype = src.dtype
-        if src.dtype in (np.float64, np.complex128):
-            arr = np.ascontiguousarray(src)   # f64 tier
-        elif src.dtype.kind == "c":
-            arr = np.ascontiguousarray(src.astype(np.complex64))
-        else:
-            if src.dtype.kind in "iu" and src.size and src.ndim >= 2:
-                # the reference adds integers exactly; here sums are formed in double and stored as f32, exact only below 2^24:
-                # refuse loudly instead of returning rounded integers
-                cover = -(-int(src.shape[-1]) // max(int(src.shape[-1]) - overlap, 1))
-                if int(np.abs(src).max()) * cover >= 2 ** 24:
-                    raise ArgumentError("overlap_and_add: integer sums beyond 2^24 cannot be represented exactly by the f32 "
-                                        "MI355X path; cast to a float type explicitly")
-            arr = _host_f32(src, "overlap_and_add")
-        shape, dt = arr.shape, arr.dtype
-    if len(shape) < 2:
+        if src.dtype.kind in "iu" and src.size and src.ndim >= 2:
+            # the reference adds integers exactly; here sums are formed in double and stored as f32, exact only below 2^24:
+            # refuse loudly instead of returning rounded integers
+            cover = -(-int(src.shape[-1]) // max(int(src.shape[-1]) - overlap, 1))
+            if int(np.abs(src).max()) * cover >= 2 ** 24:
+                raise ArgumentError("overlap_and_add: integer sums beyond 2^24 cannot be represented exactly by the f32 "
+                                    "MI355X path; cast to a float type explicitly")
+        _host_f32(x, "overlap_and_add")
+    if len(x.shape) < 2:
         raise ArgumentError("overlap_and_add expects a tensor of shape {..., M, N}")
-    Mf, N = int(shape[-2]), int(shape[-1])
+    (batch, Mf), N = rows_last(x.shape[:-1]), int(x.shape[-1])
     if overlap >= N:  # :692-695 — the message prints the window size twice (quirk B10)
         raise ArgumentError(f"overlap_length must be a number less than the window size {N}, got: {N}")
-    if not dev:
-        c = _ctx_of(None, ctx)
-    comps = 2 if np.dtype(dt).kind == "c" else 1
-    entry = lib.nxsig_overlap_and_add_f64 if np.dtype(dt) in (np.dtype(np.float64), np.dtype(np.complex128)) else lib.nxsig_overlap_and_add
-    batch = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
-    out_len = Mf * (N - overlap) + overlap
-    out_shape = tuple(shape[:-2]) + (out_len,)
-    if dev:
-        out = c.empty(out_shape, dt)
-        _lib.check(entry(c.handle, C.c_void_p(ptr), Mf, batch, N, overlap, comps, C.c_void_p(out.ptr), _lib.DEVICE))
+    c = x.context(ctx, caller_first=True)
+    comps = 2 if x.dtype.kind == "c" else 1
+    entry = lib.nxsig_overlap_and_add_f64 if x.dtype in (np.float64, np.complex128) else lib.nxsig_overlap_and_add
+    out = x.result(x.shape[:-2] + (Mf * (N - overlap) + overlap,), x.dtype)
+    _lib.check(entry(c.handle, x.ptr, Mf, batch, N, overlap, comps, ptr(out), x.mem))
+    if x.device:
         return out
-    out = np.empty(out_shape, dtype=dt)
-    _lib.check(entry(c.handle, _as_ptr(arr), Mf, batch, N, overlap, comps, _as_ptr(out), _lib.HOST))
     target = o["type"] if o["type"] is not None else src_dtype  # code default: the input type (:685, B10)
     return out.astype(target) if np.dtype(target) != out.dtype else out
 
@@ -515,7 +409,7 @@ def mel_filters(fft_length, mel_bins, sampling_rate, **opts):
 def _mel_filters_table(fft_length: int, mel_bins: int, sampling_rate: float, max_mel: float, spacing: float) -> np.ndarray:
     """the filterbank is a pure function of its five parameters: generated once per combination (read-only copy)"""
     out = np.empty((mel_bins, fft_length), dtype=np.float32)
-    _lib.check(_lib.load().nxsig_mel_filters_f32(fft_length, mel_bins, sampling_rate, max_mel, spacing, _as_ptr(out)))
+    _lib.check(_lib.load().nxsig_mel_filters_f32(fft_length, mel_bins, sampling_rate, max_mel, spacing, ptr(out)))
     out.setflags(write=False)
     return out
 
@@ -535,25 +429,15 @@ def stft_to_mel(z, sampling_rate, ctx: Context | None = None, **opts):
     K, mb = int(o["fft_length"]), int(o["mel_bins"])
     fopts = {k: o[k] for k in ("max_mel", "mel_frequency_spacing") if o[k] is not None}
     filt = _mel_filters_for(K, mb, sampling_rate, fopts)
-    lib = _lib.load()
-    if is_device(z):
-        ptr, shape, dt = device_view(z)
-        if dt != np.complex64:
-            raise ArgumentError("stft_to_mel: device input must be complex64")
-        if shape[-1] != K:
-            raise ArgumentError("stft_to_mel: the last axis must be fft_length")
-        c = _ctx_of(z, ctx)
-        rows = int(np.prod(shape[:-1], dtype=np.int64))
-        out = c.empty(tuple(shape[:-1]) + (mb,), np.float32)
-        _lib.check(lib.nxsig_stft_to_mel(c.handle, C.c_void_p(ptr), rows, K, mb, _as_ptr(filt), C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    zin = np.ascontiguousarray(np.asarray(z).astype(np.complex64))
-    if zin.shape[-1] != K:
+    x = Operand(z)
+    if x.device and x.dtype != np.complex64:
+        raise ArgumentError("stft_to_mel: device input must be complex64")
+    x.cast(np.complex64)
+    if x.shape[-1] != K:
         raise ArgumentError("stft_to_mel: the last axis must be fft_length")
-    c = _ctx_of(None, ctx)
-    rows = int(np.prod(zin.shape[:-1], dtype=np.int64))
-    out = np.empty(zin.shape[:-1] + (mb,), dtype=np.float32)
-    _lib.check(lib.nxsig_stft_to_mel(c.handle, _as_ptr(zin), rows, K, mb, _as_ptr(filt), _as_ptr(out), _lib.HOST))
+    c = x.context(ctx, caller_first=True)
+    out = x.result(x.shape[:-1] + (mb,), np.float32)
+    _lib.check(_lib.load().nxsig_stft_to_mel(c.handle, x.ptr, rows_last(x.shape)[0], K, mb, ptr(filt), ptr(out), x.mem))
     return out
 
 
@@ -565,23 +449,15 @@ def spectrum_multiply(z, h, ctx: Context | None = None):
     if hh.ndim != 1:
         raise ArgumentError("spectrum_multiply: h must be a rank-1 tensor of fft_length bins")
     K = int(hh.shape[0])
-    lib = _lib.load()
-    if is_device(z):
-        ptr, shape, dt = device_view(z)
-        if dt != np.complex64 or shape[-1] != K:
-            raise ArgumentError("spectrum_multiply: z must be complex64 with fft_length bins on the last axis")
-        c = _ctx_of(z, ctx)
-        out = c.empty(tuple(shape), np.complex64)
-        rows = int(np.prod(shape[:-1], dtype=np.int64))
-        _lib.check(lib.nxsig_spectrum_mul_c64(c.handle, C.c_void_p(ptr), rows, K, _as_ptr(hh), C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    zin = np.ascontiguousarray(np.asarray(z).astype(np.complex64))
-    if zin.shape[-1] != K:
+    x = Operand(z)
+    if x.device and (x.dtype != np.complex64 or x.shape[-1] != K):
+        raise ArgumentError("spectrum_multiply: z must be complex64 with fft_length bins on the last axis")
+    x.cast(np.complex64)
+    if x.shape[-1] != K:
         raise ArgumentError("spectrum_multiply: z must have fft_length bins on the last axis")
-    c = _ctx_of(None, ctx)
-    out = np.empty_like(zin)
-    rows = int(np.prod(zin.shape[:-1], dtype=np.int64))
-    _lib.check(lib.nxsig_spectrum_mul_c64(c.handle, _as_ptr(zin), rows, K, _as_ptr(hh), _as_ptr(out), _lib.HOST))
+    c = x.context(ctx, caller_first=True)
+    out = x.result(x.shape, np.complex64)
+    _lib.check(_lib.load().nxsig_spectrum_mul_c64(c.handle, x.ptr, rows_last(x.shape)[0], K, ptr(hh), ptr(out), x.mem))
     return out
 
 
@@ -590,20 +466,16 @@ _MASK_REAL, _MASK_ONESIDED, _MASK_COMPLEX = 0, 1, 2   # nxsig_mask_kind
 
 def _mask_operands(z, mask, fn):
     """Shape / type / placement checks shared by spectrum_mask and istft_masked — all of them before a context exists.
-    -> (dev, zv, mv, (M, K), kind, (Bz, Bm), lead): zv / mv are (ptr, shape, dtype) of device operands or contiguous host arrays."""
+    -> (z, mask, (M, K), kind, (Bz, Bm), lead): the two as Operands, host arrays contiguous in c64 and in f32 / c64."""
     z, mask = _as_tensor(z), _as_tensor(mask)
-    dev = is_device(z)
-    if dev != is_device(mask):
+    if is_device(z) != is_device(mask):
         raise ArgumentError(f"{fn}: z and mask must both be host tensors or both be device-resident")
-    if dev:
-        zv, mv = device_view(z), device_view(mask)
-        zshape, zdt, mshape, mdt = tuple(zv[1]), np.dtype(zv[2]), tuple(mv[1]), np.dtype(mv[2])
-        cz, cm = getattr(z, "ctx", None), getattr(mask, "ctx", None)
-        if cz is not None and cm is not None and cz is not cm:
-            raise ArgumentError(f"{fn}: z and mask live on different contexts")
-    else:
-        zv, mv = np.asarray(z), np.asarray(mask)
-        zshape, zdt, mshape, mdt = zv.shape, zv.dtype, mv.shape, mv.dtype
+    z, mask = Operand(z), Operand(mask)
+    dev = z.device
+    if z.owner is not None and mask.owner is not None and z.owner is not mask.owner:
+        raise ArgumentError(f"{fn}: z and mask live on different contexts")
+    z.owner = z.owner or mask.owner   # the call runs where either operand lives
+    zshape, zdt, mshape, mdt = z.shape, z.dtype, mask.shape, mask.dtype
     if zdt in (np.dtype(np.complex128), np.dtype(np.float64)) or mdt in (np.dtype(np.complex128), np.dtype(np.float64)):
         raise ArgumentError(f"{fn} is an f32 extension: f64 / c128 operands are not taken (cast to complex64 / float32)")
     if dev and zdt != np.dtype(np.complex64):
@@ -634,8 +506,7 @@ def _mask_operands(z, mask, fn):
         raise ArgumentError(f"{fn}: a one-sided mask needs an even fft_length, got {K}")
     else:
         raise ArgumentError(f"{fn}: the mask's last axis must be fft_length ({K}) or fft_length / 2 + 1, got {Km}")
-    Bz = int(np.prod(zshape[:-2], dtype=np.int64)) if len(zshape) > 2 else 1
-    Bm = int(np.prod(mshape[:-2], dtype=np.int64)) if len(mshape) > 2 else 1
+    Bz, Bm = rows_last(zshape[:-1])[0], rows_last(mshape[:-1])[0]
     if Bz != Bm and Bz != 1 and Bm != 1:
         raise ArgumentError(f"{fn}: z has {Bz} rows and mask {Bm}: they must be equal, or one of them 1")
     if max(Bz, Bm) < 1:
@@ -644,10 +515,9 @@ def _mask_operands(z, mask, fn):
         raise ArgumentError(f"{fn}: at most 65535 rows")
     # the leading shape of whichever operand carries the rows (the spectrum's when both do)
     lead = tuple(zshape[:-2]) if (Bz >= Bm and (Bz > 1 or len(zshape) >= len(mshape))) else tuple(mshape[:-2])
-    if not dev:
-        zv = np.ascontiguousarray(zv.astype(np.complex64))
-        mv = np.ascontiguousarray(mv.astype(np.complex64 if cplx else np.float32))
-    return dev, zv, mv, (M, K), kind, (Bz, Bm), tuple(int(d) for d in lead)
+    z.cast(np.complex64)
+    mask.cast(np.complex64 if cplx else np.float32)
+    return z, mask, (M, K), kind, (Bz, Bm), tuple(int(d) for d in lead)
 
 
 def spectrum_mask(z, mask, ctx: Context | None = None):
@@ -655,16 +525,11 @@ def spectrum_mask(z, mask, ctx: Context | None = None):
     c64[..., M, K] or the one-sided real f32[..., M, K/2 + 1] (bin k > K/2 takes mask[K - k]).  The flattened leading axes are equal
     or one of them is 1 (broadcast: one mixture and S masks).  Complex masks multiply like spectrum_multiply; a real gain
     multiplies each component on its own, in double with one rounding.  -> c64[lead..., M, K], host or DeviceBuffer like the inputs."""
-    dev, zv, mv, (M, K), kind, (Bz, Bm), lead = _mask_operands(z, mask, "spectrum_mask")
+    z, mask, (M, K), kind, (Bz, Bm), lead = _mask_operands(z, mask, "spectrum_mask")
     lib = _lib.load()
-    c = _ctx_of(z if isinstance(z, DeviceBuffer) else (mask if isinstance(mask, DeviceBuffer) else None), ctx)
-    if dev:
-        out = c.empty(lead + (M, K), np.complex64)
-        _lib.check(lib.nxsig_spectrum_mask_c64(c.handle, C.c_void_p(zv[0]), Bz, C.c_void_p(mv[0]), kind, Bm, M, K,
-                                               C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    out = np.empty(lead + (M, K), dtype=np.complex64)
-    _lib.check(lib.nxsig_spectrum_mask_c64(c.handle, _as_ptr(zv), Bz, _as_ptr(mv), kind, Bm, M, K, _as_ptr(out), _lib.HOST))
+    c = z.context(ctx, caller_first=True)
+    out = z.result(lead + (M, K), np.complex64)
+    _lib.check(lib.nxsig_spectrum_mask_c64(c.handle, z.ptr, Bz, mask.ptr, kind, Bm, M, K, ptr(out), z.mem))
     return out
 
 
@@ -677,21 +542,16 @@ def istft_masked(z, mask, window, ctx: Context | None = None, **opts):
     o, w, N, hop, fs = _istft_options(window, opts)
     if w.dtype == np.float64:
         raise ArgumentError("istft_masked is an f32 extension: an f64 window is not taken")
-    dev, zv, mv, (M, K), kind, (Bz, Bm), lead = _mask_operands(z, mask, "istft_masked")
+    z, mask, (M, K), kind, (Bz, Bm), lead = _mask_operands(z, mask, "istft_masked")
     K = _istft_fft_length(o, K)
     if K != N:
         raise ArgumentError("istft: fft_length must equal the window length (the reference broadcasts {M,K} x {N}, lib/nx_signal.ex:628)")
     lib = _lib.load()
-    c = _ctx_of(z if isinstance(z, DeviceBuffer) else (mask if isinstance(mask, DeviceBuffer) else None), ctx)
+    c = z.context(ctx, caller_first=True)
     p = StftParams(N, hop, K, 0, 0, 0, _SCALING[o["scaling"]], 0, fs)
     out_len = _lib.check(lib.nxsig_ola_length(M, N, hop))
-    if dev:
-        y = c.empty(lead + (out_len,), np.complex64)
-        _lib.check(lib.nxsig_istft_masked_c64(c.handle, C.c_void_p(zv[0]), Bz, M, _as_ptr(w), C.byref(p), C.c_void_p(mv[0]), kind, Bm,
-                                              C.c_void_p(y.ptr), _lib.DEVICE))
-        return y
-    y = np.empty(lead + (out_len,), dtype=np.complex64)
-    _lib.check(lib.nxsig_istft_masked_c64(c.handle, _as_ptr(zv), Bz, M, _as_ptr(w), C.byref(p), _as_ptr(mv), kind, Bm, _as_ptr(y), _lib.HOST))
+    y = z.result(lead + (out_len,), np.complex64)
+    _lib.check(lib.nxsig_istft_masked_c64(c.handle, z.ptr, Bz, M, ptr(w), C.byref(p), mask.ptr, kind, Bm, ptr(y), z.mem))
     return y
 
 
@@ -701,53 +561,32 @@ def mel_spectrogram(data, window, ctx: Context | None = None, **opts):
     :mel_frequency_spacing.  Returns f32[..., frames, mel_bins], equal to the two-step result to fp32 rounding."""
     mel_keys = {"mel_bins": 128, "max_mel": None, "mel_frequency_spacing": None}
     mo = {k: opts.pop(k) for k in list(opts) if k in mel_keys}
-    o = _validate(
-        opts,
-        {"overlap_length": None, "window": None, "scaling": None, "window_padding": "valid", "sampling_rate": 100,
-         "fft_length": "power_of_two"},
-        "mel_spectrogram",
-    )
+    p, N, hop, K = _resolve_stft_opts(window, opts, "mel_spectrogram")
     w = _window_host(window)
-    N = int(w.shape[0])
-    fs = float(o["sampling_rate"])
-    overlap = N // 2 if o["overlap_length"] is None else int(o["overlap_length"])
-    hop = N - overlap
-    if o["scaling"] not in _SCALING:
-        raise ArgumentError(f"invalid :scaling, expected one of :spectrum, :psd or nil, got: {o['scaling']!r}")
-    mode, lo, hi = _pad_args(o["window_padding"])
-    K = _resolve_fft_length(o["fft_length"], N)
     mb = int(mo.get("mel_bins", 128))
     fopts = {k: mo[k] for k in ("max_mel", "mel_frequency_spacing") if mo.get(k) is not None}
-    filt = _mel_filters_for(K, mb, fs, fopts)
-    p = StftParams(N, hop, K, mode, lo, hi, _SCALING[o["scaling"]], 0, fs)
-    lib = _lib.load()
+    filt = _mel_filters_for(K, mb, p.sampling_rate, fopts)
     M = C.c_int64()
-    if is_device(data):
-        ptr, shape, dt = device_view(data)
-        if dt != np.float32:
-            raise ArgumentError("mel_spectrogram: device input must be float32")
-        c = _ctx_of(data, ctx)
-        L = shape[-1]
-        batch = int(np.prod(shape[:-1], dtype=np.int64)) if len(shape) > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-        out = c.empty(tuple(shape[:-1]) + (m, mb), np.float32)
-        _lib.check(lib.nxsig_stft_mel_f32(c.handle, C.c_void_p(ptr), L, batch, L, _as_ptr(w), C.byref(p), mb, _as_ptr(filt),
-                                          C.c_void_p(out.ptr), C.byref(M), _lib.DEVICE))
-        return out
-    x = _host_f32(data, "mel_spectrogram")
-    c = _ctx_of(None, ctx)
-    L = x.shape[-1]
-    batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-    m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-    out = np.empty(x.shape[:-1] + (m, mb), dtype=np.float32)
-    _lib.check(lib.nxsig_stft_mel_f32(c.handle, _as_ptr(x), L, batch, L, _as_ptr(w), C.byref(p), mb, _as_ptr(filt), _as_ptr(out),
-                                      C.byref(M), _lib.HOST))
+    x = _real_f32(data, "mel_spectrogram")
+    c, batch, L, m = _frames(x, ctx, p)
+    out = x.result(x.shape[:-1] + (m, mb), np.float32)
+    _lib.check(_lib.load().nxsig_stft_mel_f32(c.handle, x.ptr, L, batch, L, ptr(w), C.byref(p), mb, ptr(filt), ptr(out), C.byref(M), x.mem))
     return out
+
+
+def _real_f32(data, fn) -> Operand:
+    """the operand of the fused f32 extensions: a device tensor of f32, or a host array by the rule of _host_f32"""
+    x = Operand(data)
+    if not x.device:
+        return _host_f32(x, fn)
+    if x.dtype != np.float32:
+        raise ArgumentError(f"{fn}: device input must be float32")
+    return x
 
 
 def _stft_times(m: int, N: int, fs: float) -> np.ndarray:
     times = np.empty(m, dtype=np.float32)
-    _lib.check(_lib.load().nxsig_stft_times_f32(N, fs, m, _as_ptr(times)))
+    _lib.check(_lib.load().nxsig_stft_times_f32(N, fs, m, ptr(times)))
     return times
 
 
@@ -763,47 +602,17 @@ def spectrogram(data, window, ctx: Context | None = None, **opts):
     kind = opts.pop("kind", "magnitude")
     if kind not in _MAG_KINDS:
         raise ArgumentError(f"invalid :kind, expected one of {list(_MAG_KINDS)}, got: {kind!r}")
-    o = _validate(
-        opts,
-        {"overlap_length": None, "window": None, "scaling": None, "window_padding": "valid", "sampling_rate": 100,
-         "fft_length": "power_of_two"},
-        "spectrogram",
-    )
+    p, N, hop, K = _resolve_stft_opts(window, opts, "spectrogram")
     w = _window_host(window)
-    N = int(w.shape[0])
-    fs = float(o["sampling_rate"])
-    overlap = N // 2 if o["overlap_length"] is None else int(o["overlap_length"])
-    hop = N - overlap
-    if o["scaling"] not in _SCALING:
-        raise ArgumentError(f"invalid :scaling, expected one of :spectrum, :psd or nil, got: {o['scaling']!r}")
-    mode, lo, hi = _pad_args(o["window_padding"])
-    K = _resolve_fft_length(o["fft_length"], N)
     half = K // 2
-    p = StftParams(N, hop, K, mode, lo, hi, _SCALING[o["scaling"]], 0, fs)
-    lib = _lib.load()
     M = C.c_int64()
-    f = fft_frequencies(fs, fft_length=K)[:half]
-    if is_device(data):
-        ptr, shape, dt = device_view(data)
-        if dt != np.float32:
-            raise ArgumentError("spectrogram: device input must be float32")
-        c = _ctx_of(data, ctx)
-        L = shape[-1]
-        batch = int(np.prod(shape[:-1], dtype=np.int64)) if len(shape) > 1 else 1
-        m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-        out = c.empty(tuple(shape[:-1]) + (m, half), np.float32)
-        _lib.check(lib.nxsig_stft_magnitude_f32(c.handle, C.c_void_p(ptr), L, batch, L, _as_ptr(w), C.byref(p), _MAG_KINDS[kind],
-                                                C.c_void_p(out.ptr), C.byref(M), _lib.DEVICE))
-        return out, _stft_times(m, N, fs), f
-    x = _host_f32(data, "spectrogram")
-    c = _ctx_of(None, ctx)
-    L = x.shape[-1]
-    batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-    m = _lib.check(lib.nxsig_num_frames(L, N, hop, mode, lo, hi))
-    out = np.empty(x.shape[:-1] + (m, half), dtype=np.float32)
-    _lib.check(lib.nxsig_stft_magnitude_f32(c.handle, _as_ptr(x), L, batch, L, _as_ptr(w), C.byref(p), _MAG_KINDS[kind], _as_ptr(out),
-                                            C.byref(M), _lib.HOST))
-    return out, _stft_times(m, N, fs), f
+    f = fft_frequencies(p.sampling_rate, fft_length=K)[:half]
+    x = _real_f32(data, "spectrogram")
+    c, batch, L, m = _frames(x, ctx, p)
+    out = x.result(x.shape[:-1] + (m, half), np.float32)
+    _lib.check(_lib.load().nxsig_stft_magnitude_f32(c.handle, x.ptr, L, batch, L, ptr(w), C.byref(p), _MAG_KINDS[kind], ptr(out), C.byref(M),
+                                                    x.mem))
+    return out, _stft_times(m, N, p.sampling_rate), f
 
 
 from . import convolution, filters, peak_finding, spectral, transforms, waveforms, windows  # noqa: E402,F401

@@ -13,18 +13,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, NxSignalUnsupported
-from .device import default_context, device_view, is_device
+from ._marshal import Operand, _as_tensor, is_device, ptr, rows_last, validate
 
 _MODES = {"full": _lib.CONV_FULL, "same": _lib.CONV_SAME, "valid": _lib.CONV_VALID}
 
 
 def convolve(in1, in2, ctx=None, **opts):
-    allowed = {"mode": "full", "method": "direct"}
-    unknown = [k for k in opts if k not in allowed]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in convolve options, the allowed keys are: {list(allowed)}")
-    o = dict(allowed)
-    o.update(opts)
+    o = validate(opts, {"mode": "full", "method": "direct"}, "convolve")
     if o["mode"] not in _MODES:  # convolution.ex:41-44 (mode is validated before method, quirk B12)
         raise ArgumentError(f"expected mode to be one of [:full, :same, :valid], got: {o['mode']!r}")
     if o["method"] not in ("direct", "fft"):  # :46-49
@@ -44,14 +39,20 @@ def _convolve_direct(in1, in2, mode, ctx):
             raise ArgumentError(f"Incompatible ranks: {{{a.ndim}, {b.ndim}}}")
         raise ArgumentError("NxSignal.convolve/3 requires both inputs to have the same rank or one of them to be a scalar, "
                             f"got {a.ndim} and {b.ndim}")
+    scalar = a.ndim == 0
+    res = _nd(_lib.load().nxsig_convolve_direct, a, b, mode, ctx, "convolve", scalar, max_rank=8)
+    return res.reshape(()) if scalar else res
+
+
+def _nd(entry, a, b, mode, ctx, fn, scalar=False, max_rank=None):
+    """the two n-D entry points (host operands of equal rank): f32 / c64 operands and their shapes in, the result's shape out"""
     for t in (a, b):
         if t.dtype in (np.float64, np.complex128):
-            raise ArgumentError("convolve: f64 / c128 is outside this path (f32 / c64); cast explicitly")
-    scalar = a.ndim == 0
+            raise ArgumentError(f"{fn}: f64 / c128 is outside this path (f32 / c64); cast explicitly")
     if scalar:
         a, b = a.reshape(1), b.reshape(1)
-    if a.ndim > 8:
-        raise NxSignalUnsupported("convolve: rank > 8")
+    if max_rank is not None and a.ndim > max_rank:
+        raise NxSignalUnsupported(f"{fn}: rank > {max_rank}")
     a_real, b_real = not np.iscomplexobj(a), not np.iscomplexobj(b)
     ac = np.ascontiguousarray(a.astype(np.float32 if a_real else np.complex64))
     bc = np.ascontiguousarray(b.astype(np.float32 if b_real else np.complex64))
@@ -59,13 +60,11 @@ def _convolve_direct(in1, in2, mode, ctx):
     s1 = (C.c_int64 * rank)(*ac.shape)
     s2 = (C.c_int64 * rank)(*bc.shape)
     osh = (C.c_int64 * rank)()
-    out = np.empty([x + y - 1 for x, y in zip(ac.shape, bc.shape)], np.float32 if (a_real and b_real) else np.complex64)
-    c = ctx or default_context()
-    _lib.check(_lib.load().nxsig_convolve_direct(c.handle, ac.ctypes.data_as(C.c_void_p), int(a_real), s1, bc.ctypes.data_as(C.c_void_p),
-                                                 int(b_real), s2, rank, _MODES[mode], out.ctypes.data_as(C.c_void_p), osh, _lib.HOST))
+    out = np.empty([x + y - 1 for x, y in zip(ac.shape, bc.shape)], np.float32 if (a_real and b_real) else np.complex64)  # every mode's result fits
+    c = Operand(ac).context(ctx, caller_first=True)
+    _lib.check(entry(c.handle, ptr(ac), int(a_real), s1, ptr(bc), int(b_real), s2, rank, _MODES[mode], ptr(out), osh, _lib.HOST))
     shape = tuple(int(v) for v in osh)
-    res = out.reshape(-1)[: int(np.prod(shape))].reshape(shape).copy()
-    return res.reshape(()) if scalar else res
+    return out.reshape(-1)[: int(np.prod(shape))].reshape(shape).copy()
 
 
 def correlate(in1, in2, ctx=None, **opts):
@@ -80,24 +79,7 @@ def correlate(in1, in2, ctx=None, **opts):
 
 def _fftconvolve_nd(a, b, mode, ctx):
     """equal-rank n-D operands (host): nxsig_fftconvolve_nd"""
-    lib = _lib.load()
-    for t in (a, b):
-        if t.dtype in (np.float64, np.complex128):
-            raise ArgumentError("fftconvolve: f64 / c128 is outside this path (f32 / c64); cast explicitly")
-    a_real, b_real = not np.iscomplexobj(a), not np.iscomplexobj(b)
-    ac = np.ascontiguousarray(a.astype(np.float32 if a_real else np.complex64))
-    bc = np.ascontiguousarray(b.astype(np.float32 if b_real else np.complex64))
-    rank = ac.ndim
-    s1 = (C.c_int64 * rank)(*ac.shape)
-    s2 = (C.c_int64 * rank)(*bc.shape)
-    osh = (C.c_int64 * rank)()
-    full = [x + y - 1 for x, y in zip(ac.shape, bc.shape)]
-    out = np.empty(full, np.float32 if (a_real and b_real) else np.complex64)  # every mode's result fits
-    c = ctx or default_context()
-    _lib.check(lib.nxsig_fftconvolve_nd(c.handle, ac.ctypes.data_as(C.c_void_p), int(a_real), s1, bc.ctypes.data_as(C.c_void_p),
-                                        int(b_real), s2, rank, _MODES[mode], out.ctypes.data_as(C.c_void_p), osh, _lib.HOST))
-    shape = tuple(int(v) for v in osh)
-    return out.reshape(-1)[: int(np.prod(shape))].reshape(shape).copy()
+    return _nd(_lib.load().nxsig_fftconvolve_nd, a, b, mode, ctx, "fftconvolve")
 
 
 def _fftconvolve_f64(a, h, mode, ctx):
@@ -113,33 +95,31 @@ def _fftconvolve_f64(a, h, mode, ctx):
             start = (full.shape[0] - a.shape[0]) // 2
             return full[start:start + a.shape[0]]
         x, h64 = h64, x
-    c = ctx or default_context()
-    L = int(x.shape[-1])
-    batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-    n_out = _lib.check(lib.nxsig_conv_length(L, h64.size, _MODES[mode]))
-    y = np.empty(x.shape[:-1] + (n_out,), dtype=np.float64)
-    _lib.check(lib.nxsig_fir_f64(c.handle, x.ctypes.data_as(C.c_void_p), L, batch, L, h64.ctypes.data_as(C.c_void_p), h64.size,
-                                 _MODES[mode], y.ctypes.data_as(C.c_void_p), _lib.HOST))
+    return _fir(lib.nxsig_fir_f64, Operand(x), h64, mode, ctx)
+
+
+def _fir(entry, x, h, mode, ctx):
+    """rows of x against the taps h (host, x's precision) over the last axis: nxsig_fir_f32 / nxsig_fir_f64"""
+    c = x.context(ctx, caller_first=True)
+    batch, L = rows_last(x.shape)
+    n_out = _lib.check(_lib.load().nxsig_conv_length(L, h.size, _MODES[mode]))
+    y = x.result(x.shape[:-1] + (n_out,), x.dtype)
+    _lib.check(entry(c.handle, x.ptr, L, batch, L, ptr(h), h.size, _MODES[mode], ptr(y), x.mem))
     return y
 
 
 def fftconvolve(in1, in2, ctx=None, **opts):
     """1-D real case of fftconvolve: the longer operand streams through HBM, the shorter one is the FIR kernel.
     in1 may carry leading batch axes (independent channels) when it is the signal."""
-    allowed = {"mode": "full", "method": "direct"}  # :method accepted and ignored (quirk B12)
-    unknown = [k for k in opts if k not in allowed]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in fftconvolve options, the allowed keys are: {list(allowed)}")
+    validate(opts, ("mode", "method"), "fftconvolve")  # :method accepted and ignored (quirk B12)
     mode = opts.get("mode", "full")
     if mode not in _MODES:
         raise ArgumentError(f"expected mode to be one of [:full, :same, :valid], got: {mode!r}")
     lib = _lib.load()
-    from . import _as_tensor   # Python numbers / lists follow Nx.tensor's inference (f32); np.float64 arrays are f64
-    in1, in2 = _as_tensor(in1), _as_tensor(in2)
-    dev = is_device(in1)
-    h = np.asarray(in2) if not is_device(in2) else None
-    if h is None:
+    in1, in2 = _as_tensor(in1), _as_tensor(in2)   # Python numbers / lists follow Nx.tensor's inference (f32); np.float64 arrays are f64
+    if is_device(in2):
         raise ArgumentError("fftconvolve: the second operand (filter taps) must be a host tensor")
+    dev, h = is_device(in1), np.asarray(in2)
     if np.iscomplexobj(h) or (not dev and np.iscomplexobj(np.asarray(in1))):
         if dev:
             raise NxSignalUnsupported("complex fftconvolve takes host tensors")
@@ -150,13 +130,12 @@ def fftconvolve(in1, in2, ctx=None, **opts):
             return _fftconvolve_nd(a, h, mode, ctx)
         if a.dtype == np.complex128 or h.dtype == np.complex128:
             raise ArgumentError("fftconvolve: complex128 is outside this path (f32/c64); cast to complex64 explicitly")
-        ac = np.ascontiguousarray(a.astype(np.complex64))
+        x = Operand(a).cast(np.complex64)
         bc = np.ascontiguousarray(h.astype(np.complex64))
-        n_out = _lib.check(lib.nxsig_conv_length(ac.size, bc.size, _MODES[mode]))
-        out = np.empty(n_out, dtype=np.complex64)
-        c = ctx or default_context()
-        _lib.check(lib.nxsig_fftconvolve_c64(c.handle, ac.ctypes.data_as(C.c_void_p), ac.size, bc.ctypes.data_as(C.c_void_p),
-                                             bc.size, _MODES[mode], out.ctypes.data_as(C.c_void_p), _lib.HOST))
+        n_out = _lib.check(lib.nxsig_conv_length(x.host.size, bc.size, _MODES[mode]))
+        out = x.result(n_out, np.complex64)
+        c = x.context(ctx, caller_first=True)
+        _lib.check(lib.nxsig_fftconvolve_c64(c.handle, x.ptr, x.host.size, ptr(bc), bc.size, _MODES[mode], ptr(out), x.mem))
         return out
     if h.ndim != 1:
         if dev:
@@ -166,37 +145,23 @@ def fftconvolve(in1, in2, ctx=None, **opts):
             raise ArgumentError("Rank of in1 and in2 must be equal.")
         return _fftconvolve_nd(a, h, mode, ctx)
     h32 = np.ascontiguousarray(h.astype(np.float32))
+    x = Operand(in1)
     if dev:
-        ptr, shape, dt = device_view(in1)
-        if dt != np.float32:
+        if x.dtype != np.float32:
             raise ArgumentError("fftconvolve: device input must be float32")
-        c = ctx or getattr(in1, "ctx", None) or default_context()
-        L = int(shape[-1])
-        batch = int(np.prod(shape[:-1], dtype=np.int64)) if len(shape) > 1 else 1
-        n_out = _lib.check(lib.nxsig_conv_length(L, h32.size, _MODES[mode]))
-        y = c.empty(tuple(shape[:-1]) + (n_out,), np.float32)
-        _lib.check(lib.nxsig_fir_f32(c.handle, C.c_void_p(ptr), L, batch, L, h32.ctypes.data_as(C.c_void_p), h32.size,
-                                     _MODES[mode], C.c_void_p(y.ptr), _lib.DEVICE))
-        return y
-    a = np.asarray(in1)
-    if a.ndim != 1 and a.ndim != h.ndim and a.ndim < 1:
+        return _fir(lib.nxsig_fir_f32, x, h32, mode, ctx)
+    a = x.host
+    if a.ndim < 1:
         raise ArgumentError("Rank of in1 and in2 must be equal.")
     if a.dtype == np.float64 or h.dtype == np.float64:
         return _fftconvolve_f64(a, h, mode, ctx)
-    x = np.ascontiguousarray(a.astype(np.float32))
-    if x.ndim == 1 and x.shape[0] < h32.shape[0]:
-        x, h32 = h32, x  # convolution commutes; keep the longer operand as the stream
+    x.cast(np.float32)
+    if len(x.shape) == 1 and x.shape[0] < h32.shape[0]:
         if mode == "same":
             # :same is centred on in1 (convolution.ex:304-306): compute full and slice like the reference
-            full = fftconvolve(x, h32, ctx=ctx, mode="full")
+            full = fftconvolve(h32, x.host, ctx=ctx, mode="full")
             new = a.shape[0]
             start = (full.shape[0] - new) // 2
             return full[start:start + new]
-    c = ctx or default_context()
-    L = int(x.shape[-1])
-    batch = int(np.prod(x.shape[:-1], dtype=np.int64)) if x.ndim > 1 else 1
-    n_out = _lib.check(lib.nxsig_conv_length(L, h32.size, _MODES[mode]))
-    y = np.empty(x.shape[:-1] + (n_out,), dtype=np.float32)
-    _lib.check(lib.nxsig_fir_f32(c.handle, x.ctypes.data_as(C.c_void_p), L, batch, L, h32.ctypes.data_as(C.c_void_p),
-                                 h32.size, _MODES[mode], y.ctypes.data_as(C.c_void_p), _lib.HOST))
-    return y
+        x, h32 = Operand(h32), x.host  # convolution commutes; keep the longer operand as the stream
+    return _fir(lib.nxsig_fir_f32, x, h32, mode, ctx)

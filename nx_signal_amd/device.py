@@ -175,8 +175,9 @@ def is_device(obj) -> bool:
     return isinstance(obj, DeviceBuffer) or hasattr(obj, "data_ptr") or hasattr(obj, "__cuda_array_interface__")
 
 
-def device_view(obj):
-    """(ptr, shape, dtype) of a device-resident object (DeviceBuffer, torch tensor, CUDA array interface)."""
+def device_view(obj, any_dtype=False):
+    """(ptr, shape, dtype) of a device-resident object (DeviceBuffer, torch tensor, CUDA array interface).  A torch tensor must be f32
+    or c64, or with any_dtype (PeakFinding: integer tensors) of any type numpy has a name for."""
     if isinstance(obj, DeviceBuffer):
         return obj.ptr, obj.shape, obj.dtype
     if hasattr(obj, "__cuda_array_interface__"):
@@ -187,9 +188,15 @@ def device_view(obj):
     if hasattr(obj, "data_ptr"):  # torch tensor
         if not obj.is_contiguous():
             raise _lib.ArgumentError("device inputs must be contiguous")
-        import torch  # only reached when the caller already uses torch
+        if any_dtype:
+            try:
+                dt = np.dtype(str(obj.dtype).replace("torch.", ""))
+            except TypeError:
+                dt = None
+        else:
+            import torch  # only reached when the caller already uses torch
 
-        dt = {torch.float32: np.float32, torch.complex64: np.complex64}.get(obj.dtype)
+            dt = {torch.float32: np.float32, torch.complex64: np.complex64}.get(obj.dtype)
         if dt is None:
             raise _lib.ArgumentError(f"unsupported device dtype {obj.dtype}")
         return int(obj.data_ptr()), tuple(obj.shape), np.dtype(dt)

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib, convolution
 from ._lib import ArgumentError, NxSignalUnsupported
-from .device import DeviceBuffer, default_context, device_view, is_device
+from ._marshal import Operand, ptr, rows_last, validate
 
 _WINDOWS = {
     "hamming": _lib.WIN_HAMMING, "hann": _lib.WIN_HANN, "blackman": _lib.WIN_BLACKMAN,
@@ -19,12 +19,7 @@ _WINDOWS = {
 def firwin(num_taps, cutoff, **opts):
     """Window-method FIR design.  `cutoff` must be a list (quirk B13); window one of "hamming", "hann",
     "blackman", "bartlett", "rectangular" or ("kaiser", beta)."""
-    allowed = {"window": "hamming", "pass_zero": True, "scale": True, "sampling_rate": 2.0, "type": "f32"}
-    unknown = [k for k in opts if k not in allowed]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in firwin options, the allowed keys are: {list(allowed)}")
-    o = dict(allowed)
-    o.update(opts)
+    o = validate(opts, {"window": "hamming", "pass_zero": True, "scale": True, "sampling_rate": 2.0, "type": "f32"}, "firwin")
     if not isinstance(cutoff, (list, tuple)):  # filters.ex:160-162
         raise ArgumentError(f"cutoff must be a list of frequencies, got: {cutoff!r}")
     win, beta = o["window"], 0.0
@@ -42,9 +37,8 @@ def firwin(num_taps, cutoff, **opts):
     cut = (C.c_double * len(cutoff))(*[float(c) for c in cutoff])
     out = np.empty(int(num_taps), dtype=np.float64 if f64 else np.float32)
     entry = _lib.load().nxsig_firwin_f64 if f64 else _lib.load().nxsig_firwin_f32
-    _lib.check(entry(int(num_taps), cut, len(cutoff), kind, beta, int(bool(o["pass_zero"])),
-                                            int(bool(o["scale"])), float(o["sampling_rate"]),
-                                            out.ctypes.data_as(C.c_void_p)))
+    _lib.check(entry(int(num_taps), cut, len(cutoff), kind, beta, int(bool(o["pass_zero"])), int(bool(o["scale"])), float(o["sampling_rate"]),
+                     ptr(out)))
     return out
 
 
@@ -55,29 +49,15 @@ def fir(x, taps, mode="same", ctx=None):
     return convolution.convolve(x, taps, mode=mode, method="fft", ctx=ctx)
 
 
-def _tensor(t):
-    """(host array or None, device (ptr, shape, dtype) or None) of a filter input"""
-    if is_device(t):
-        return None, device_view(t)
-    return np.asarray(t), None
-
-
-def _unknown(opts, allowed, fn):
-    unknown = [k for k in opts if k not in allowed]
-    if unknown:   # Keyword.validate!
-        raise ArgumentError(f"unknown keys {unknown} in {fn} options, the allowed keys are: {list(allowed)}")
-
-
 def median(t, ctx=None, **opts):
     """Filters.median/2 — lib/nx_signal/filters.ex:17-55.  median(t, kernel_shape=(k_0, ..., k_{r-1})): the median of the window of
     kernel_shape that starts at min(i_d, n_d - k_d) on every axis (no padding), as f32 of t's shape.  Host arrays of any real type
     (integers are computed like f64) or a device tensor of f32 / f64, which gives a device tensor back.  Order like np.sort: NaN
     above +Inf, -0.0 == +0.0; even windows average the two middle values in the input's type."""
-    _unknown(opts, ("kernel_shape",), "median")
+    validate(opts, ("kernel_shape",), "median")
     ks = opts.get("kernel_shape")
-    host, dev = _tensor(t)
-    shape = tuple(host.shape) if dev is None else tuple(dev[1])
-    dtype = host.dtype if dev is None else np.dtype(dev[2])
+    x = Operand(t)
+    shape, dtype = x.shape, x.dtype
     if not isinstance(ks, tuple) or len(ks) != len(shape):   # filters.ex:38-40
         raise ArgumentError("kernel shape must be of the same rank as the tensor")
     if dtype.kind == "c":
@@ -93,19 +73,12 @@ def median(t, ctx=None, **opts):
     is_f64 = dtype != np.float32
     sh = (C.c_int64 * len(shape))(*shape)
     kc = (C.c_int64 * len(shape))(*ks)
-    lib = _lib.load()
-    if dev is not None:
-        if dtype not in (np.float32, np.float64):
-            raise ArgumentError(f"median: device tensors must be f32 or f64, got {dtype}")
-        c = t.ctx if isinstance(t, DeviceBuffer) else (ctx or default_context())
-        out = DeviceBuffer.empty(c, shape, np.float32)
-        _lib.check(lib.nxsig_median_filter(c.handle, C.c_void_p(dev[0]), int(is_f64), sh, len(shape), kc, C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    x = np.ascontiguousarray(host, dtype=np.float64 if is_f64 else np.float32)
-    out = np.empty(shape, np.float32)
-    c = ctx or default_context()
-    _lib.check(lib.nxsig_median_filter(c.handle, x.ctypes.data_as(C.c_void_p), int(is_f64), sh, len(shape), kc,
-                                       out.ctypes.data_as(C.c_void_p), _lib.HOST))
+    if x.device and dtype not in (np.float32, np.float64):
+        raise ArgumentError(f"median: device tensors must be f32 or f64, got {dtype}")
+    x.cast(np.float64 if is_f64 else np.float32)
+    c = x.context(ctx, caller_first=False)
+    out = x.result(shape, np.float32)
+    _lib.check(_lib.load().nxsig_median_filter(c.handle, x.ptr, int(is_f64), sh, len(shape), kc, ptr(out), x.mem))
     return out
 
 
@@ -113,12 +86,11 @@ def wiener(t, ctx=None, return_noise=False, **opts):
     """Filters.wiener/2 — lib/nx_signal/filters.ex:81-110, :281-303.  wiener(t, kernel_size=3, noise=None): local mean and variance
     over the :same-padded window in f64, then the Wiener formula; the result has t's type (f32 or f64, host or device).  noise=None
     estimates it as the mean local variance.  return_noise=True also returns the noise the formula used."""
-    _unknown(opts, ("noise", "kernel_size"), "wiener")
+    validate(opts, ("noise", "kernel_size"), "wiener")
     ks = opts.get("kernel_size", 3)
     noise = opts.get("noise")
-    host, dev = _tensor(t)
-    shape = tuple(host.shape) if dev is None else tuple(dev[1])
-    dtype = host.dtype if dev is None else np.dtype(dev[2])
+    x = Operand(t)
+    shape, dtype = x.shape, x.dtype
     rank = len(shape)
     if isinstance(ks, (int, np.integer)) and not isinstance(ks, bool):
         ks = (int(ks),) * rank
@@ -135,24 +107,32 @@ def wiener(t, ctx=None, return_noise=False, **opts):
         raise NxSignalUnsupported(f"wiener: f32 and f64 tensors are built, got {dtype}")
     if not 1 <= rank <= 8:
         raise ArgumentError("wiener: rank must be in [1, 8]")
-    is_f64 = dtype == np.float64
     sh = (C.c_int64 * rank)(*shape)
     kc = (C.c_int64 * rank)(*ks)
     used = C.c_double(0.0)
-    args = (int(noise is not None), float(noise) if noise is not None else 0.0)
-    lib = _lib.load()
-    if dev is not None:
-        c = t.ctx if isinstance(t, DeviceBuffer) else (ctx or default_context())
-        out = DeviceBuffer.empty(c, shape, dtype)
-        _lib.check(lib.nxsig_wiener(c.handle, C.c_void_p(dev[0]), int(is_f64), sh, rank, kc, *args, C.c_void_p(out.ptr),
-                                    C.byref(used) if return_noise else None, _lib.DEVICE))
-    else:
-        x = np.ascontiguousarray(host)
-        out = np.empty(shape, dtype)
-        c = ctx or default_context()
-        _lib.check(lib.nxsig_wiener(c.handle, x.ctypes.data_as(C.c_void_p), int(is_f64), sh, rank, kc, *args, out.ctypes.data_as(C.c_void_p),
-                                    C.byref(used) if return_noise else None, _lib.HOST))
+    x.cast()
+    c = x.context(ctx, caller_first=False)
+    out = x.result(shape, dtype)
+    _lib.check(_lib.load().nxsig_wiener(c.handle, x.ptr, int(dtype == np.float64), sh, rank, kc, int(noise is not None),
+                                        float(noise) if noise is not None else 0.0, ptr(out), C.byref(used) if return_noise else None, x.mem))
     return (out, used.value) if return_noise else out
+
+
+def _axis_last(x, axis, fn, device_error):
+    """`axis` of operand x, validated and counted from the front.  A host array gets that axis at the back; a device tensor is taken
+    along its last axis only (else device_error)."""
+    rank = len(x.shape)
+    if rank < 1:
+        raise ArgumentError(f"{fn}: the tensor must have at least one axis")
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not -rank <= axis < rank:
+        raise ArgumentError(f"{fn}: axis {axis!r} is out of bounds for a tensor of rank {rank}")
+    axis = int(axis) % rank
+    if any(s < 1 for s in x.shape):
+        raise ArgumentError(f"{fn}: empty dimension")
+    if x.device and axis != rank - 1:
+        raise device_error
+    x.move_last(axis)
+    return axis
 
 
 _RESAMPLE_KEYS = ("ctx", "axis", "window", "taps", "padtype")
@@ -189,7 +169,7 @@ def resample_poly(x, up, down, ctx=None, axis=-1, window=("kaiser", 5.0), taps=N
     filter is resample_poly_taps(up, down, window); taps: a 1-D real array instead (scipy's array form of `window=`, WITHOUT the
     gain: h = up * taps).  up == down after reduction returns a copy.  Host arrays: any axis, numpy out; a device tensor: the last
     axis only, a DeviceBuffer out.  An Inf / NaN sample reaches the outputs whose taps cover it and nothing else."""
-    _unknown(opts, _RESAMPLE_KEYS, "resample_poly")
+    validate(opts, _RESAMPLE_KEYS, "resample_poly")
     up, down = _resample_ratio(up, down)
     if padtype != "constant":
         raise ArgumentError(f"resample_poly: only padtype \"constant\" is built, got: {padtype!r}")
@@ -205,41 +185,18 @@ def resample_poly(x, up, down, ctx=None, axis=-1, window=("kaiser", 5.0), taps=N
     else:
         firwin(3, [0.5], window=window)   # the window is validated although nothing is filtered
         h = np.ones(1, np.float32)
-    host, dev = _tensor(x)
-    shape = tuple(host.shape) if dev is None else tuple(dev[1])
-    dtype = host.dtype if dev is None else np.dtype(dev[2])
-    if dtype not in (np.float32, np.complex64):
-        raise NxSignalUnsupported(f"resample_poly: f32 and c64 tensors are built, got {dtype}")
-    rank = len(shape)
-    if rank < 1:
-        raise ArgumentError("resample_poly: the tensor must have at least one axis")
-    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not -rank <= axis < rank:
-        raise ArgumentError(f"resample_poly: axis {axis!r} is out of bounds for a tensor of rank {rank}")
-    axis = int(axis) % rank
-    if any(s < 1 for s in shape):
-        raise ArgumentError("resample_poly: empty dimension")
+    x = Operand(x)
+    if x.dtype not in (np.float32, np.complex64):
+        raise NxSignalUnsupported(f"resample_poly: f32 and c64 tensors are built, got {x.dtype}")
+    axis = _axis_last(x, axis, "resample_poly", ArgumentError("resample_poly: device tensors are resampled along their last axis only"))
     lib = _lib.load()
-    is_c = int(dtype == np.complex64)
-    if dev is not None:
-        if axis != rank - 1:
-            raise ArgumentError("resample_poly: device tensors are resampled along their last axis only")
-        n = shape[-1]
-        n_out = _lib.check(lib.nxsig_resample_length(n, up, down))
-        batch = int(np.prod(shape[:-1], dtype=np.int64))
-        c = x.ctx if isinstance(x, DeviceBuffer) else (ctx or default_context())
-        out = DeviceBuffer.empty(c, shape[:-1] + (n_out,), dtype)
-        _lib.check(lib.nxsig_resample_poly(_lib.ctx_ptr(c.handle), C.c_void_p(dev[0]), is_c, n, batch, n, h.ctypes.data_as(C.c_void_p), h.shape[0],
-                                           up, down, C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    xs = np.ascontiguousarray(np.moveaxis(host, axis, -1))
-    n = xs.shape[-1]
+    batch, n = rows_last(x.shape)
     n_out = _lib.check(lib.nxsig_resample_length(n, up, down))
-    batch = int(np.prod(xs.shape[:-1], dtype=np.int64))
-    out = np.empty(xs.shape[:-1] + (n_out,), dtype)
-    c = ctx or default_context()
-    _lib.check(lib.nxsig_resample_poly(_lib.ctx_ptr(c.handle), xs.ctypes.data_as(C.c_void_p), is_c, n, batch, n, h.ctypes.data_as(C.c_void_p), h.shape[0],
-                                       up, down, out.ctypes.data_as(C.c_void_p), _lib.HOST))
-    return np.ascontiguousarray(np.moveaxis(out, -1, axis))
+    c = x.context(ctx, caller_first=False)
+    out = x.result(x.shape[:-1] + (n_out,), x.dtype)
+    _lib.check(lib.nxsig_resample_poly(_lib.ctx_ptr(c.handle), x.ptr, int(x.dtype == np.complex64), n, batch, n, ptr(h), h.shape[0], up, down,
+                                       ptr(out), x.mem))
+    return out if x.device else np.ascontiguousarray(np.moveaxis(out, -1, axis))
 
 
 # ---- recursive filters: scipy.signal.sosfilt / sosfilt_zi / sosfiltfilt (include/nxsig.h)
@@ -264,27 +221,14 @@ def _sos(sos, fn):
     return s
 
 
-def _sos_rows(x, axis, ctx, fn):
-    """(host rows [batch, n] or None, device (ptr, shape, dtype) or None, shape, axis, a function that gives the context) of the tensor a
-    recursive filter runs over; the context is looked up only once every argument has been checked"""
-    host, dev = _tensor(x)
-    shape = tuple(host.shape) if dev is None else tuple(dev[1])
-    dtype = host.dtype if dev is None else np.dtype(dev[2])
-    if dtype != np.float32:
-        raise NxSignalUnsupported(f"{fn}: real f32 tensors are built, got {dtype}")
-    rank = len(shape)
-    if rank < 1:
-        raise ArgumentError(f"{fn}: the tensor must have at least one axis")
-    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not -rank <= axis < rank:
-        raise ArgumentError(f"{fn}: axis {axis!r} is out of bounds for a tensor of rank {rank}")
-    axis = int(axis) % rank
-    if any(s < 1 for s in shape):
-        raise ArgumentError(f"{fn}: empty dimension")
-    if dev is not None:
-        if axis != rank - 1:
-            raise NxSignalUnsupported(f"{fn}: device tensors are filtered along their last axis only")
-        return None, dev, shape, axis, lambda: x.ctx if isinstance(x, DeviceBuffer) else (ctx or default_context())
-    return np.ascontiguousarray(np.moveaxis(host, axis, -1)), None, shape, axis, lambda: ctx or default_context()
+def _sos_operand(x, axis, fn):
+    """(operand, its shape as given, axis) of the tensor a recursive filter runs over: real f32, the rows at the back"""
+    x = Operand(x)
+    if x.dtype != np.float32:
+        raise NxSignalUnsupported(f"{fn}: real f32 tensors are built, got {x.dtype}")
+    shape = x.shape
+    axis = _axis_last(x, axis, fn, NxSignalUnsupported(f"{fn}: device tensors are filtered along their last axis only"))
+    return x, shape, axis
 
 
 def sosfilt_zi(sos):
@@ -292,7 +236,7 @@ def sosfilt_zi(sos):
     s = _sos(sos, "sosfilt_zi")
     zi = np.empty((s.shape[0], 2), np.float64)
     pd = C.POINTER(C.c_double)
-    _lib.check(_lib.load().nxsig_sosfilt_zi(s.ctypes.data_as(pd), s.shape[0], zi.ctypes.data_as(pd)))
+    _lib.check(_lib.load().nxsig_sosfilt_zi(C.cast(ptr(s), pd), s.shape[0], C.cast(ptr(zi), pd)))
     return zi
 
 
@@ -304,11 +248,10 @@ def sosfilt(x, sos, zi=None, ctx=None, axis=-1, direction=0):
     groups of 16 (f32 rows between the groups).  direction=1 runs the filter from the end of each row towards its start.  Outputs
     ahead of a row's first Inf / NaN are untouched by it; every output from it on is non-finite."""
     s = _sos(sos, "sosfilt")
-    rows, dev, shape, axis, get_ctx = _sos_rows(x, axis, ctx, "sosfilt")
+    x, shape, axis = _sos_operand(x, axis, "sosfilt")
     if direction not in (0, 1):
         raise ArgumentError(f"sosfilt: direction must be 0 or 1, got: {direction!r}")
-    n, ns = shape[axis], s.shape[0]
-    batch = int(np.prod(shape, dtype=np.int64)) // n
+    (batch, n), ns = rows_last(x.shape), s.shape[0]
     zrows = None
     if zi is not None:
         z = np.asarray(zi)
@@ -318,30 +261,23 @@ def sosfilt(x, sos, zi=None, ctx=None, axis=-1, direction=0):
                                 f"{ns} sections, zi must have shape {want}, got {z.shape}.")
         # [batch][n_sections][2] for the C ABI
         zrows = np.ascontiguousarray(np.moveaxis(z.astype(np.float64), axis + 1, -1).reshape(ns, batch, 2).transpose(1, 0, 2))
-    lib, c = _lib.load(), get_ctx()
+    lib, c = _lib.load(), x.context(ctx, caller_first=False)
     zf = np.empty((batch, ns, 2), np.float64) if zi is not None else None
-    src, out = (dev[0], None) if dev is not None else (rows, None)
+    src, out = x.ptr, None
     for g0 in range(0, ns, _SOS_MAX):
         sg = np.ascontiguousarray(s[g0:g0 + _SOS_MAX])
         k = sg.shape[0]
         zig = np.ascontiguousarray(zrows[:, g0:g0 + k]) if zrows is not None else None
         zfg = np.empty((batch, k, 2), np.float64) if zrows is not None else None
-        args = (sg.ctypes.data_as(C.c_void_p), k, zig.ctypes.data_as(C.c_void_p) if zig is not None else None, batch,
-                zfg.ctypes.data_as(C.c_void_p) if zfg is not None else None, int(direction))
-        if dev is not None:
-            nxt = DeviceBuffer.empty(c, shape, np.float32)
-            _lib.check(lib.nxsig_sosfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), C.c_void_p(src), n, batch, n, *args, C.c_void_p(nxt.ptr), _lib.DEVICE))
-            out = nxt   # the previous group's result is let go only now, behind the call that read it
-            src = out.ptr
-        else:
-            out = np.empty((batch, n), np.float32)
-            _lib.check(lib.nxsig_sosfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), src.ctypes.data_as(C.c_void_p), n, batch, n, *args,
-                                             out.ctypes.data_as(C.c_void_p), _lib.HOST))
-            src = out
+        nxt = x.result(x.shape, np.float32)
+        _lib.check(lib.nxsig_sosfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), src, n, batch, n, ptr(sg), k, ptr(zig), batch, ptr(zfg),
+                                         int(direction), ptr(nxt), x.mem))
+        out = nxt   # the previous group's result is let go only now, behind the call that read it
+        src = ptr(out)
         if zfg is not None:
             zf[:, g0:g0 + k] = zfg
-    if dev is None:
-        out = np.ascontiguousarray(np.moveaxis(out.reshape(shape[:axis] + shape[axis + 1:] + (n,)), -1, axis))
+    if not x.device:
+        out = np.ascontiguousarray(np.moveaxis(out, -1, axis))
     if zi is None:
         return out
     zf = np.moveaxis(zf.transpose(1, 0, 2).reshape((ns,) + shape[:axis] + shape[axis + 1:] + (2,)), -1, axis + 1)
@@ -358,11 +294,10 @@ def sosfiltfilt(x, sos, ctx=None, axis=-1, padtype="odd", padlen=None):
         raise ArgumentError(f"sosfiltfilt: unknown value {padtype!r} given to padtype. padtype must be 'even', 'odd', 'constant', or None.")
     if padlen is not None and (isinstance(padlen, bool) or not isinstance(padlen, (int, np.integer)) or padlen < 0):
         raise ArgumentError(f"sosfiltfilt: padlen must be a non-negative integer or None, got: {padlen!r}")
-    rows, dev, shape, axis, get_ctx = _sos_rows(x, axis, ctx, "sosfiltfilt")
+    x, shape, axis = _sos_operand(x, axis, "sosfiltfilt")
     if s.shape[0] > _SOS_MAX:
         raise NxSignalUnsupported(f"sosfiltfilt: cascades of up to {_SOS_MAX} sections are built, got {s.shape[0]}")
-    n = shape[axis]
-    batch = int(np.prod(shape, dtype=np.int64)) // n
+    batch, n = rows_last(x.shape)
     if padtype is None:
         edge = 0
     elif padlen is None:
@@ -371,13 +306,8 @@ def sosfiltfilt(x, sos, ctx=None, axis=-1, padtype="odd", padlen=None):
         edge = int(padlen)
     if n <= edge:   # scipy's _validate_pad
         raise ArgumentError(f"sosfiltfilt: the length of the input vector x must be greater than padlen, which is {edge}.")
-    lib, c = _lib.load(), get_ctx()
-    args = (s.ctypes.data_as(C.c_void_p), s.shape[0], _SOS_PADTYPES[padtype], edge)
-    if dev is not None:
-        out = DeviceBuffer.empty(c, shape, np.float32)
-        _lib.check(lib.nxsig_sosfiltfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), C.c_void_p(dev[0]), n, batch, n, *args, C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    out = np.empty((batch, n), np.float32)
-    _lib.check(lib.nxsig_sosfiltfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), rows.ctypes.data_as(C.c_void_p), n, batch, n, *args,
-                                         out.ctypes.data_as(C.c_void_p), _lib.HOST))
-    return np.ascontiguousarray(np.moveaxis(out.reshape(shape[:axis] + shape[axis + 1:] + (n,)), -1, axis))
+    c = x.context(ctx, caller_first=False)
+    out = x.result(x.shape, np.float32)
+    _lib.check(_lib.load().nxsig_sosfiltfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), x.ptr, n, batch, n, ptr(s), s.shape[0],
+                                                 _SOS_PADTYPES[padtype], edge, ptr(out), x.mem))
+    return out if x.device else np.ascontiguousarray(np.moveaxis(out, -1, axis))

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError
-from .device import DeviceBuffer, default_context, is_device
+from ._marshal import Operand, _as_tensor, is_device, ptr, validate
 
 # native element types of the kernels; narrower ones are widened exactly before the call
 _DT = {np.dtype(np.float32): _lib.DT_F32, np.dtype(np.float64): _lib.DT_F64, np.dtype(np.int32): _lib.DT_S32,
@@ -20,10 +20,8 @@ _CMP = {"less": _lib.CMP_LESS, "greater": _lib.CMP_GREATER, "less_equal": _lib.C
 _UFUNC = {np.less: "less", np.greater: "greater", np.less_equal: "less_equal", np.greater_equal: "greater_equal"}
 
 
-def _options(opts, fn):
-    unknown = [k for k in opts if k not in ("axis", "order")]
-    if unknown:   # keyword!
-        raise ArgumentError(f"unknown keys {unknown} in {fn} options, the allowed keys are: ['axis', 'order']")
+def _axis_order(opts, fn):
+    validate(opts, ["axis", "order"], fn)   # keyword!
     axis, order = opts.get("axis", 0), opts.get("order", 1)
     if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)):
         raise ArgumentError(f"{fn}: axis must be an integer, got: {axis!r}")
@@ -54,75 +52,41 @@ def _check_shape(shape, axis, fn):
     return axis % rank
 
 
-def _device(t):
-    """(ptr, shape, dtype, ctx or None) of a device input of any element type"""
-    if isinstance(t, DeviceBuffer):
-        return t.ptr, t.shape, t.dtype, t.ctx
-    if hasattr(t, "__cuda_array_interface__"):
-        cai = t.__cuda_array_interface__
-        if cai.get("strides") is not None:
-            raise ArgumentError("device inputs must be contiguous")
-        return int(cai["data"][0]), tuple(cai["shape"]), np.dtype(cai["typestr"]), None
-    if not t.is_contiguous():
-        raise ArgumentError("device inputs must be contiguous")
-    try:
-        dt = np.dtype(str(t.dtype).replace("torch.", ""))
-    except TypeError:
-        raise ArgumentError(f"unsupported device dtype {t.dtype}") from None
-    return int(t.data_ptr()), tuple(t.shape), dt, None
-
-
-def _result(c, shape, dev):
-    size, rank = math.prod(shape), len(shape)
-    if dev:
-        return DeviceBuffer.empty(c, (size, rank), np.int32), DeviceBuffer.empty(c, (), np.uint32)
-    return np.empty((size, rank), np.int32), np.zeros((), np.uint32)
-
-
-def _ptr(a):
-    return C.c_void_p(a.ptr) if isinstance(a, DeviceBuffer) else a.ctypes.data_as(C.c_void_p)
+def _compact(c, x, call):
+    """{"indices", "valid_indices"} where operand x lives, filled by call(indices pointer, valid pointer)"""
+    indices, valid = x.result((math.prod(x.shape), len(x.shape)), np.int32), x.result((), np.uint32)
+    if not x.device:
+        valid[...] = 0
+    _lib.check(call(ptr(indices), ptr(valid)))
+    return {"indices": indices, "valid_indices": valid}
 
 
 def _fused(data, name, ctx, axis, order, fn):
-    if is_device(data):
-        ptr, shape, dtype, owner = _device(data)
-        ax = _check_shape(shape, axis, fn)
-        if dtype.kind == "c":
-            raise ArgumentError(f"{fn}: complex tensors have no order")
-        if dtype not in _DT:
-            raise ArgumentError(f"{fn}: device tensors must be f32, f64, s32, s64, u32 or u64, got {dtype}")
-        c = owner or ctx or default_context()
-        mem, x = _lib.DEVICE, C.c_void_p(ptr)
-    else:
-        a = np.asarray(_as_tensor(data))
-        shape = a.shape
-        ax = _check_shape(shape, axis, fn)
-        if a.dtype.kind == "c":
-            raise ArgumentError(f"{fn}: complex tensors have no order")
-        if a.dtype not in _DT:
-            if a.dtype.kind not in _WIDEN:
-                raise ArgumentError(f"{fn}: unsupported type {a.dtype}")
-            a = a.astype(_WIDEN[a.dtype.kind])
-        a = np.ascontiguousarray(a)
-        dtype, c, mem, x = a.dtype, ctx or default_context(), _lib.HOST, a.ctypes.data_as(C.c_void_p)
-    lib = _lib.load()
-    indices, valid = _result(c, shape, mem == _lib.DEVICE)
+    x = Operand(_as_tensor(data), any_dtype=True)
+    ax = _check_shape(x.shape, axis, fn)
+    if x.dtype.kind == "c":
+        raise ArgumentError(f"{fn}: complex tensors have no order")
+    if x.dtype not in _DT:
+        if x.device:
+            raise ArgumentError(f"{fn}: device tensors must be f32, f64, s32, s64, u32 or u64, got {x.dtype}")
+        if x.dtype.kind not in _WIDEN:
+            raise ArgumentError(f"{fn}: unsupported type {x.dtype}")
+    x.cast(x.dtype if x.dtype in _DT else _WIDEN[x.dtype.kind])
+    c = x.context(ctx, caller_first=False)
+    lib, shape = _lib.load(), x.shape
     sh = (C.c_int64 * len(shape))(*shape)
-    _lib.check(lib.nxsig_argrelextrema(c.handle, x, _DT[np.dtype(dtype)], sh, len(shape), ax, _shifts(order), _CMP[name], _ptr(indices),
-                                       _ptr(valid), mem))
-    return {"indices": indices, "valid_indices": valid}
+    return _compact(c, x, lambda ip, vp: lib.nxsig_argrelextrema(c.handle, x.ptr, _DT[x.dtype], sh, len(shape), ax, _shifts(order), _CMP[name],
+                                                                 ip, vp, x.mem))
 
 
 def nonzero(mask, ctx=None):
     """The compaction step on its own: coordinates of the non-zero elements of a host mask (any rank 1 .. 8) in row-major order, then
     -1 rows, as argrelextrema returns them."""
-    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-    _check_shape(m.shape, 0, "nonzero")
-    c = ctx or default_context()
-    indices, valid = _result(c, m.shape, False)
-    sh = (C.c_int64 * m.ndim)(*m.shape)
-    _lib.check(_lib.load().nxsig_nonzero(c.handle, m.ctypes.data_as(C.c_void_p), sh, m.ndim, _ptr(indices), _ptr(valid), _lib.HOST))
-    return {"indices": indices, "valid_indices": valid}
+    x = Operand(np.asarray(mask) != 0).cast(np.uint8)
+    _check_shape(x.shape, 0, "nonzero")
+    c = x.context(ctx, caller_first=True)
+    sh = (C.c_int64 * len(x.shape))(*x.shape)
+    return _compact(c, x, lambda ip, vp: _lib.load().nxsig_nonzero(c.handle, x.ptr, sh, len(x.shape), ip, vp, x.mem))
 
 
 def _custom(data, comparator, ctx, axis, order, fn):
@@ -151,7 +115,7 @@ def argrelextrema(data, comparator, ctx=None, **opts):
     fused kernels), or any callable comparator(x, y) -> boolean array (host tensors; the mask is compacted on the device).
     Options axis (default 0, negative counts from the end) and order (default 1; order <= 0 marks every element, as in the
     reference).  Host input gives numpy int32 (size, rank) and a 0-d uint32; device input gives DeviceBuffers."""
-    axis, order = _options(opts, "argrelextrema")
+    axis, order = _axis_order(opts, "argrelextrema")
     name = comparator if isinstance(comparator, str) else _UFUNC.get(comparator)
     if name is not None:
         if name not in _CMP:
@@ -164,16 +128,11 @@ def argrelextrema(data, comparator, ctx=None, **opts):
 
 def argrelmin(data, ctx=None, **opts):
     """PeakFinding.argrelmin/2: argrelextrema(data, "less", ...)"""
-    axis, order = _options(opts, "argrelmin")
+    axis, order = _axis_order(opts, "argrelmin")
     return _fused(data, "less", ctx, axis, order, "argrelmin")
 
 
 def argrelmax(data, ctx=None, **opts):
     """PeakFinding.argrelmax/2: argrelextrema(data, "greater", ...)"""
-    axis, order = _options(opts, "argrelmax")
+    axis, order = _axis_order(opts, "argrelmax")
     return _fused(data, "greater", ctx, axis, order, "argrelmax")
-
-
-def _as_tensor(x):
-    from . import _as_tensor as as_tensor
-    return as_tensor(x)

@@ -3,23 +3,20 @@ and the magnitude-squared coherence of real f32 rows — scipy.signal.welch / cs
 average="mean", options spelled as in stft (include/nxsig.h: nxsig_welch_f32, nxsig_csd_f32)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, NxSignalUnsupported
-from .device import DeviceBuffer, default_context, device_view, is_device
+from ._marshal import Operand, ptr, rows_last, validate
+from .device import DeviceBuffer
 
 _KEYS = ("overlap_length", "fft_length", "sampling_rate", "detrend", "scaling", "average")
 _SCALINGS = {"density": 0, "spectrum": 1}
 
 
-def _options(fn, n, opts):
+def _parse(fn, n, opts):
     """(hop, fft_length, sampling_rate, detrend, scaling) of the validated options"""
-    unknown = [k for k in opts if k not in _KEYS]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in {fn} options, the allowed keys are: {list(_KEYS)}")
+    validate(opts, _KEYS, fn)
     overlap = opts.get("overlap_length", n // 2)
     if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not 0 <= overlap < n:
         raise ArgumentError(f"{fn}: overlap_length must be an integer in [0, {n}), got: {overlap!r}")
@@ -45,20 +42,15 @@ def _options(fn, n, opts):
     return n - int(overlap), int(k), float(fs), int(detrend == "constant"), _SCALINGS[scaling]
 
 
-def _rows(fn, t):
-    """(host array or None, device pointer or None, shape) of a real f32 input"""
-    if is_device(t):
-        ptr, shape, dtype = device_view(t)
-        host = None
-    else:
-        host = np.asarray(t)
-        ptr, shape, dtype = None, host.shape, host.dtype
-    if np.dtype(dtype) != np.float32:
-        raise NxSignalUnsupported(f"{fn}: real f32 tensors are built, got {np.dtype(dtype)}")
-    shape = tuple(int(s) for s in shape)
-    if len(shape) < 1 or any(s < 1 for s in shape):
+def _real_f32(fn, t) -> Operand:
+    """a real f32 input with at least one axis and no empty one; a host array is made contiguous"""
+    x = Operand(t)
+    if x.dtype != np.float32:
+        raise NxSignalUnsupported(f"{fn}: real f32 tensors are built, got {x.dtype}")
+    x.shape = tuple(int(s) for s in x.shape)
+    if len(x.shape) < 1 or any(s < 1 for s in x.shape):
         raise ArgumentError(f"{fn}: the tensor must have at least one axis and no empty dimension")
-    return (None if host is None else np.ascontiguousarray(host)), ptr, shape
+    return x.cast()
 
 
 def _window(fn, window):
@@ -77,45 +69,34 @@ def frequencies(fft_length, sampling_rate=1.0):
 def _estimate(fn, x, y, window, ctx, want_auto, opts):
     w = _window(fn, window)
     n = int(w.shape[0])
-    hop, k, fs, detrend, scaling = _options(fn, n, opts)
-    xh, xp, shape = _rows(fn, x)
+    hop, k, fs, detrend, scaling = _parse(fn, n, opts)
+    x = _real_f32(fn, x)
+    shape = x.shape
     if y is not None:
-        yh, yp, yshape = _rows(fn, y)
-        if yshape != shape:
-            raise ArgumentError(f"{fn}: x and y must have the same shape, got {shape} and {yshape}")
-        if (xp is None) != (yp is None):
+        y = _real_f32(fn, y)
+        if y.shape != shape:
+            raise ArgumentError(f"{fn}: x and y must have the same shape, got {shape} and {y.shape}")
+        if x.device != y.device:
             raise ArgumentError(f"{fn}: x and y must both be host tensors or both be device tensors")
-    length = shape[-1]
+    batch, length = rows_last(shape)
     if length < n:
         raise ArgumentError(f"{fn}: the window of length {n} does not fit rows of length {length}")
-    batch = int(np.prod(shape[:-1], dtype=np.int64))
     if batch >= 2 ** 31:
         raise ArgumentError(f"{fn}: 2^31 or more rows")
     lib = _lib.load()
     nb = _lib.check(lib.nxsig_welch_bins(k))
     oshape = shape[:-1] + (nb,)
-    device = xp is not None
-    c = x.ctx if isinstance(x, DeviceBuffer) else (ctx or default_context())
-    mem = _lib.DEVICE if device else _lib.HOST
-    wp = w.ctypes.data_as(C.c_void_p)
-
-    def buf(dtype):
-        return DeviceBuffer.empty(c, oshape, dtype) if device else np.empty(oshape, dtype)
-
-    def ptr(b):
-        return None if b is None else (C.c_void_p(b.ptr) if device else b.ctypes.data_as(C.c_void_p))
-
-    xin = C.c_void_p(xp) if device else xh.ctypes.data_as(C.c_void_p)
+    c = x.context(ctx, caller_first=False)
+    cp = _lib.ctx_ptr(c.handle, _lib._ctx_spectral)
     if y is None:
-        pxx = buf(np.float32)
-        _lib.check(lib.nxsig_welch_f32(_lib.ctx_ptr(c.handle, _lib._ctx_spectral), xin, length, batch, length, wp, n, hop, k, detrend, scaling, fs, ptr(pxx), mem))
+        pxx = x.result(oshape, np.float32)
+        _lib.check(lib.nxsig_welch_f32(cp, x.ptr, length, batch, length, ptr(w), n, hop, k, detrend, scaling, fs, ptr(pxx), x.mem))
         return frequencies(k, fs), pxx
-    yin = C.c_void_p(yp) if device else yh.ctypes.data_as(C.c_void_p)
-    pxy = buf(np.complex64)
-    pxx = buf(np.float32) if want_auto else None
-    pyy = buf(np.float32) if want_auto else None
-    _lib.check(lib.nxsig_csd_f32(_lib.ctx_ptr(c.handle, _lib._ctx_spectral), xin, yin, length, batch, length, wp, n, hop, k, detrend, scaling, fs, ptr(pxx), ptr(pyy),
-                                 ptr(pxy), mem))
+    pxy = x.result(oshape, np.complex64)
+    pxx = x.result(oshape, np.float32) if want_auto else None
+    pyy = x.result(oshape, np.float32) if want_auto else None
+    _lib.check(lib.nxsig_csd_f32(cp, x.ptr, y.ptr, length, batch, length, ptr(w), n, hop, k, detrend, scaling, fs, ptr(pxx), ptr(pyy), ptr(pxy),
+                                 x.mem))
     return frequencies(k, fs), pxx, pyy, pxy, c
 
 

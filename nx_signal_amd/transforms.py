@@ -10,33 +10,25 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError
-from .device import DeviceBuffer, default_context, device_view, is_device
+from ._marshal import Operand, _as_tensor, ptr, rows_last, validate
 
 
 def _run(tensor, inverse, opts, ctx):
     """Enum.zip_reduce(axes, lengths, tensor, &Nx.fft(&3, axis: &1, length: &2)) — transforms.ex:9-11 / :18-20"""
-    unknown = [k for k in opts if k not in ("axes", "lengths")]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in fft_nd options, the allowed keys are: ['axes', 'lengths']")
+    validate(opts, ["axes", "lengths"], "fft_nd")
     axes = list(opts.get("axes", [-1]))
     lengths = opts.get("lengths") or [None] * len(axes)
     if len(lengths) != len(axes):
         raise ArgumentError("fft_nd: :axes and :lengths must have the same size")
-    dev = is_device(tensor)
-    if dev:
-        ptr, shape, dt = device_view(tensor)
-        c = ctx or getattr(tensor, "ctx", None) or default_context()
-        if dt not in (np.dtype(np.float32), np.dtype(np.complex64)):
+    x = Operand(_as_tensor(tensor))   # Python numbers / lists follow Nx.tensor's inference (f32 / c64)
+    if x.device:
+        if x.dtype not in (np.float32, np.complex64):
             raise ArgumentError("fft_nd: device input must be float32 or complex64")
-        is_real = dt == np.dtype(np.float32)
     else:
-        from . import _as_tensor   # Python numbers / lists follow Nx.tensor's inference (f32 / c64)
-        a = np.asarray(_as_tensor(tensor))
-        if a.dtype in (np.float64, np.complex128):
-            return _run_f64(a, inverse, axes, lengths, ctx)
-        a = np.ascontiguousarray(a.astype(np.complex64 if np.iscomplexobj(a) else np.float32))
-        shape, is_real = a.shape, not np.iscomplexobj(a)
-        c = ctx or default_context()
+        if x.dtype in (np.float64, np.complex128):
+            return _run_f64(x, inverse, axes, lengths, ctx)
+        x.cast(np.complex64 if x.dtype.kind == "c" else np.float32)
+    shape, is_real = x.shape, x.dtype == np.float32
     rank = len(shape)
     if rank == 0:
         raise ArgumentError("fft_nd: expected a tensor of rank >= 1")
@@ -57,33 +49,26 @@ def _run(tensor, inverse, opts, ctx):
     sh = (C.c_int64 * rank)(*[int(s) for s in shape])
     axs = (C.c_int32 * max(len(ax_n), 1))(*ax_n)
     lns = (C.c_int64 * max(len(len_n), 1))(*len_n)
-    if dev:
-        out = c.empty(tuple(out_shape), np.complex64)
-        _lib.check(lib.nxsig_fft_nd(c.handle, C.c_void_p(ptr), int(is_real), sh, rank, axs, lns, len(ax_n), int(inverse),
-                                    C.c_void_p(out.ptr), _lib.DEVICE))
-        return out
-    out = np.empty(tuple(out_shape), np.complex64)
-    _lib.check(lib.nxsig_fft_nd(c.handle, a.ctypes.data_as(C.c_void_p), int(is_real), sh, rank, axs, lns, len(ax_n), int(inverse),
-                                out.ctypes.data_as(C.c_void_p), _lib.HOST))
+    c = x.context(ctx, caller_first=True)
+    out = x.result(tuple(out_shape), np.complex64)
+    _lib.check(lib.nxsig_fft_nd(c.handle, x.ptr, int(is_real), sh, rank, axs, lns, len(ax_n), int(inverse), ptr(out), x.mem))
     return out
 
 
-def _run_f64(a, inverse, axes, lengths, ctx):
+def _run_f64(x, inverse, axes, lengths, ctx):
     """f64 tier (nxsig_fft_c128): Nx.fft / Nx.ifft in c128 over the LAST axis; other axes are not built in double"""
-    if a.ndim == 0:
+    rank = len(x.shape)
+    if rank == 0:
         raise ArgumentError("fft_nd: expected a tensor of rank >= 1")
-    if len(axes) != 1 or int(axes[0]) % a.ndim != a.ndim - 1:
+    if len(axes) != 1 or int(axes[0]) % rank != rank - 1:
         raise _lib.NxSignalUnsupported("fft_nd: f64 / c128 tensors are transformed over the last axis only")
-    a = np.ascontiguousarray(a)
-    n_in = int(a.shape[-1])
+    rows, n_in = rows_last(x.cast().shape)
     K = int(lengths[0]) if lengths[0] is not None else n_in
     if K < 1:
         raise ArgumentError("fft_nd: lengths must be positive")
-    rows = int(np.prod(a.shape[:-1], dtype=np.int64)) if a.ndim > 1 else 1
-    c = ctx or default_context()
-    out = np.empty(a.shape[:-1] + (K,), np.complex128)
-    _lib.check(_lib.load().nxsig_fft_c128(c.handle, a.ctypes.data_as(C.c_void_p), int(a.dtype == np.float64), rows, n_in, K, int(inverse),
-                                          out.ctypes.data_as(C.c_void_p), _lib.HOST))
+    c = x.context(ctx, caller_first=True)
+    out = x.result(x.shape[:-1] + (K,), np.complex128)
+    _lib.check(_lib.load().nxsig_fft_c128(c.handle, x.ptr, int(x.dtype == np.float64), rows, n_in, K, int(inverse), ptr(out), x.mem))
     return out
 
 

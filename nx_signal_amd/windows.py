@@ -6,15 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError
-
-
-def _validate(opts, allowed, fn):
-    unknown = [k for k in opts if k not in allowed]
-    if unknown:
-        raise ArgumentError(f"unknown keys {unknown} in {fn} options, the allowed keys are: {list(allowed)}")
-    out = dict(allowed)
-    out.update(opts)
-    return out
+from ._marshal import ptr, validate as _validate
 
 
 def _is_f64(t):
@@ -27,14 +19,12 @@ def _gen(kind, n, periodic=True, beta=0.0, eps=1.0e-7, t=None):
         raise ArgumentError(f"window length must be an integer, got: {n!r}")
     if _is_f64(t):
         out = np.empty(int(n), dtype=np.float64)
-        _lib.check(_lib.load().nxsig_window_f64(kind, int(n), int(bool(periodic)), float(beta), float(eps),
-                                                out.ctypes.data_as(_lib.C.c_void_p)))
+        _lib.check(_lib.load().nxsig_window_f64(kind, int(n), int(bool(periodic)), float(beta), float(eps), ptr(out)))
         return out
     if t not in (None, "f32", np.float32):
         raise ArgumentError(f"window type must be f32 or f64 (got {t!r})")
     out = np.empty(int(n), dtype=np.float32)
-    _lib.check(_lib.load().nxsig_window_f32(kind, int(n), int(bool(periodic)), float(beta), float(eps),
-                                            out.ctypes.data_as(_lib.C.c_void_p)))
+    _lib.check(_lib.load().nxsig_window_f32(kind, int(n), int(bool(periodic)), float(beta), float(eps), ptr(out)))
     return out
 
 
