@@ -5,10 +5,18 @@
  * found.  It is nevertheless compiled and EXECUTED by the test-suite: tests/stub/erl_nif.h declares the subset of the NIF
  * API used here and tests/stub/erl_nif_fake.c is a miniature term runtime, so tests/test_nif_shim.py (CPU: host generators,
  * argument validation; GPU: stft / istft / fir / device chains / sharded calls) calls these functions exactly as the BEAM
- * would (entry->funcs[i].fptr(env, argc, argv)) and compares with the ctypes path bit for bit.
+ * would (entry->funcs[i].fptr(env, argc, argv)) and compares with the ctypes path bit for bit; tests/test_nif_calls_host.py
+ * pins what every NIF hands to the C ABI and gives back, error paths included, against a recording stand-in for the library.
  *
  * The shim is deliberately mechanical: every function unpacks terms, validates sizes BEFORE allocating, calls ONE
  * nxsig_* entry point and packs the result; all logic lives behind the C ABI.
+ *
+ * A new NIF is written with three helpers.  get_rows() reads a tensor operand — a binary of EXACTLY elem * a * b * c bytes, or a
+ * device buffer of the call's context that holds at least as many.  result_t holds the result — a BEAM binary or a device block —
+ * behind res_open() / res_fail() / res_term(), so that a NIF has one error exit whatever it allocated.  get_frames_args() is the
+ * argument prologue of the STFT family (length or frame count, batch, window, [window_is_f64,] params, the window size check and
+ * the rows' output length).  Where two table entries differ only in an element type (f32 / f64, c64 / c128) or in where the tensors
+ * live (host / device), they are one body with that as a parameter and the callee chosen by a branch at the single call site.
  *
  * Conventions:
  *   - every GPU call is a dirty job (ERL_NIF_DIRTY_JOB_IO_BOUND: the scheduler thread waits on the GPU);
@@ -88,18 +96,17 @@ static ERL_NIF_TERM mk_error_msg(ErlNifEnv* env, int code, const char* msg) {
 static ERL_NIF_TERM mk_error(ErlNifEnv* env, int code) { return mk_error_msg(env, code, nxsig_last_error()); }
 static ERL_NIF_TERM mk_oom(ErlNifEnv* env) { return mk_error_msg(env, NXSIG_ERR_OOM, "cannot allocate the result binary"); }
 static ERL_NIF_TERM mk_ok(ErlNifEnv* env, ERL_NIF_TERM v) { return enif_make_tuple2(env, mk_atom(env, "ok"), v); }
+static ERL_NIF_TERM mk_ok2(ErlNifEnv* env, ERL_NIF_TERM v, ERL_NIF_TERM w) { return enif_make_tuple3(env, mk_atom(env, "ok"), v, w); }
 
-/* result binaries: enif_alloc_binary reports failure instead of aborting the VM; sizes are overflow-checked */
+/* sizes are overflow-checked */
 static int mul_size(size_t* acc, uint64_t f) {
   if (f != 0 && *acc > (size_t)-1 / f) return 0;
   *acc *= (size_t)f;
   return 1;
 }
-static int out_bin(ErlNifBinary* b, uint64_t a, uint64_t c, uint64_t d, uint64_t elem) {
-  size_t n = 1;
-  if (!mul_size(&n, a) || !mul_size(&n, c) || !mul_size(&n, d) || !mul_size(&n, elem)) return 0;
-  if (n > ((size_t)1 << 46)) return 0; /* 64 TiB: far beyond any host; keeps a bad shape from reaching the allocator */
-  return enif_alloc_binary(n, b);
+static int rows_bytes(size_t* n, size_t elem, uint64_t a, uint64_t b, uint64_t c) {
+  *n = elem;
+  return mul_size(n, a) && mul_size(n, b) && mul_size(n, c);
 }
 
 static int get_ctx(ErlNifEnv* env, ERL_NIF_TERM t, ctx_res_t** out) {
@@ -153,6 +160,90 @@ static ERL_NIF_TERM make_gbuf(ErlNifEnv* env, grp_res_t* g, int member, void* d,
   return t;
 }
 
+/* ------------------------------------------------------------------------------------------------ operands and results */
+/* A tensor operand: a x b x c items of `elem` bytes, every count at least 1.  mem NXSIG_HOST: a binary of exactly that many bytes — the
+ * library reads all of them and not one more, so neither a short binary nor one with trailing elements is let through.  NXSIG_DEVICE: a
+ * buffer resource that lives on context c and holds at least that many bytes (a buffer may be larger than the tensor it carries). */
+static int get_rows(ErlNifEnv* env, ERL_NIF_TERM t, const ctx_res_t* c, int mem, size_t elem, int64_t a, int64_t b, int64_t d, const void** data) {
+  size_t need;
+  if (a < 1 || b < 1 || d < 1 || !rows_bytes(&need, elem, (uint64_t)a, (uint64_t)b, (uint64_t)d)) return 0;
+  if (mem == NXSIG_HOST) {
+    ErlNifBinary bin;
+    if (!enif_inspect_binary(env, t, &bin) || bin.size != need) return 0;
+    *data = bin.data;
+  } else {
+    buf_res_t* buf;
+    if (!get_buf(env, t, &buf) || buf->owner != c || buf->bytes < need) return 0;
+    *data = buf->dptr;
+  }
+  return 1;
+}
+
+/* A result tensor: a BEAM binary (NXSIG_HOST; enif_alloc_binary reports failure instead of aborting the VM) or a block of context c's
+ * device memory (NXSIG_DEVICE).  res_open returns 0, RES_NOMEM or the library's (negative) status; res_fail releases whatever n results
+ * hold and makes the error term; res_term hands the tensor to the BEAM as a binary or a buffer resource. */
+typedef struct { int open, mem; ctx_res_t* c; ErlNifBinary bin; void* data; size_t bytes; } result_t;
+enum { RES_NOMEM = 1 };
+
+static int res_open(result_t* r, ctx_res_t* c, int mem, size_t elem, uint64_t a, uint64_t b, uint64_t d) {
+  if (!rows_bytes(&r->bytes, elem, a, b, d)) return RES_NOMEM;
+  r->mem = mem; r->c = c;
+  if (mem == NXSIG_HOST) {
+    if (r->bytes > ((size_t)1 << 46)) return RES_NOMEM; /* 64 TiB: far beyond any host; keeps a bad shape from reaching the allocator */
+    if (!enif_alloc_binary(r->bytes, &r->bin)) return RES_NOMEM;
+    r->data = r->bin.data;
+  } else {
+    int rc = nxsig_alloc(c->ctx, r->bytes, &r->data);
+    if (rc) return rc;
+  }
+  r->open = 1;
+  return 0;
+}
+static ERL_NIF_TERM res_fail(ErlNifEnv* env, result_t* r, int n, int rc) {
+  for (int i = 0; i < n; ++i) {
+    if (r[i].open && r[i].mem == NXSIG_HOST) enif_release_binary(&r[i].bin);
+    if (r[i].open && r[i].mem != NXSIG_HOST) nxsig_free(r[i].c->ctx, r[i].data);
+    r[i].open = 0;
+  }
+  return rc == RES_NOMEM ? mk_oom(env) : mk_error(env, rc);
+}
+static ERL_NIF_TERM res_term(ErlNifEnv* env, result_t* r) {
+  return r->mem == NXSIG_HOST ? enif_make_binary(env, &r->bin) : make_buf(env, r->c, r->data, r->bytes);
+}
+/* the usual ending: {:ok, result} or the error of status rc */
+static ERL_NIF_TERM res_ok(ErlNifEnv* env, result_t* r, int rc) { return rc ? res_fail(env, r, 1, rc) : mk_ok(env, res_term(env, r)); }
+/* ... and {:ok, result, count} */
+static ERL_NIF_TERM res_ok2(ErlNifEnv* env, result_t* r, int rc, int64_t count) {
+  return rc ? res_fail(env, r, 1, rc) : mk_ok2(env, res_term(env, r), enif_make_int64(env, count));
+}
+static int term_mem(ErlNifEnv* env, ERL_NIF_TERM t) {
+  ErlNifBinary b;
+  return enif_inspect_binary(env, t, &b) ? NXSIG_HOST : NXSIG_DEVICE;
+}
+
+/* The argument run every STFT-family NIF has at argv[2 ...]: length, batch, window_bin, [window_is_f64 — the f64 tier,] params; for the
+ * inverse transforms the first is num_frames.  `out` is what the geometry makes of one row: nxsig_num_frames(length ...) frames, or for
+ * the inverse nxsig_ola_length(num_frames ...) samples; negative: the library's status, to be reported with mk_error once the NIF's
+ * remaining arguments have passed their own checks (badarg comes first). */
+typedef struct {
+  ErlNifSInt64 len;
+  int batch, wf64;
+  ErlNifBinary w;
+  nxsig_stft_params p;
+  int64_t out;
+} frames_args_t;
+static int get_frames_args(ErlNifEnv* env, const ERL_NIF_TERM* argv, int wide, int inverse, frames_args_t* a) {
+  a->wf64 = 0;
+  if (!enif_get_int64(env, argv[0], &a->len) || !enif_get_int(env, argv[1], &a->batch) || !enif_inspect_binary(env, argv[2], &a->w) ||
+      (wide && !enif_get_int(env, argv[3], &a->wf64)) || !get_params(env, argv[wide ? 4 : 3], &a->p))
+    return 0;
+  /* the window binary is read by the library: its size must match (ADVICE r1: a short window was read out of bounds) */
+  if (a->batch < 1 || a->len < 1 || a->w.size != (size_t)a->p.frame_length * (a->wf64 ? 8 : 4)) return 0;
+  a->out = inverse ? nxsig_ola_length(a->len, a->p.frame_length, a->p.hop)
+                   : nxsig_num_frames(a->len, a->p.frame_length, a->p.hop, a->p.pad_mode, a->p.pad_lo, a->p.pad_hi);
+  return 1;
+}
+
 /* ------------------------------------------------------------------------------------------------ contexts */
 static ERL_NIF_TERM nif_device_count(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   (void)argv;
@@ -198,26 +289,31 @@ static ERL_NIF_TERM nif_last_dispatch(ErlNifEnv* env, int argc, const ERL_NIF_TE
   return mk_ok(env, enif_make_binary(env, &b));
 }
 
-/* ------------------------------------------------------------------------------------------------ host generators */
-/* window(kind, n, periodic, beta, eps) -> {:ok, f32 binary}   (NxSignal.Windows.*, BinaryBackend rounding) */
-static ERL_NIF_TERM nif_window(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* ------------------------------------------------------------------------------------------------ host generators
+ * The reference computes in the type of its operands (include/nxsig.h "f64 / c128 tier"): each generator has an _f64 entry that
+ * takes the same terms and returns an f64 binary. */
+/* window(kind, n, periodic, beta, eps) -> {:ok, f32 binary}   (NxSignal.Windows.*, BinaryBackend rounding)
+ * window_f64: the same -> {:ok, f64 binary}   (NxSignal.Windows.*(n, type: {:f, 64})) */
+static ERL_NIF_TERM window_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
   int kind, n, per;
   double beta, eps;
+  result_t o = {0};
   if (argc != 5 || !enif_get_int(env, argv[0], &kind) || !enif_get_int(env, argv[1], &n) || !enif_get_int(env, argv[2], &per) ||
       !get_number(env, argv[3], &beta) || !get_number(env, argv[4], &eps) || n < 0)
     return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)n, 1, 1, 4)) return mk_oom(env);
-  int rc = nxsig_window_f32(kind, n, per, beta, eps, (float*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
+  int rc = res_open(&o, NULL, NXSIG_HOST, f64 ? 8 : 4, (uint64_t)n, 1, 1);
+  if (!rc) rc = f64 ? nxsig_window_f64(kind, n, per, beta, eps, (double*)o.data) : nxsig_window_f32(kind, n, per, beta, eps, (float*)o.data);
+  return res_ok(env, &o, rc);
 }
+static ERL_NIF_TERM nif_window(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return window_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_window_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return window_any(env, argc, argv, 1); }
 
-/* firwin(num_taps, [cutoff], window_kind, beta, pass_zero, scale, sampling_rate) */
-static ERL_NIF_TERM nif_firwin(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* firwin(num_taps, [cutoff], window_kind, beta, pass_zero, scale, sampling_rate) -> {:ok, f32 binary}; firwin_f64 -> {:ok, f64 binary} */
+static ERL_NIF_TERM firwin_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
   int taps, kind, pz, sc;
   double beta, fs, cut[64];
   unsigned len;
+  result_t o = {0};
   if (argc != 7 || !enif_get_int(env, argv[0], &taps) || !enif_get_list_length(env, argv[1], &len) || len > 64 ||
       !enif_get_int(env, argv[2], &kind) || !get_number(env, argv[3], &beta) || !enif_get_int(env, argv[4], &pz) ||
       !enif_get_int(env, argv[5], &sc) || !get_number(env, argv[6], &fs) || taps < 1)
@@ -225,446 +321,270 @@ static ERL_NIF_TERM nif_firwin(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv
   ERL_NIF_TERM head, tail = argv[1];
   for (unsigned i = 0; i < len; ++i)
     if (!enif_get_list_cell(env, tail, &head, &tail) || !get_number(env, head, &cut[i])) return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)taps, 1, 1, 4)) return mk_oom(env);
-  int rc = nxsig_firwin_f32(taps, cut, (int)len, kind, beta, pz, sc, fs, (float*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
+  int rc = res_open(&o, NULL, NXSIG_HOST, f64 ? 8 : 4, (uint64_t)taps, 1, 1);
+  if (!rc) rc = f64 ? nxsig_firwin_f64(taps, cut, (int)len, kind, beta, pz, sc, fs, (double*)o.data)
+                    : nxsig_firwin_f32(taps, cut, (int)len, kind, beta, pz, sc, fs, (float*)o.data);
+  return res_ok(env, &o, rc);
 }
+static ERL_NIF_TERM nif_firwin(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return firwin_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_firwin_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return firwin_any(env, argc, argv, 1); }
 
-/* fft_frequencies(sampling_rate, fft_length, endpoint) -> {:ok, f32 binary}   (lib/nx_signal.ex:154-166) */
-static ERL_NIF_TERM nif_fft_frequencies(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* fft_frequencies(sampling_rate, fft_length, endpoint) -> {:ok, f32 binary}   (lib/nx_signal.ex:154-166); fft_frequencies_f64 -> f64 */
+static ERL_NIF_TERM fft_frequencies_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
   double fs;
   int k, endpoint;
+  result_t o = {0};
   if (argc != 3 || !get_number(env, argv[0], &fs) || !enif_get_int(env, argv[1], &k) || !enif_get_int(env, argv[2], &endpoint) || k < 1)
     return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)k, 1, 1, 4)) return mk_oom(env);
-  int rc = nxsig_fft_frequencies_f32(fs, k, endpoint, (float*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
+  int rc = res_open(&o, NULL, NXSIG_HOST, f64 ? 8 : 4, (uint64_t)k, 1, 1);
+  if (!rc) rc = f64 ? nxsig_fft_frequencies_f64(fs, k, endpoint, (double*)o.data) : nxsig_fft_frequencies_f32(fs, k, endpoint, (float*)o.data);
+  return res_ok(env, &o, rc);
 }
+static ERL_NIF_TERM nif_fft_frequencies(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fft_frequencies_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_fft_frequencies_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fft_frequencies_any(env, argc, argv, 1); }
 
 /* mel_filters(fft_length, mel_bins, sampling_rate, max_mel, mel_frequency_spacing) -> {:ok, f32[mel_bins][fft_length]} (:397-445) */
 static ERL_NIF_TERM nif_mel_filters(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   int k, bins;
   double fs, max_mel, sp;
+  result_t o = {0};
   if (argc != 5 || !enif_get_int(env, argv[0], &k) || !enif_get_int(env, argv[1], &bins) || !get_number(env, argv[2], &fs) ||
       !get_number(env, argv[3], &max_mel) || !get_number(env, argv[4], &sp) || k < 1 || bins < 1)
     return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)k, (uint64_t)bins, 1, 4)) return mk_oom(env);
-  int rc = nxsig_mel_filters_f32(k, bins, fs, max_mel, sp, (float*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
+  int rc = res_open(&o, NULL, NXSIG_HOST, 4, (uint64_t)k, (uint64_t)bins, 1);
+  if (!rc) rc = nxsig_mel_filters_f32(k, bins, fs, max_mel, sp, (float*)o.data);
+  return res_ok(env, &o, rc);
 }
 
-/* sinc(t_bin) -> {:ok, f32 binary}   (lib/nx_signal/waveforms.ex:451-457) */
-static ERL_NIF_TERM nif_sinc(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ErlNifBinary t, b;
-  if (argc != 1 || !enif_inspect_binary(env, argv[0], &t) || t.size % 4) return enif_make_badarg(env);
-  if (!out_bin(&b, t.size / 4, 1, 1, 4)) return mk_oom(env);
-  int rc = nxsig_sinc_f32((const float*)t.data, (int64_t)(t.size / 4), (float*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
+/* sinc(t_bin) -> {:ok, f32 binary}   (lib/nx_signal/waveforms.ex:451-457); sinc_f64: f64 in, f64 out */
+static ERL_NIF_TERM sinc_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
+  const size_t elem = f64 ? 8 : 4;
+  ErlNifBinary t;
+  result_t o = {0};
+  if (argc != 1 || !enif_inspect_binary(env, argv[0], &t) || t.size % elem) return enif_make_badarg(env);
+  const int64_t n = (int64_t)(t.size / elem);
+  int rc = res_open(&o, NULL, NXSIG_HOST, elem, (uint64_t)n, 1, 1);
+  if (!rc) rc = f64 ? nxsig_sinc_f64((const double*)t.data, n, (double*)o.data) : nxsig_sinc_f32((const float*)t.data, n, (float*)o.data);
+  return res_ok(env, &o, rc);
 }
+static ERL_NIF_TERM nif_sinc(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return sinc_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_sinc_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return sinc_any(env, argc, argv, 1); }
 
-/* ------------------------------------------------------------------------------------------------ hot path, host tensors */
+/* ------------------------------------------------------------------------------------------------ hot path
+ * One body per call family.  `mem`: the tensors are binaries (NXSIG_HOST) or buffer resources of the context (NXSIG_DEVICE: the chain
+ * stft -> edit -> istft stays in HBM; guides/filtering.livemd:137-159; device calls are asynchronous on the
+ * context's stream, from_device synchronises).  `f64`: the f64 / c128 tier (include/nxsig.h), whose NIFs take window_is_f64 after the
+ * window: f64 / c128 binaries in, the same out. */
 /* stft(ctx, x_bin, length, batch, window_bin, params) -> {:ok, z_bin, num_frames, times_bin, freqs_bin}
- * stft_c64: the same with x_bin holding c64 samples (interleaved f32 re, im) — lib/nx_signal.ex:94-102 on complex data */
-static ERL_NIF_TERM stft_host(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], size_t elem) {
+ * stft_c64: the same with x_bin holding c64 samples (interleaved f32 re, im) — lib/nx_signal.ex:94-102 on complex data
+ * stft_f64(ctx, x_bin (f64), length, batch, window_bin, window_is_f64, params) -> {:ok, z_bin (c128), num_frames, times_bin, freqs_bin}
+ * stft_c128: the same with complex f64 samples (lib/nx_signal.ex:94-102 on a c128 tensor, or c64 samples under an f64 window);
+ *   times / frequencies stay f32 like the reference's (lib/nx_signal.ex:106-111)
+ * stft_dev(ctx, x_buf, length, batch, window_bin, params) -> {:ok, z_buf, num_frames}; stft_c64_dev: x_buf holds c64 samples */
+static ERL_NIF_TERM stft_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int cplx, int f64, int mem) {
   ctx_res_t* c;
-  ErlNifBinary x, w, zb, tb, fb;
-  ErlNifSInt64 length;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p))
+  frames_args_t a;
+  const void* x;
+  result_t r[3] = {{0}};   /* spectrum, times, frequencies */
+  if (argc != 6 + f64 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, f64, 0, &a) ||
+      !get_rows(env, argv[1], c, mem, (size_t)(f64 ? 8 : 4) << cplx, a.batch, a.len, 1, &x))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size / elem / (size_t)batch != (size_t)length || x.size % elem || w.size != (size_t)p.frame_length * 4)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&zb, (uint64_t)batch, (uint64_t)m, (uint64_t)p.fft_length, 8)) return mk_oom(env);
-  int rc = elem == 8 ? nxsig_stft_c64(c->ctx, (const nxsig_c64*)x.data, length, batch, length, (const float*)w.data, &p, (nxsig_c64*)zb.data, NULL, NXSIG_HOST)
-                     : nxsig_stft_f32(c->ctx, (const float*)x.data, length, batch, length, (const float*)w.data, &p, (nxsig_c64*)zb.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&zb); return mk_error(env, rc); }
-  if (!out_bin(&tb, (uint64_t)m, 1, 1, 4)) { enif_release_binary(&zb); return mk_oom(env); }
-  if (!out_bin(&fb, (uint64_t)p.fft_length, 1, 1, 4)) { enif_release_binary(&zb); enif_release_binary(&tb); return mk_oom(env); }
-  if ((rc = nxsig_stft_times_f32(p.frame_length, p.sampling_rate, m, (float*)tb.data)) ||
-      (rc = nxsig_fft_frequencies_f32(p.sampling_rate, p.fft_length, 0, (float*)fb.data))) {
-    enif_release_binary(&zb); enif_release_binary(&tb); enif_release_binary(&fb);
-    return mk_error(env, rc);
-  }
-  return enif_make_tuple5(env, mk_atom(env, "ok"), enif_make_binary(env, &zb), enif_make_int64(env, m), enif_make_binary(env, &tb),
-                          enif_make_binary(env, &fb));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&r[0], c, mem, f64 ? 16 : 8, (uint64_t)a.batch, (uint64_t)a.out, (uint64_t)a.p.fft_length);
+  if (!rc)
+    rc = f64 ? (cplx ? nxsig_stft_c128(c->ctx, (const nxsig_c128*)x, a.len, a.batch, a.len, a.w.data, a.wf64, &a.p, (nxsig_c128*)r[0].data, NULL, mem)
+                     : nxsig_stft_f64(c->ctx, (const double*)x, a.len, a.batch, a.len, a.w.data, a.wf64, &a.p, (nxsig_c128*)r[0].data, NULL, mem))
+             : (cplx ? nxsig_stft_c64(c->ctx, (const nxsig_c64*)x, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, (nxsig_c64*)r[0].data, NULL, mem)
+                     : nxsig_stft_f32(c->ctx, (const float*)x, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, (nxsig_c64*)r[0].data, NULL, mem));
+  if (mem == NXSIG_DEVICE) return res_ok2(env, &r[0], rc, a.out);
+  /* the times and frequencies binaries of a host result */
+  if (!rc) rc = res_open(&r[1], NULL, NXSIG_HOST, 4, (uint64_t)a.out, 1, 1);
+  if (!rc) rc = res_open(&r[2], NULL, NXSIG_HOST, 4, (uint64_t)a.p.fft_length, 1, 1);
+  if (!rc) rc = nxsig_stft_times_f32(a.p.frame_length, a.p.sampling_rate, a.out, (float*)r[1].data);
+  if (!rc) rc = nxsig_fft_frequencies_f32(a.p.sampling_rate, a.p.fft_length, 0, (float*)r[2].data);
+  if (rc) return res_fail(env, r, 3, rc);
+  return enif_make_tuple5(env, mk_atom(env, "ok"), res_term(env, &r[0]), enif_make_int64(env, a.out), res_term(env, &r[1]), res_term(env, &r[2]));
 }
+static ERL_NIF_TERM nif_stft(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_any(env, argc, argv, 0, 0, NXSIG_HOST); }
+static ERL_NIF_TERM nif_stft_c64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_any(env, argc, argv, 1, 0, NXSIG_HOST); }
+static ERL_NIF_TERM nif_stft_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_any(env, argc, argv, 0, 1, NXSIG_HOST); }
+static ERL_NIF_TERM nif_stft_c128(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_any(env, argc, argv, 1, 1, NXSIG_HOST); }
+static ERL_NIF_TERM nif_stft_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_any(env, argc, argv, 0, 0, NXSIG_DEVICE); }
+static ERL_NIF_TERM nif_stft_c64_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_any(env, argc, argv, 1, 0, NXSIG_DEVICE); }
 
-static ERL_NIF_TERM nif_stft(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_host(env, argc, argv, 4); }
-static ERL_NIF_TERM nif_stft_c64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_host(env, argc, argv, 8); }
-
-/* istft(ctx, z_bin, num_frames, batch, window_bin, params) -> {:ok, y_bin} */
-static ERL_NIF_TERM nif_istft(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* istft(ctx, z_bin, num_frames, batch, window_bin, params) -> {:ok, y_bin}
+ * istft_c128(ctx, z_bin (c128), num_frames, batch, window_bin, window_is_f64, params) -> {:ok, y_bin (c128)}
+ * istft_dev(ctx, z_buf, num_frames, batch, window_bin, params) -> {:ok, y_buf} */
+static ERL_NIF_TERM istft_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64, int mem) {
   ctx_res_t* c;
-  ErlNifBinary z, w, yb;
-  ErlNifSInt64 m;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p))
+  frames_args_t a;
+  const void* z;
+  result_t y = {0};
+  const size_t elem = f64 ? 16 : 8;
+  if (argc != 6 + f64 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, f64, 1, &a) ||
+      !get_rows(env, argv[1], c, mem, elem, a.batch, a.len, a.p.fft_length, &z))
     return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || z.size % 8 || z.size / 8 / (size_t)batch / (size_t)m != (size_t)p.fft_length ||
-      z.size / 8 % ((size_t)batch * (size_t)m) || w.size != (size_t)p.frame_length * 4)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 8)) return mk_oom(env);
-  int rc = nxsig_istft_c64(c->ctx, (const nxsig_c64*)z.data, m, batch, (const float*)w.data, &p, (nxsig_c64*)yb.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&y, c, mem, elem, (uint64_t)a.batch, (uint64_t)a.out, 1);
+  if (!rc)
+    rc = f64 ? nxsig_istft_c128(c->ctx, (const nxsig_c128*)z, a.len, a.batch, a.w.data, a.wf64, &a.p, (nxsig_c128*)y.data, mem)
+             : nxsig_istft_c64(c->ctx, (const nxsig_c64*)z, a.len, a.batch, (const float*)a.w.data, &a.p, (nxsig_c64*)y.data, mem);
+  return res_ok(env, &y, rc);
 }
+static ERL_NIF_TERM nif_istft(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return istft_any(env, argc, argv, 0, NXSIG_HOST); }
+static ERL_NIF_TERM nif_istft_c128(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return istft_any(env, argc, argv, 1, NXSIG_HOST); }
+static ERL_NIF_TERM nif_istft_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return istft_any(env, argc, argv, 0, NXSIG_DEVICE); }
 
 /* istft_filtered(ctx, z_bin, num_frames, batch, window_bin, params, h_bin) -> {:ok, y_bin}
- * NxSignal.istft(Nx.multiply(z, hfft), window, opts) in one library call (guides/filtering.livemd:141 + :150-157) */
-static ERL_NIF_TERM nif_istft_filtered(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+ * NxSignal.istft(Nx.multiply(z, hfft), window, opts) in one library call (guides/filtering.livemd:141 + :150-157)
+ * istft_filtered_dev(ctx, z_buf, num_frames, batch, window_bin, params, h_bin) -> {:ok, y_buf}   (z_buf is left untouched) */
+static ERL_NIF_TERM istft_filtered_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int mem) {
   ctx_res_t* c;
-  ErlNifBinary z, w, h, yb;
-  ErlNifSInt64 m;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_inspect_binary(env, argv[6], &h))
+  frames_args_t a;
+  ErlNifBinary h;
+  const void* z;
+  result_t y = {0};
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, 0, 1, &a) || !enif_inspect_binary(env, argv[6], &h) ||
+      h.size != (size_t)a.p.fft_length * 8 || !get_rows(env, argv[1], c, mem, 8, a.batch, a.len, a.p.fft_length, &z))
     return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || p.fft_length < 1 || z.size % 8 || z.size / 8 / (size_t)batch / (size_t)m != (size_t)p.fft_length ||
-      z.size / 8 % ((size_t)batch * (size_t)m) || w.size != (size_t)p.frame_length * 4 || h.size != (size_t)p.fft_length * 8)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 8)) return mk_oom(env);
-  int rc = nxsig_istft_filtered_c64(c->ctx, (const nxsig_c64*)z.data, m, batch, (const float*)w.data, &p, (const nxsig_c64*)h.data,
-                                    (nxsig_c64*)yb.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&y, c, mem, 8, (uint64_t)a.batch, (uint64_t)a.out, 1);
+  if (!rc)
+    rc = nxsig_istft_filtered_c64(c->ctx, (const nxsig_c64*)z, a.len, a.batch, (const float*)a.w.data, &a.p, (const nxsig_c64*)h.data,
+                                  (nxsig_c64*)y.data, mem);
+  return res_ok(env, &y, rc);
+}
+static ERL_NIF_TERM nif_istft_filtered(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return istft_filtered_any(env, argc, argv, NXSIG_HOST); }
+static ERL_NIF_TERM nif_istft_filtered_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return istft_filtered_any(env, argc, argv, NXSIG_DEVICE); }
+
+/* The argument run the FIR NIFs have at argv[2 ...]: length, batch, taps_bin (f32, or f64 on the f64 tier), mode; `out` as in
+ * frames_args_t: nxsig_conv_length(length, taps, mode) samples per result row, or the library's status */
+typedef struct {
+  ErlNifSInt64 len;
+  int batch, taps, mode;
+  ErlNifBinary h;
+  int64_t out;
+} fir_args_t;
+static int get_fir_args(ErlNifEnv* env, const ERL_NIF_TERM* argv, size_t elem, fir_args_t* a) {
+  if (!enif_get_int64(env, argv[0], &a->len) || !enif_get_int(env, argv[1], &a->batch) || !enif_inspect_binary(env, argv[2], &a->h) ||
+      !enif_get_int(env, argv[3], &a->mode))
+    return 0;
+  if (a->batch < 1 || a->len < 1 || a->h.size < elem || a->h.size % elem || a->h.size / elem > 0x7fffffff) return 0;
+  a->taps = (int)(a->h.size / elem);
+  a->out = nxsig_conv_length(a->len, a->taps, a->mode);
+  return 1;
 }
 
-/* fir(ctx, x_bin, length, batch, taps_bin, mode) -> {:ok, y_bin}   (Convolution.convolve(method: :fft), real 1-D rows) */
-static ERL_NIF_TERM nif_fir(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* fir(ctx, x_bin, length, batch, taps_bin, mode) -> {:ok, y_bin}   (Convolution.convolve(method: :fft), real 1-D rows)
+ * fir_f64(ctx, x_bin (f64), length, batch, taps_bin (f64), mode) -> {:ok, y_bin (f64)}
+ * fir_dev(ctx, x_buf, length, batch, taps_bin, mode) -> {:ok, y_buf, out_length} */
+static ERL_NIF_TERM fir_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64, int mem) {
   ctx_res_t* c;
-  ErlNifBinary x, h, yb;
-  ErlNifSInt64 length;
-  int batch, mode;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &h) || !enif_get_int(env, argv[5], &mode))
+  fir_args_t a;
+  const void* x;
+  result_t y = {0};
+  const size_t elem = f64 ? 8 : 4;
+  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_fir_args(env, argv + 2, elem, &a) ||
+      !get_rows(env, argv[1], c, mem, elem, a.batch, a.len, 1, &x))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length || h.size < 4 || h.size % 4 ||
-      h.size / 4 > 0x7fffffff)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_conv_length(length, (int64_t)(h.size / 4), mode);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 4)) return mk_oom(env);
-  int rc = nxsig_fir_f32(c->ctx, (const float*)x.data, length, batch, length, (const float*)h.data, (int)(h.size / 4), mode,
-                         (float*)yb.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&y, c, mem, elem, (uint64_t)a.batch, (uint64_t)a.out, 1);
+  if (!rc)
+    rc = f64 ? nxsig_fir_f64(c->ctx, (const double*)x, a.len, a.batch, a.len, (const double*)a.h.data, a.taps, a.mode, (double*)y.data, mem)
+             : nxsig_fir_f32(c->ctx, (const float*)x, a.len, a.batch, a.len, (const float*)a.h.data, a.taps, a.mode, (float*)y.data, mem);
+  return mem == NXSIG_DEVICE ? res_ok2(env, &y, rc, a.out) : res_ok(env, &y, rc);
 }
+static ERL_NIF_TERM nif_fir(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fir_any(env, argc, argv, 0, NXSIG_HOST); }
+static ERL_NIF_TERM nif_fir_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fir_any(env, argc, argv, 1, NXSIG_HOST); }
+static ERL_NIF_TERM nif_fir_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fir_any(env, argc, argv, 0, NXSIG_DEVICE); }
 
-/* as_windowed(ctx, x_bin, length, batch, window_length, stride, pad_mode, pad_lo, pad_hi) -> {:ok, frames_bin, num_frames} */
-static ERL_NIF_TERM nif_as_windowed(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* as_windowed(ctx, x_bin, length, batch, window_length, stride, pad_mode, pad_lo, pad_hi) -> {:ok, frames_bin, num_frames}
+ * as_windowed_f64: the same on f64 binaries */
+static ERL_NIF_TERM as_windowed_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
   ctx_res_t* c;
-  ErlNifBinary x, ob;
   ErlNifSInt64 length, lo, hi;
   int batch, wl, stride, pad;
-  if (argc != 9 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_get_int(env, argv[4], &wl) || !enif_get_int(env, argv[5], &stride) ||
-      !enif_get_int(env, argv[6], &pad) || !enif_get_int64(env, argv[7], &lo) || !enif_get_int64(env, argv[8], &hi))
+  const void* x;
+  result_t o = {0};
+  const size_t elem = f64 ? 8 : 4;
+  if (argc != 9 || !get_ctx(env, argv[0], &c) || !enif_get_int64(env, argv[2], &length) || !enif_get_int(env, argv[3], &batch) ||
+      !enif_get_int(env, argv[4], &wl) || !enif_get_int(env, argv[5], &stride) || !enif_get_int(env, argv[6], &pad) ||
+      !enif_get_int64(env, argv[7], &lo) || !enif_get_int64(env, argv[8], &hi) ||
+      !get_rows(env, argv[1], c, NXSIG_HOST, elem, batch, length, 1, &x))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length) return enif_make_badarg(env);
   int64_t m = nxsig_num_frames(length, wl, stride, pad, lo, hi);
   if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)m, (uint64_t)wl, 4)) return mk_oom(env);
-  int rc = nxsig_as_windowed_f32(c->ctx, (const float*)x.data, length, batch, length, wl, stride, pad, lo, hi, (float*)ob.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &ob), enif_make_int64(env, m));
+  int rc = res_open(&o, c, NXSIG_HOST, elem, (uint64_t)batch, (uint64_t)m, (uint64_t)wl);
+  if (!rc)
+    rc = f64 ? nxsig_as_windowed_f64(c->ctx, (const double*)x, length, batch, length, wl, stride, pad, lo, hi, (double*)o.data, NULL, NXSIG_HOST)
+             : nxsig_as_windowed_f32(c->ctx, (const float*)x, length, batch, length, wl, stride, pad, lo, hi, (float*)o.data, NULL, NXSIG_HOST);
+  return res_ok2(env, &o, rc, m);
 }
+static ERL_NIF_TERM nif_as_windowed(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return as_windowed_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_as_windowed_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return as_windowed_any(env, argc, argv, 1); }
 
-/* overlap_and_add(ctx, frames_bin, num_frames, batch, frame_length, overlap_length, components) -> {:ok, out_bin} */
-static ERL_NIF_TERM nif_overlap_and_add(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* overlap_and_add(ctx, frames_bin, num_frames, batch, frame_length, overlap_length, components) -> {:ok, out_bin}
+ * overlap_and_add_f64: the same on f64 (components 1) / c128 (2) binaries */
+static ERL_NIF_TERM overlap_and_add_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
   ctx_res_t* c;
-  ErlNifBinary f, ob;
   ErlNifSInt64 m;
   int batch, n, overlap, comps;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &f) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_get_int(env, argv[4], &n) || !enif_get_int(env, argv[5], &overlap) ||
-      !enif_get_int(env, argv[6], &comps))
-    return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || n < 1 || (comps != 1 && comps != 2) || f.size % ((size_t)4 * (size_t)comps) ||
-      f.size / 4 / (size_t)comps / (size_t)batch / (size_t)m != (size_t)n || f.size / 4 / (size_t)comps % ((size_t)batch * (size_t)m))
+  const void* f;
+  result_t o = {0};
+  const size_t elem = f64 ? 8 : 4;
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_get_int64(env, argv[2], &m) || !enif_get_int(env, argv[3], &batch) ||
+      !enif_get_int(env, argv[4], &n) || !enif_get_int(env, argv[5], &overlap) || !enif_get_int(env, argv[6], &comps) ||
+      (comps != 1 && comps != 2) || !get_rows(env, argv[1], c, NXSIG_HOST, elem * (size_t)comps, batch, m, n, &f))
     return enif_make_badarg(env);
   /* the reference's own check (lib/nx_signal.ex:692-695) must surface as ArgumentError, not badarg: let the library say it */
   int64_t out_len = (overlap >= 0 && overlap < n) ? m * (int64_t)(n - overlap) + overlap : 1;
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)out_len, (uint64_t)comps, 4)) return mk_oom(env);
-  int rc = nxsig_overlap_and_add(c->ctx, (const float*)f.data, m, batch, n, overlap, comps, (float*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&o, c, NXSIG_HOST, elem, (uint64_t)batch, (uint64_t)out_len, (uint64_t)comps);
+  if (!rc)
+    rc = f64 ? nxsig_overlap_and_add_f64(c->ctx, (const double*)f, m, batch, n, overlap, comps, (double*)o.data, NXSIG_HOST)
+             : nxsig_overlap_and_add(c->ctx, (const float*)f, m, batch, n, overlap, comps, (float*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
+static ERL_NIF_TERM nif_overlap_and_add(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return overlap_and_add_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_overlap_and_add_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return overlap_and_add_any(env, argc, argv, 1); }
 
-/* fft(ctx, in_bin, in_is_real, rows, n_in, fft_length, inverse) -> {:ok, c64 binary}   (Nx.fft / Nx.ifft over the last axis) */
-static ERL_NIF_TERM nif_fft(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+/* fft(ctx, in_bin, in_is_real, rows, n_in, fft_length, inverse) -> {:ok, c64 binary}   (Nx.fft / Nx.ifft over the last axis)
+ * fft_c128: the same -> {:ok, c128 binary}   (Nx.fft / Nx.ifft of f64 / c128 rows) */
+static ERL_NIF_TERM fft_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int f64) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
   ErlNifSInt64 rows;
   int is_real, n_in, k, inv;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !enif_get_int(env, argv[2], &is_real) ||
-      !enif_get_int64(env, argv[3], &rows) || !enif_get_int(env, argv[4], &n_in) || !enif_get_int(env, argv[5], &k) ||
-      !enif_get_int(env, argv[6], &inv))
+  const void* in;
+  result_t o = {0};
+  const size_t real = f64 ? 8 : 4;
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[2], &is_real) || !enif_get_int64(env, argv[3], &rows) ||
+      !enif_get_int(env, argv[4], &n_in) || !enif_get_int(env, argv[5], &k) || !enif_get_int(env, argv[6], &inv) || k < 1 ||
+      !get_rows(env, argv[1], c, NXSIG_HOST, is_real ? real : 2 * real, rows, n_in, 1, &in))
     return enif_make_badarg(env);
-  const size_t es = is_real ? 4 : 8;
-  if (rows < 1 || n_in < 1 || k < 1 || in.size % es || in.size / es / (size_t)rows != (size_t)n_in || in.size / es % (size_t)rows)
-    return enif_make_badarg(env);
-  if (!out_bin(&ob, (uint64_t)rows, (uint64_t)k, 1, 8)) return mk_oom(env);
-  int rc = nxsig_fft(c->ctx, in.data, is_real, rows, n_in, k, inv, (nxsig_c64*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&o, c, NXSIG_HOST, 2 * real, (uint64_t)rows, (uint64_t)k, 1);
+  if (!rc)
+    rc = f64 ? nxsig_fft_c128(c->ctx, in, is_real, rows, n_in, k, inv, (nxsig_c128*)o.data, NXSIG_HOST)
+             : nxsig_fft(c->ctx, in, is_real, rows, n_in, k, inv, (nxsig_c64*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
-
-/* ------------------------------------------------------------------------------------------------ f64 / c128 tier
- * The reference computes in the type of its operands (include/nxsig.h "f64 / c128 tier"): f64 / c128 binaries in, the same out. */
-/* window_f64(kind, n, periodic, beta, eps) -> {:ok, f64 binary}   (NxSignal.Windows.*(n, type: {:f, 64})) */
-static ERL_NIF_TERM nif_window_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  int kind, n, per;
-  double beta, eps;
-  if (argc != 5 || !enif_get_int(env, argv[0], &kind) || !enif_get_int(env, argv[1], &n) || !enif_get_int(env, argv[2], &per) ||
-      !get_number(env, argv[3], &beta) || !get_number(env, argv[4], &eps) || n < 0)
-    return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)n, 1, 1, 8)) return mk_oom(env);
-  int rc = nxsig_window_f64(kind, n, per, beta, eps, (double*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
-}
-
-/* firwin_f64(num_taps, [cutoff], window_kind, beta, pass_zero, scale, sampling_rate) -> {:ok, f64 binary} */
-static ERL_NIF_TERM nif_firwin_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  int taps, kind, pz, sc;
-  double beta, fs, cut[64];
-  unsigned len;
-  if (argc != 7 || !enif_get_int(env, argv[0], &taps) || !enif_get_list_length(env, argv[1], &len) || len > 64 ||
-      !enif_get_int(env, argv[2], &kind) || !get_number(env, argv[3], &beta) || !enif_get_int(env, argv[4], &pz) ||
-      !enif_get_int(env, argv[5], &sc) || !get_number(env, argv[6], &fs) || taps < 1)
-    return enif_make_badarg(env);
-  ERL_NIF_TERM head, tail = argv[1];
-  for (unsigned i = 0; i < len; ++i)
-    if (!enif_get_list_cell(env, tail, &head, &tail) || !get_number(env, head, &cut[i])) return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)taps, 1, 1, 8)) return mk_oom(env);
-  int rc = nxsig_firwin_f64(taps, cut, (int)len, kind, beta, pz, sc, fs, (double*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
-}
-
-/* fft_frequencies_f64(sampling_rate, fft_length, endpoint) -> {:ok, f64 binary} */
-static ERL_NIF_TERM nif_fft_frequencies_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  double fs;
-  int k, endpoint;
-  if (argc != 3 || !get_number(env, argv[0], &fs) || !enif_get_int(env, argv[1], &k) || !enif_get_int(env, argv[2], &endpoint) || k < 1)
-    return enif_make_badarg(env);
-  ErlNifBinary b;
-  if (!out_bin(&b, (uint64_t)k, 1, 1, 8)) return mk_oom(env);
-  int rc = nxsig_fft_frequencies_f64(fs, k, endpoint, (double*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
-}
-
-/* sinc_f64(t_bin) -> {:ok, f64 binary} */
-static ERL_NIF_TERM nif_sinc_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ErlNifBinary t, b;
-  if (argc != 1 || !enif_inspect_binary(env, argv[0], &t) || t.size % 8) return enif_make_badarg(env);
-  if (!out_bin(&b, t.size / 8, 1, 1, 8)) return mk_oom(env);
-  int rc = nxsig_sinc_f64((const double*)t.data, (int64_t)(t.size / 8), (double*)b.data);
-  if (rc) { enif_release_binary(&b); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &b));
-}
-
-/* stft_f64(ctx, x_bin (f64), length, batch, window_bin, window_is_f64, params) -> {:ok, z_bin (c128), num_frames, times_bin, freqs_bin}
- * times / frequencies stay f32 like the reference's (lib/nx_signal.ex:106-111) */
-static ERL_NIF_TERM nif_stft_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary x, w, zb, tb, fb;
-  ErlNifSInt64 length;
-  int batch, wf64;
-  nxsig_stft_params p;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !enif_get_int(env, argv[5], &wf64) ||
-      !get_params(env, argv[6], &p))
-    return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 8 || x.size / 8 / (size_t)batch != (size_t)length ||
-      w.size != (size_t)p.frame_length * (wf64 ? 8 : 4))
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&zb, (uint64_t)batch, (uint64_t)m, (uint64_t)p.fft_length, 16)) return mk_oom(env);
-  int rc = nxsig_stft_f64(c->ctx, (const double*)x.data, length, batch, length, w.data, wf64, &p, (nxsig_c128*)zb.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&zb); return mk_error(env, rc); }
-  if (!out_bin(&tb, (uint64_t)m, 1, 1, 4)) { enif_release_binary(&zb); return mk_oom(env); }
-  if (!out_bin(&fb, (uint64_t)p.fft_length, 1, 1, 4)) { enif_release_binary(&zb); enif_release_binary(&tb); return mk_oom(env); }
-  if ((rc = nxsig_stft_times_f32(p.frame_length, p.sampling_rate, m, (float*)tb.data)) ||
-      (rc = nxsig_fft_frequencies_f32(p.sampling_rate, p.fft_length, 0, (float*)fb.data))) {
-    enif_release_binary(&zb); enif_release_binary(&tb); enif_release_binary(&fb);
-    return mk_error(env, rc);
-  }
-  return enif_make_tuple5(env, mk_atom(env, "ok"), enif_make_binary(env, &zb), enif_make_int64(env, m), enif_make_binary(env, &tb),
-                          enif_make_binary(env, &fb));
-}
-
-/* stft_c128(ctx, x_bin (c128), length, batch, window_bin, window_is_f64, params) -> {:ok, z_bin (c128), num_frames, times_bin, freqs_bin}
- * complex f64 samples (lib/nx_signal.ex:94-102 on a c128 tensor, or c64 samples under an f64 window) */
-static ERL_NIF_TERM nif_stft_c128(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary x, w, zb, tb, fb;
-  ErlNifSInt64 length;
-  int batch, wf64;
-  nxsig_stft_params p;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !enif_get_int(env, argv[5], &wf64) ||
-      !get_params(env, argv[6], &p))
-    return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 16 || x.size / 16 / (size_t)batch != (size_t)length ||
-      w.size != (size_t)p.frame_length * (wf64 ? 8 : 4))
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&zb, (uint64_t)batch, (uint64_t)m, (uint64_t)p.fft_length, 16)) return mk_oom(env);
-  int rc = nxsig_stft_c128(c->ctx, (const nxsig_c128*)x.data, length, batch, length, w.data, wf64, &p, (nxsig_c128*)zb.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&zb); return mk_error(env, rc); }
-  if (!out_bin(&tb, (uint64_t)m, 1, 1, 4)) { enif_release_binary(&zb); return mk_oom(env); }
-  if (!out_bin(&fb, (uint64_t)p.fft_length, 1, 1, 4)) { enif_release_binary(&zb); enif_release_binary(&tb); return mk_oom(env); }
-  if ((rc = nxsig_stft_times_f32(p.frame_length, p.sampling_rate, m, (float*)tb.data)) ||
-      (rc = nxsig_fft_frequencies_f32(p.sampling_rate, p.fft_length, 0, (float*)fb.data))) {
-    enif_release_binary(&zb); enif_release_binary(&tb); enif_release_binary(&fb);
-    return mk_error(env, rc);
-  }
-  return enif_make_tuple5(env, mk_atom(env, "ok"), enif_make_binary(env, &zb), enif_make_int64(env, m), enif_make_binary(env, &tb),
-                          enif_make_binary(env, &fb));
-}
-
-/* istft_c128(ctx, z_bin (c128), num_frames, batch, window_bin, window_is_f64, params) -> {:ok, y_bin (c128)} */
-static ERL_NIF_TERM nif_istft_c128(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary z, w, yb;
-  ErlNifSInt64 m;
-  int batch, wf64;
-  nxsig_stft_params p;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !enif_get_int(env, argv[5], &wf64) ||
-      !get_params(env, argv[6], &p))
-    return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || z.size % 16 || z.size / 16 / (size_t)batch / (size_t)m != (size_t)p.fft_length ||
-      z.size / 16 % ((size_t)batch * (size_t)m) || w.size != (size_t)p.frame_length * (wf64 ? 8 : 4))
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 16)) return mk_oom(env);
-  int rc = nxsig_istft_c128(c->ctx, (const nxsig_c128*)z.data, m, batch, w.data, wf64, &p, (nxsig_c128*)yb.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
-}
-
-/* fir_f64(ctx, x_bin (f64), length, batch, taps_bin (f64), mode) -> {:ok, y_bin (f64)} */
-static ERL_NIF_TERM nif_fir_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary x, h, yb;
-  ErlNifSInt64 length;
-  int batch, mode;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &h) || !enif_get_int(env, argv[5], &mode))
-    return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 8 || x.size / 8 / (size_t)batch != (size_t)length || h.size < 8 || h.size % 8 ||
-      h.size / 8 > 0x7fffffff)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_conv_length(length, (int64_t)(h.size / 8), mode);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 8)) return mk_oom(env);
-  int rc = nxsig_fir_f64(c->ctx, (const double*)x.data, length, batch, length, (const double*)h.data, (int)(h.size / 8), mode,
-                         (double*)yb.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
-}
-
-/* fft_c128(ctx, in_bin, in_is_real, rows, n_in, fft_length, inverse) -> {:ok, c128 binary}   (Nx.fft / Nx.ifft of f64 / c128 rows) */
-static ERL_NIF_TERM nif_fft_c128(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary in, ob;
-  ErlNifSInt64 rows;
-  int is_real, n_in, k, inv;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !enif_get_int(env, argv[2], &is_real) ||
-      !enif_get_int64(env, argv[3], &rows) || !enif_get_int(env, argv[4], &n_in) || !enif_get_int(env, argv[5], &k) ||
-      !enif_get_int(env, argv[6], &inv))
-    return enif_make_badarg(env);
-  const size_t es = is_real ? 8 : 16;
-  if (rows < 1 || n_in < 1 || k < 1 || in.size % es || in.size / es / (size_t)rows != (size_t)n_in || in.size / es % (size_t)rows)
-    return enif_make_badarg(env);
-  if (!out_bin(&ob, (uint64_t)rows, (uint64_t)k, 1, 16)) return mk_oom(env);
-  int rc = nxsig_fft_c128(c->ctx, in.data, is_real, rows, n_in, k, inv, (nxsig_c128*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
-}
-
-/* as_windowed_f64(ctx, x_bin, length, batch, window_length, stride, pad_mode, pad_lo, pad_hi) -> {:ok, frames_bin, num_frames} */
-static ERL_NIF_TERM nif_as_windowed_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary x, ob;
-  ErlNifSInt64 length, lo, hi;
-  int batch, wl, stride, pad;
-  if (argc != 9 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_get_int(env, argv[4], &wl) || !enif_get_int(env, argv[5], &stride) ||
-      !enif_get_int(env, argv[6], &pad) || !enif_get_int64(env, argv[7], &lo) || !enif_get_int64(env, argv[8], &hi))
-    return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 8 || x.size / 8 / (size_t)batch != (size_t)length) return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, wl, stride, pad, lo, hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)m, (uint64_t)wl, 8)) return mk_oom(env);
-  int rc = nxsig_as_windowed_f64(c->ctx, (const double*)x.data, length, batch, length, wl, stride, pad, lo, hi, (double*)ob.data, NULL,
-                                 NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &ob), enif_make_int64(env, m));
-}
-
-/* overlap_and_add_f64(ctx, frames_bin, num_frames, batch, frame_length, overlap_length, components) -> {:ok, out_bin} */
-static ERL_NIF_TERM nif_overlap_and_add_f64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary f, ob;
-  ErlNifSInt64 m;
-  int batch, n, overlap, comps;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &f) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_get_int(env, argv[4], &n) || !enif_get_int(env, argv[5], &overlap) ||
-      !enif_get_int(env, argv[6], &comps))
-    return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || n < 1 || (comps != 1 && comps != 2) || f.size % ((size_t)8 * (size_t)comps) ||
-      f.size / 8 / (size_t)comps / (size_t)batch / (size_t)m != (size_t)n || f.size / 8 / (size_t)comps % ((size_t)batch * (size_t)m))
-    return enif_make_badarg(env);
-  int64_t out_len = (overlap >= 0 && overlap < n) ? m * (int64_t)(n - overlap) + overlap : 1;
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)out_len, (uint64_t)comps, 8)) return mk_oom(env);
-  int rc = nxsig_overlap_and_add_f64(c->ctx, (const double*)f.data, m, batch, n, overlap, comps, (double*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
-}
+static ERL_NIF_TERM nif_fft(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fft_any(env, argc, argv, 0); }
+static ERL_NIF_TERM nif_fft_c128(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return fft_any(env, argc, argv, 1); }
 
 /* fftconvolve_c64(ctx, a_bin, b_bin, mode) -> {:ok, c64 binary}   (1-D complex case of Convolution.fftconvolve/3) */
 static ERL_NIF_TERM nif_fftconvolve_c64(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary a, b, ob;
+  ErlNifBinary a, b;
   int mode;
+  result_t o = {0};
   if (argc != 4 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &a) || !enif_inspect_binary(env, argv[2], &b) ||
       !enif_get_int(env, argv[3], &mode) || a.size < 8 || b.size < 8 || a.size % 8 || b.size % 8)
     return enif_make_badarg(env);
   int64_t n = nxsig_conv_length((int64_t)(a.size / 8), (int64_t)(b.size / 8), mode);
   if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&ob, (uint64_t)n, 1, 1, 8)) return mk_oom(env);
-  int rc = nxsig_fftconvolve_c64(c->ctx, (const nxsig_c64*)a.data, (int64_t)(a.size / 8), (const nxsig_c64*)b.data, (int64_t)(b.size / 8), mode,
-                                 (nxsig_c64*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&o, c, NXSIG_HOST, 8, (uint64_t)n, 1, 1);
+  if (!rc)
+    rc = nxsig_fftconvolve_c64(c->ctx, (const nxsig_c64*)a.data, (int64_t)(a.size / 8), (const nxsig_c64*)b.data, (int64_t)(b.size / 8), mode,
+                               (nxsig_c64*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 static int get_i64_list(ErlNifEnv* env, ERL_NIF_TERM list, int64_t* out, unsigned cap, unsigned* n) {
@@ -677,32 +597,39 @@ static int get_i64_list(ErlNifEnv* env, ERL_NIF_TERM list, int64_t* out, unsigne
   }
   return 1;
 }
+/* a shape list of rank 1 .. 8 without an empty dimension; *n = its element count */
+static int get_shape(ErlNifEnv* env, ERL_NIF_TERM list, int64_t* shape, unsigned* rank, size_t* n) {
+  if (!get_i64_list(env, list, shape, 8, rank) || *rank < 1) return 0;
+  *n = 1;
+  for (unsigned d = 0; d < *rank; ++d)
+    if (shape[d] < 1 || !mul_size(n, (uint64_t)shape[d])) return 0;
+  return 1;
+}
 
 /* fft_nd(ctx, in_bin, in_is_real, shape, axes, lengths, inverse) -> {:ok, c64 binary}   (Transforms.fft_nd / ifft_nd, any axes) */
 static ERL_NIF_TERM nif_fft_nd(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
   int is_real, inv;
   int64_t shape[8], axes64[16], lengths[16], osh[8];
   int32_t axes[16];
   unsigned rank, na, nl;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !enif_get_int(env, argv[2], &is_real) ||
-      !get_i64_list(env, argv[3], shape, 8, &rank) || !get_i64_list(env, argv[4], axes64, 16, &na) ||
-      !get_i64_list(env, argv[5], lengths, 16, &nl) || !enif_get_int(env, argv[6], &inv) || rank < 1 || na != nl)
+  size_t n_in, n_out = 1;
+  const void* in;
+  result_t o = {0};
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[2], &is_real) || !get_shape(env, argv[3], shape, &rank, &n_in) ||
+      !get_i64_list(env, argv[4], axes64, 16, &na) || !get_i64_list(env, argv[5], lengths, 16, &nl) || !enif_get_int(env, argv[6], &inv) ||
+      na != nl || !get_rows(env, argv[1], c, NXSIG_HOST, is_real ? 4 : 8, (int64_t)n_in, 1, 1, &in))
     return enif_make_badarg(env);
-  size_t n_in = 1, n_out = 1;
-  for (unsigned d = 0; d < rank; ++d) { if (shape[d] < 1 || !mul_size(&n_in, (uint64_t)shape[d])) return enif_make_badarg(env); osh[d] = shape[d]; }
-  if (in.size % (is_real ? 4 : 8) || in.size / (is_real ? 4 : 8) != n_in) return enif_make_badarg(env);
+  memcpy(osh, shape, sizeof osh);
   for (unsigned i = 0; i < na; ++i) {
     int64_t ax = axes64[i] < 0 ? axes64[i] + (int64_t)rank : axes64[i];
     if (ax < 0 || ax >= (int64_t)rank || lengths[i] < 1) return enif_make_badarg(env);
     axes[i] = (int32_t)ax; osh[ax] = lengths[i];
   }
   for (unsigned d = 0; d < rank; ++d) if (!mul_size(&n_out, (uint64_t)osh[d])) return mk_oom(env);
-  if (!out_bin(&ob, n_out, 1, 1, 8)) return mk_oom(env);
-  int rc = nxsig_fft_nd(c->ctx, in.data, is_real, shape, (int32_t)rank, axes, lengths, (int32_t)na, inv, (nxsig_c64*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&o, c, NXSIG_HOST, 8, n_out, 1, 1);
+  if (!rc) rc = nxsig_fft_nd(c->ctx, in, is_real, shape, (int32_t)rank, axes, lengths, (int32_t)na, inv, (nxsig_c64*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* fftconvolve_nd(ctx, a_bin, a_is_real, a_shape, b_bin, b_is_real, b_shape, mode) -> {:ok, out_bin, out_shape}
@@ -711,10 +638,11 @@ typedef int (*conv_nd_fn)(nxsig_ctx*, const void*, int32_t, const int64_t*, cons
                           int64_t*, int32_t);
 static ERL_NIF_TERM conv_nd_common(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], conv_nd_fn fn, const char* rank_msg) {
   ctx_res_t* c;
-  ErlNifBinary a, b, ob;
+  ErlNifBinary a, b;
   int a_real, b_real, mode;
   int64_t s1[8], s2[8], osh[8];
   unsigned r1, r2;
+  result_t o = {0};
   if (argc != 8 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &a) || !enif_get_int(env, argv[2], &a_real) ||
       !get_i64_list(env, argv[3], s1, 8, &r1) || !enif_inspect_binary(env, argv[4], &b) || !enif_get_int(env, argv[5], &b_real) ||
       !get_i64_list(env, argv[6], s2, 8, &r2) || !enif_get_int(env, argv[7], &mode) || r1 < 1)
@@ -729,14 +657,14 @@ static ERL_NIF_TERM conv_nd_common(ErlNifEnv* env, int argc, const ERL_NIF_TERM 
   if (a.size % (a_real ? 4 : 8) || a.size / (a_real ? 4 : 8) != na || b.size % (b_real ? 4 : 8) || b.size / (b_real ? 4 : 8) != nb)
     return enif_make_badarg(env);
   const size_t es = (a_real && b_real) ? 4 : 8;
-  if (!out_bin(&ob, nfull, 1, 1, es)) return mk_oom(env);  /* every mode's result fits the full size */
-  int rc = fn(c->ctx, a.data, a_real, s1, b.data, b_real, s2, (int32_t)r1, mode, ob.data, osh, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
+  int rc = res_open(&o, c, NXSIG_HOST, es, nfull, 1, 1);  /* every mode's result fits the full size */
+  if (!rc) rc = fn(c->ctx, a.data, a_real, s1, b.data, b_real, s2, (int32_t)r1, mode, o.data, osh, NXSIG_HOST);
+  if (rc) return res_fail(env, &o, 1, rc);
   size_t nres = 1;
   ERL_NIF_TERM dims[8];
   for (unsigned d = 0; d < r1; ++d) { nres *= (size_t)osh[d]; dims[d] = enif_make_int64(env, osh[d]); }
-  if (!enif_realloc_binary(&ob, nres * es)) { enif_release_binary(&ob); return mk_oom(env); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &ob), enif_make_list_from_array(env, dims, r1));
+  if (!enif_realloc_binary(&o.bin, nres * es)) return res_fail(env, &o, 1, RES_NOMEM);
+  return mk_ok2(env, res_term(env, &o), enif_make_list_from_array(env, dims, r1));
 }
 static ERL_NIF_TERM nif_fftconvolve_nd(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   return conv_nd_common(env, argc, argv, nxsig_fftconvolve_nd, "Rank of in1 and in2 must be equal.");  /* convolution.ex:295-296 */
@@ -749,88 +677,70 @@ static ERL_NIF_TERM nif_convolve_direct(ErlNifEnv* env, int argc, const ERL_NIF_
 }
 
 /* filter inputs: binary of prod(shape) f32 / f64 elements, shape and window lists of one length <= 8 */
-static int filter_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], ctx_res_t** c, ErlNifBinary* in, int* is_f64, int64_t* shape, int64_t* ks,
+static int filter_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], ctx_res_t** c, const void** in, int* is_f64, int64_t* shape, int64_t* ks,
                        unsigned* rank, size_t* n) {
   unsigned r2;
-  if (!get_ctx(env, argv[0], c) || !enif_inspect_binary(env, argv[1], in) || !enif_get_int(env, argv[2], is_f64) ||
-      !get_i64_list(env, argv[3], shape, 8, rank) || !get_i64_list(env, argv[4], ks, 8, &r2) || *rank < 1 || r2 != *rank)
-    return 0;
-  *n = 1;
-  for (unsigned d = 0; d < *rank; ++d)
-    if (shape[d] < 1 || !mul_size(n, (uint64_t)shape[d])) return 0;
-  return in->size % (*is_f64 ? 8 : 4) == 0 && in->size / (*is_f64 ? 8 : 4) == *n;
+  return get_ctx(env, argv[0], c) && enif_get_int(env, argv[2], is_f64) && get_shape(env, argv[3], shape, rank, n) &&
+         get_i64_list(env, argv[4], ks, 8, &r2) && r2 == *rank && get_rows(env, argv[1], *c, NXSIG_HOST, *is_f64 ? 8 : 4, (int64_t)*n, 1, 1, in);
 }
 
 /* median(ctx, x_bin, is_f64, shape, kernel_shape) -> {:ok, f32 binary}   (Filters.median/2, lib/nx_signal/filters.ex:17-55) */
 static ERL_NIF_TERM nif_median(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
+  const void* in;
   int is_f64;
   int64_t shape[8], ks[8];
   unsigned rank;
   size_t n;
+  result_t o = {0};
   if (argc != 5 || !filter_args(env, argv, &c, &in, &is_f64, shape, ks, &rank, &n)) return enif_make_badarg(env);
-  if (!out_bin(&ob, n, 1, 1, 4)) return mk_oom(env);
-  int rc = nxsig_median_filter(c->ctx, in.data, is_f64, shape, (int32_t)rank, ks, (float*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&o, c, NXSIG_HOST, 4, n, 1, 1);
+  if (!rc) rc = nxsig_median_filter(c->ctx, in, is_f64, shape, (int32_t)rank, ks, (float*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
-/* the scalar arguments the two resample_poly NIFs share: argv[2 ...] = is_complex, length, batch, taps_bin (f32, gain included), up, down */
-static int resample_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], int* is_complex, ErlNifSInt64* length, int* batch, ErlNifBinary* h, int* up,
-                         int* down) {
-  return enif_get_int(env, argv[2], is_complex) && enif_get_int64(env, argv[3], length) && enif_get_int(env, argv[4], batch) &&
-         enif_inspect_binary(env, argv[5], h) && enif_get_int(env, argv[6], up) && enif_get_int(env, argv[7], down) && *batch >= 1 &&
-         *length >= 1 && h->size % 4 == 0 && h->size / 4 <= 0x7fffffff;
+/* wiener(ctx, x_bin, is_f64, shape, kernel_size, has_noise, noise) -> {:ok, binary of x's type}   (Filters.wiener/2, filters.ex:81-110) */
+static ERL_NIF_TERM nif_wiener(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  ctx_res_t* c;
+  const void* in;
+  int is_f64, has_noise;
+  double noise;
+  int64_t shape[8], ks[8];
+  unsigned rank;
+  size_t n;
+  result_t o = {0};
+  if (argc != 7 || !filter_args(env, argv, &c, &in, &is_f64, shape, ks, &rank, &n) || !enif_get_int(env, argv[5], &has_noise) ||
+      !get_number(env, argv[6], &noise))
+    return enif_make_badarg(env);
+  int rc = res_open(&o, c, NXSIG_HOST, is_f64 ? 8 : 4, n, 1, 1);
+  if (!rc) rc = nxsig_wiener(c->ctx, in, is_f64, shape, (int32_t)rank, ks, has_noise, noise, o.data, NULL, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* resample_poly(ctx, x_bin, is_complex, length, batch, taps_bin, up, down) -> {:ok, y_bin, out_length}
-   (Filters.resample_poly/4: polyphase resampling of f32 / c64 rows by up / down, include/nxsig.h: nxsig_resample_poly) */
-static ERL_NIF_TERM nif_resample_poly(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+ * (Filters.resample_poly/4: polyphase resampling of f32 / c64 rows by up / down, include/nxsig.h: nxsig_resample_poly; the taps are f32,
+ * gain included)
+ * resample_poly_dev(ctx, x_buf, is_complex, length, batch, taps_bin, up, down) -> {:ok, y_buf, out_length} */
+static ERL_NIF_TERM resample_poly_any(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int mem) {
   ctx_res_t* c;
-  ErlNifBinary x, h, yb;
-  ErlNifSInt64 length;
-  int is_complex, batch, up, down;
-  if (argc != 8 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) ||
-      !resample_args(env, argv, &is_complex, &length, &batch, &h, &up, &down))
-    return enif_make_badarg(env);
-  const size_t es = is_complex ? 8 : 4;
-  size_t xbytes = es;
-  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x.size != xbytes) return enif_make_badarg(env);
-  int64_t n = nxsig_resample_length(length, up, down);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, es)) return mk_oom(env);
-  int rc = nxsig_resample_poly(c->ctx, x.data, is_complex, length, batch, length, (const float*)h.data, (int)(h.size / 4), up, down, yb.data,
-                               NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &yb), enif_make_int64(env, n));
-}
-
-/* resample_poly_dev(ctx, x_buf, is_complex, length, batch, taps_bin, up, down) -> {:ok, y_buf, out_length} */
-static ERL_NIF_TERM nif_resample_poly_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  buf_res_t* x;
   ErlNifBinary h;
   ErlNifSInt64 length;
   int is_complex, batch, up, down;
-  if (argc != 8 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &x) ||
-      !resample_args(env, argv, &is_complex, &length, &batch, &h, &up, &down))
-    return enif_make_badarg(env);
-  const size_t es = is_complex ? 8 : 4;
-  size_t xbytes = es;
-  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x->owner != c || x->bytes < xbytes)
+  const void* x;
+  result_t y = {0};
+  if (argc != 8 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[2], &is_complex) || !enif_get_int64(env, argv[3], &length) ||
+      !enif_get_int(env, argv[4], &batch) || !enif_inspect_binary(env, argv[5], &h) || !enif_get_int(env, argv[6], &up) ||
+      !enif_get_int(env, argv[7], &down) || h.size % 4 || h.size / 4 > 0x7fffffff ||
+      !get_rows(env, argv[1], c, mem, is_complex ? 8 : 4, batch, length, 1, &x))
     return enif_make_badarg(env);
   int64_t n = nxsig_resample_length(length, up, down);
   if (n < 0) return mk_error(env, (int)n);
-  size_t ybytes = es;
-  if (!mul_size(&ybytes, (uint64_t)batch) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
-  void* y = NULL;
-  int rc = nxsig_alloc(c->ctx, ybytes, &y);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_resample_poly(c->ctx, x->dptr, is_complex, length, batch, length, (const float*)h.data, (int)(h.size / 4), up, down, y, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), make_buf(env, c, y, ybytes), enif_make_int64(env, n));
+  int rc = res_open(&y, c, mem, is_complex ? 8 : 4, (uint64_t)batch, (uint64_t)n, 1);
+  if (!rc) rc = nxsig_resample_poly(c->ctx, x, is_complex, length, batch, length, (const float*)h.data, (int)(h.size / 4), up, down, y.data, mem);
+  return res_ok2(env, &y, rc, n);
 }
+static ERL_NIF_TERM nif_resample_poly(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return resample_poly_any(env, argc, argv, NXSIG_HOST); }
+static ERL_NIF_TERM nif_resample_poly_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return resample_poly_any(env, argc, argv, NXSIG_DEVICE); }
 
 /* the arguments the welch and csd NIFs share, from argv[at]: length, batch, window_bin (f32), hop, fft_length, detrend, scaling, sampling_rate */
 static int welch_args(ErlNifEnv* env, const ERL_NIF_TERM* argv, ErlNifSInt64* length, int* batch, ErlNifBinary* w, int* hop, int* fft_length,
@@ -845,121 +755,90 @@ static int welch_args(ErlNifEnv* env, const ERL_NIF_TERM* argv, ErlNifSInt64* le
    (Spectral.welch/3: Welch's averaged periodogram of real f32 rows, include/nxsig.h: nxsig_welch_f32) */
 static ERL_NIF_TERM nif_welch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary x, w, pb;
+  ErlNifBinary w;
   ErlNifSInt64 length;
   int batch, hop, fft_length, detrend, scaling;
   double fs;
-  if (argc != 10 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) ||
-      !welch_args(env, argv + 2, &length, &batch, &w, &hop, &fft_length, &detrend, &scaling, &fs))
+  const void* x;
+  result_t o = {0};
+  if (argc != 10 || !get_ctx(env, argv[0], &c) || !welch_args(env, argv + 2, &length, &batch, &w, &hop, &fft_length, &detrend, &scaling, &fs) ||
+      !get_rows(env, argv[1], c, NXSIG_HOST, 4, batch, length, 1, &x))
     return enif_make_badarg(env);
-  size_t xbytes = 4;
-  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x.size != xbytes) return enif_make_badarg(env);
   int32_t nb = nxsig_welch_bins(fft_length);
   if (nb < 0) return mk_error(env, nb);
-  if (!out_bin(&pb, (uint64_t)batch, (uint64_t)nb, 1, 4)) return mk_oom(env);
-  int rc = nxsig_welch_f32(c->ctx, (const float*)x.data, length, batch, length, (const float*)w.data, (int)(w.size / 4), hop, fft_length,
-                           detrend, scaling, fs, (float*)pb.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&pb); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &pb), enif_make_int(env, nb));
+  int rc = res_open(&o, c, NXSIG_HOST, 4, (uint64_t)batch, (uint64_t)nb, 1);
+  if (!rc)
+    rc = nxsig_welch_f32(c->ctx, (const float*)x, length, batch, length, (const float*)w.data, (int)(w.size / 4), hop, fft_length, detrend, scaling,
+                         fs, (float*)o.data, NXSIG_HOST);
+  return res_ok2(env, &o, rc, nb);
 }
 
 /* csd(ctx, x_bin, y_bin, length, batch, window_bin, hop, fft_length, detrend, scaling, sampling_rate) -> {:ok, pxy_bin, pxx_bin, pyy_bin, bins}
    (Spectral.csd/4 and coherence/4: the cross spectrum c64 and both auto-spectra f32 of one call, nxsig_csd_f32) */
 static ERL_NIF_TERM nif_csd(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary x, y, w, pxy, pxx, pyy;
+  ErlNifBinary w;
   ErlNifSInt64 length;
   int batch, hop, fft_length, detrend, scaling;
   double fs;
-  if (argc != 11 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_inspect_binary(env, argv[2], &y) ||
-      !welch_args(env, argv + 3, &length, &batch, &w, &hop, &fft_length, &detrend, &scaling, &fs))
-    return enif_make_badarg(env);
-  size_t xbytes = 4;
-  if (!mul_size(&xbytes, (uint64_t)batch) || !mul_size(&xbytes, (uint64_t)length) || x.size != xbytes || y.size != xbytes)
+  const void *x, *y;
+  result_t r[3] = {{0}};   /* pxy, pxx, pyy */
+  if (argc != 11 || !get_ctx(env, argv[0], &c) || !welch_args(env, argv + 3, &length, &batch, &w, &hop, &fft_length, &detrend, &scaling, &fs) ||
+      !get_rows(env, argv[1], c, NXSIG_HOST, 4, batch, length, 1, &x) || !get_rows(env, argv[2], c, NXSIG_HOST, 4, batch, length, 1, &y))
     return enif_make_badarg(env);
   int32_t nb = nxsig_welch_bins(fft_length);
   if (nb < 0) return mk_error(env, nb);
-  if (!out_bin(&pxy, (uint64_t)batch, (uint64_t)nb, 1, 8)) return mk_oom(env);
-  if (!out_bin(&pxx, (uint64_t)batch, (uint64_t)nb, 1, 4)) { enif_release_binary(&pxy); return mk_oom(env); }
-  if (!out_bin(&pyy, (uint64_t)batch, (uint64_t)nb, 1, 4)) { enif_release_binary(&pxy); enif_release_binary(&pxx); return mk_oom(env); }
-  int rc = nxsig_csd_f32(c->ctx, (const float*)x.data, (const float*)y.data, length, batch, length, (const float*)w.data, (int)(w.size / 4), hop,
-                         fft_length, detrend, scaling, fs, (float*)pxx.data, (float*)pyy.data, (nxsig_c64*)pxy.data, NXSIG_HOST);
-  if (rc) {
-    enif_release_binary(&pxy); enif_release_binary(&pxx); enif_release_binary(&pyy);
-    return mk_error(env, rc);
-  }
-  return enif_make_tuple5(env, mk_atom(env, "ok"), enif_make_binary(env, &pxy), enif_make_binary(env, &pxx), enif_make_binary(env, &pyy),
-                          enif_make_int(env, nb));
-}
-
-/* wiener(ctx, x_bin, is_f64, shape, kernel_size, has_noise, noise) -> {:ok, binary of x's type}   (Filters.wiener/2, filters.ex:81-110) */
-static ERL_NIF_TERM nif_wiener(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  ErlNifBinary in, ob;
-  int is_f64, has_noise;
-  double noise;
-  int64_t shape[8], ks[8];
-  unsigned rank;
-  size_t n;
-  if (argc != 7 || !filter_args(env, argv, &c, &in, &is_f64, shape, ks, &rank, &n) || !enif_get_int(env, argv[5], &has_noise) ||
-      !get_number(env, argv[6], &noise))
-    return enif_make_badarg(env);
-  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
-  int rc = nxsig_wiener(c->ctx, in.data, is_f64, shape, (int32_t)rank, ks, has_noise, noise, ob.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&r[0], c, NXSIG_HOST, 8, (uint64_t)batch, (uint64_t)nb, 1);
+  if (!rc) rc = res_open(&r[1], c, NXSIG_HOST, 4, (uint64_t)batch, (uint64_t)nb, 1);
+  if (!rc) rc = res_open(&r[2], c, NXSIG_HOST, 4, (uint64_t)batch, (uint64_t)nb, 1);
+  if (!rc)
+    rc = nxsig_csd_f32(c->ctx, (const float*)x, (const float*)y, length, batch, length, (const float*)w.data, (int)(w.size / 4), hop, fft_length,
+                       detrend, scaling, fs, (float*)r[1].data, (float*)r[2].data, (nxsig_c64*)r[0].data, NXSIG_HOST);
+  if (rc) return res_fail(env, r, 3, rc);
+  return enif_make_tuple5(env, mk_atom(env, "ok"), res_term(env, &r[0]), res_term(env, &r[1]), res_term(env, &r[2]), enif_make_int(env, nb));
 }
 
 /* peak-finding shapes: rank 1 .. 8, no empty dimension, fewer than 2^32 elements (the library checks the rest) */
 static int peaks_shape(ErlNifEnv* env, ERL_NIF_TERM list, int64_t* shape, unsigned* rank, size_t* n) {
-  if (!get_i64_list(env, list, shape, 8, rank) || *rank < 1) return 0;
-  *n = 1;
-  for (unsigned d = 0; d < *rank; ++d)
-    if (shape[d] < 1 || !mul_size(n, (uint64_t)shape[d])) return 0;
-  return *n < ((size_t)1 << 32);
-}
-
-static ERL_NIF_TERM peaks_result(ErlNifEnv* env, int rc, ErlNifBinary* ob, uint32_t valid) {
-  if (rc) { enif_release_binary(ob); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, ob), enif_make_int64(env, (int64_t)valid));
+  return get_shape(env, list, shape, rank, n) && *n < ((size_t)1 << 32);
 }
 
 /* argrelextrema(ctx, x_bin, dtype, shape, axis, shifts, comparator) -> {:ok, s32 [size][rank] binary, valid}
    (PeakFinding.argrelextrema/3, lib/nx_signal/peak_finding.ex; dtype nxsig_dtype, comparator nxsig_comparator) */
 static ERL_NIF_TERM nif_argrelextrema(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
   int dtype, axis, comparator;
   int64_t shape[8], shifts;
   unsigned rank;
   size_t n;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !enif_get_int(env, argv[2], &dtype) ||
-      !peaks_shape(env, argv[3], shape, &rank, &n) || !enif_get_int(env, argv[4], &axis) || !enif_get_int64(env, argv[5], &shifts) ||
-      !enif_get_int(env, argv[6], &comparator) || dtype < 0 || dtype > 5)
-    return enif_make_badarg(env);
-  const size_t es = dtype == 1 || dtype == 3 || dtype == 5 ? 8 : 4;
-  if (in.size != n * es) return enif_make_badarg(env);
-  if (!out_bin(&ob, n, rank, 1, 4)) return mk_oom(env);
+  const void* in;
+  result_t o = {0};
   uint32_t valid = 0;
-  int rc = nxsig_argrelextrema(c->ctx, in.data, dtype, shape, (int32_t)rank, axis, shifts, comparator, (int32_t*)ob.data, &valid, NXSIG_HOST);
-  return peaks_result(env, rc, &ob, valid);
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[2], &dtype) || !peaks_shape(env, argv[3], shape, &rank, &n) ||
+      !enif_get_int(env, argv[4], &axis) || !enif_get_int64(env, argv[5], &shifts) || !enif_get_int(env, argv[6], &comparator) || dtype < 0 ||
+      dtype > 5 || !get_rows(env, argv[1], c, NXSIG_HOST, dtype == 1 || dtype == 3 || dtype == 5 ? 8 : 4, (int64_t)n, 1, 1, &in))
+    return enif_make_badarg(env);
+  int rc = res_open(&o, c, NXSIG_HOST, 4, n, rank, 1);
+  if (!rc) rc = nxsig_argrelextrema(c->ctx, in, dtype, shape, (int32_t)rank, axis, shifts, comparator, (int32_t*)o.data, &valid, NXSIG_HOST);
+  return res_ok2(env, &o, rc, (int64_t)valid);
 }
 
 /* nonzero(ctx, mask_bin, shape) -> {:ok, s32 [size][rank] binary, valid}   (the compaction of argrelextrema/3 for a custom comparator's
    u8 mask) */
 static ERL_NIF_TERM nif_nonzero(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
   int64_t shape[8];
   unsigned rank;
   size_t n;
-  if (argc != 3 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &in) || !peaks_shape(env, argv[2], shape, &rank, &n) ||
-      in.size != n)
-    return enif_make_badarg(env);
-  if (!out_bin(&ob, n, rank, 1, 4)) return mk_oom(env);
+  const void* in;
+  result_t o = {0};
   uint32_t valid = 0;
-  int rc = nxsig_nonzero(c->ctx, in.data, shape, (int32_t)rank, (int32_t*)ob.data, &valid, NXSIG_HOST);
-  return peaks_result(env, rc, &ob, valid);
+  if (argc != 3 || !get_ctx(env, argv[0], &c) || !peaks_shape(env, argv[2], shape, &rank, &n) ||
+      !get_rows(env, argv[1], c, NXSIG_HOST, 1, (int64_t)n, 1, 1, &in))
+    return enif_make_badarg(env);
+  int rc = res_open(&o, c, NXSIG_HOST, 4, n, rank, 1);
+  if (!rc) rc = nxsig_nonzero(c->ctx, (const uint8_t*)in, shape, (int32_t)rank, (int32_t*)o.data, &valid, NXSIG_HOST);
+  return res_ok2(env, &o, rc, (int64_t)valid);
 }
 
 /* NxSignal.Waveforms (lib/nx_signal/waveforms.ex): t_bin holds f32 elements, or f64 when is_f64; results are binaries of t's type */
@@ -970,187 +849,177 @@ static int wave_args(ErlNifEnv* env, const ERL_NIF_TERM argv[], ctx_res_t** c, E
   return in->size % es == 0;
 }
 
-static ERL_NIF_TERM wave_result(ErlNifEnv* env, int rc, ErlNifBinary* ob) {
-  if (rc) { enif_release_binary(ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, ob));
-}
-
 /* sawtooth(ctx, t_bin, is_f64, width) -> {:ok, binary}   (Waveforms.sawtooth/2, waveforms.ex:29-54) */
 static ERL_NIF_TERM nif_sawtooth(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
+  ErlNifBinary in;
   int is_f64;
   size_t n;
   double width;
+  result_t o = {0};
   if (argc != 4 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !get_number(env, argv[3], &width)) return enif_make_badarg(env);
-  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
-  return wave_result(env, nxsig_sawtooth(c->ctx, in.data, is_f64, (int64_t)n, width, ob.data, NXSIG_HOST), &ob);
+  int rc = res_open(&o, c, NXSIG_HOST, is_f64 ? 8 : 4, n, 1, 1);
+  if (!rc) rc = nxsig_sawtooth(c->ctx, in.data, is_f64, (int64_t)n, width, o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* square(ctx, t_bin, is_f64, duty, duty_bin) -> {:ok, s32 binary}   (Waveforms.square/2, waveforms.ex:96-104; a duty_bin of t's size
    replaces the number, an empty one means the number) */
 static ERL_NIF_TERM nif_square(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, duty, ob;
+  ErlNifBinary in, duty;
   int is_f64;
   size_t n;
   double d;
+  result_t o = {0};
   if (argc != 5 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !get_number(env, argv[3], &d) || !enif_inspect_binary(env, argv[4], &duty) ||
       (duty.size != 0 && duty.size != in.size))
     return enif_make_badarg(env);
-  if (!out_bin(&ob, n, 1, 1, 4)) return mk_oom(env);
-  return wave_result(env, nxsig_square(c->ctx, in.data, is_f64, (int64_t)n, d, duty.size ? duty.data : NULL, (int32_t*)ob.data, NXSIG_HOST), &ob);
+  int rc = res_open(&o, c, NXSIG_HOST, 4, n, 1, 1);
+  if (!rc) rc = nxsig_square(c->ctx, in.data, is_f64, (int64_t)n, d, duty.size ? duty.data : NULL, (int32_t*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* gaussian_pulse(ctx, t_bin, is_f64, center_frequency, bandwidth, bandwidth_reference_level) -> {:ok, envelope, in_phase, quadrature}
    (Waveforms.gaussian_pulse/2, waveforms.ex:161-198) */
 static ERL_NIF_TERM nif_gaussian_pulse(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, b0, b1, b2;
+  ErlNifBinary in;
   int is_f64;
   size_t n;
   double fc, bw, bwr;
+  result_t r[3] = {{0}};   /* envelope, in_phase, quadrature */
   if (argc != 6 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !get_number(env, argv[3], &fc) || !get_number(env, argv[4], &bw) ||
       !get_number(env, argv[5], &bwr))
     return enif_make_badarg(env);
-  const size_t es = is_f64 ? 8 : 4;
-  if (!out_bin(&b0, n, 1, 1, es)) return mk_oom(env);
-  if (!out_bin(&b1, n, 1, 1, es)) { enif_release_binary(&b0); return mk_oom(env); }
-  if (!out_bin(&b2, n, 1, 1, es)) { enif_release_binary(&b0); enif_release_binary(&b1); return mk_oom(env); }
-  int rc = nxsig_gaussian_pulse(c->ctx, in.data, is_f64, (int64_t)n, fc, bw, bwr, b0.data, b1.data, b2.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&b0); enif_release_binary(&b1); enif_release_binary(&b2); return mk_error(env, rc); }
-  return enif_make_tuple4(env, mk_atom(env, "ok"), enif_make_binary(env, &b0), enif_make_binary(env, &b1), enif_make_binary(env, &b2));
+  int rc = 0;
+  for (int i = 0; i < 3 && !rc; ++i) rc = res_open(&r[i], c, NXSIG_HOST, is_f64 ? 8 : 4, n, 1, 1);
+  if (!rc) rc = nxsig_gaussian_pulse(c->ctx, in.data, is_f64, (int64_t)n, fc, bw, bwr, r[0].data, r[1].data, r[2].data, NXSIG_HOST);
+  if (rc) return res_fail(env, r, 3, rc);
+  return enif_make_tuple4(env, mk_atom(env, "ok"), res_term(env, &r[0]), res_term(env, &r[1]), res_term(env, &r[2]));
 }
 
 /* chirp(ctx, t_bin, is_f64, {f0, t1, f1}, method, vertex_zero, phi) -> {:ok, binary}   (Waveforms.chirp/5, waveforms.ex:249-300;
    method nxsig_chirp_method) */
 static ERL_NIF_TERM nif_chirp(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, ob;
+  ErlNifBinary in;
   int is_f64, method, vertex_zero, arity;
   size_t n;
   const ERL_NIF_TERM* e;
   double f0, t1, f1, phi;
+  result_t o = {0};
   if (argc != 7 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !enif_get_tuple(env, argv[3], &arity, &e) || arity != 3 ||
       !get_number(env, e[0], &f0) || !get_number(env, e[1], &t1) || !get_number(env, e[2], &f1) || !enif_get_int(env, argv[4], &method) ||
       !enif_get_int(env, argv[5], &vertex_zero) || !get_number(env, argv[6], &phi))
     return enif_make_badarg(env);
-  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
-  return wave_result(env, nxsig_chirp(c->ctx, in.data, is_f64, (int64_t)n, f0, t1, f1, method, vertex_zero, phi, ob.data, NXSIG_HOST), &ob);
+  int rc = res_open(&o, c, NXSIG_HOST, is_f64 ? 8 : 4, n, 1, 1);
+  if (!rc) rc = nxsig_chirp(c->ctx, in.data, is_f64, (int64_t)n, f0, t1, f1, method, vertex_zero, phi, o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* polynomial_sweep(ctx, t_bin, is_f64, coefs_f64_bin, phi, phi_degrees) -> {:ok, binary}   (Waveforms.polynomial_sweep/3,
    waveforms.ex:343-361) */
 static ERL_NIF_TERM nif_polynomial_sweep(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary in, cf, ob;
+  ErlNifBinary in, cf;
   int is_f64, degrees;
   size_t n;
   double phi, coefs[NXSIG_SWEEP_MAX_COEFS];
+  result_t o = {0};
   if (argc != 6 || !wave_args(env, argv, &c, &in, &is_f64, &n) || !enif_inspect_binary(env, argv[3], &cf) || cf.size % 8 != 0 ||
       !get_number(env, argv[4], &phi) || !enif_get_int(env, argv[5], &degrees))
     return enif_make_badarg(env);
   const size_t nc = cf.size / 8;
   if (nc <= NXSIG_SWEEP_MAX_COEFS) memcpy(coefs, cf.data, cf.size);   /* a sub-binary need not be 8-byte aligned */
-  if (!out_bin(&ob, n, 1, 1, is_f64 ? 8 : 4)) return mk_oom(env);
-  return wave_result(env, nxsig_polynomial_sweep(c->ctx, in.data, is_f64, (int64_t)n, coefs, nc > NXSIG_SWEEP_MAX_COEFS ? -1 : (int32_t)nc, phi,
-                                                 degrees, ob.data, NXSIG_HOST), &ob);
+  int rc = res_open(&o, c, NXSIG_HOST, is_f64 ? 8 : 4, n, 1, 1);
+  if (!rc)
+    rc = nxsig_polynomial_sweep(c->ctx, in.data, is_f64, (int64_t)n, coefs, nc > NXSIG_SWEEP_MAX_COEFS ? -1 : (int32_t)nc, phi, degrees, o.data,
+                                NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* unit_impulse(ctx, dtype, shape, index) -> {:ok, binary}   (Waveforms.unit_impulse/2, waveforms.ex:406-437; dtype nxsig_dtype, index
    one entry per axis) */
 static ERL_NIF_TERM nif_unit_impulse(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary ob;
   int dtype;
   int64_t shape[8], index[8];
   unsigned rank, r2;
   size_t n = 1;
+  result_t o = {0};
   if (argc != 4 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[1], &dtype) || dtype < 0 || dtype > 5 ||
       !get_i64_list(env, argv[2], shape, 8, &rank) || !get_i64_list(env, argv[3], index, 8, &r2) || r2 != rank)
     return enif_make_badarg(env);
   for (unsigned d = 0; d < rank; ++d)
     if (shape[d] < 0 || !mul_size(&n, (uint64_t)shape[d])) return enif_make_badarg(env);
-  if (!out_bin(&ob, n, 1, 1, dtype == 1 || dtype == 3 || dtype == 5 ? 8 : 4)) return mk_oom(env);
-  return wave_result(env, nxsig_unit_impulse(c->ctx, dtype, shape, (int32_t)rank, index, ob.data, NXSIG_HOST), &ob);
+  int rc = res_open(&o, c, NXSIG_HOST, dtype == 1 || dtype == 3 || dtype == 5 ? 8 : 4, n, 1, 1);
+  if (!rc) rc = nxsig_unit_impulse(c->ctx, dtype, shape, (int32_t)rank, index, o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* stft_to_mel(ctx, z_bin, rows, fft_length, mel_bins, filters_bin) -> {:ok, f32[rows][mel_bins]}   (lib/nx_signal.ex:486-513) */
 static ERL_NIF_TERM nif_stft_to_mel(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary z, f, ob;
   ErlNifSInt64 rows;
   int k, bins;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &z) || !enif_get_int64(env, argv[2], &rows) ||
-      !enif_get_int(env, argv[3], &k) || !enif_get_int(env, argv[4], &bins) || !enif_inspect_binary(env, argv[5], &f))
+  const void *z, *f;
+  result_t o = {0};
+  if (argc != 6 || !get_ctx(env, argv[0], &c) || !enif_get_int64(env, argv[2], &rows) || !enif_get_int(env, argv[3], &k) ||
+      !enif_get_int(env, argv[4], &bins) || !get_rows(env, argv[1], c, NXSIG_HOST, 8, rows, k, 1, &z) ||
+      !get_rows(env, argv[5], c, NXSIG_HOST, 4, bins, k, 1, &f))
     return enif_make_badarg(env);
-  if (rows < 1 || k < 1 || bins < 1 || z.size % 8 || z.size / 8 / (size_t)rows != (size_t)k || z.size / 8 % (size_t)rows ||
-      f.size % 4 || f.size / 4 / (size_t)bins != (size_t)k || f.size / 4 % (size_t)bins)
-    return enif_make_badarg(env);
-  if (!out_bin(&ob, (uint64_t)rows, (uint64_t)bins, 1, 4)) return mk_oom(env);
-  int rc = nxsig_stft_to_mel(c->ctx, (const nxsig_c64*)z.data, rows, k, bins, (const float*)f.data, (float*)ob.data, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  int rc = res_open(&o, c, NXSIG_HOST, 4, (uint64_t)rows, (uint64_t)bins, 1);
+  if (!rc) rc = nxsig_stft_to_mel(c->ctx, (const nxsig_c64*)z, rows, k, bins, (const float*)f, (float*)o.data, NXSIG_HOST);
+  return res_ok(env, &o, rc);
 }
 
 /* stft_mel(ctx, x_bin, length, batch, window_bin, params, mel_bins, filters_bin) -> {:ok, f32[batch][M][mel_bins], M}  (fused) */
 static ERL_NIF_TERM nif_stft_mel(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary x, w, f, ob;
-  ErlNifSInt64 length;
-  int batch, bins;
-  nxsig_stft_params p;
-  if (argc != 8 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_get_int(env, argv[6], &bins) || !enif_inspect_binary(env, argv[7], &f))
+  frames_args_t a;
+  int bins;
+  const void *x, *f;
+  result_t o = {0};
+  if (argc != 8 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, 0, 0, &a) || !enif_get_int(env, argv[6], &bins) ||
+      !get_rows(env, argv[1], c, NXSIG_HOST, 4, a.batch, a.len, 1, &x) || !get_rows(env, argv[7], c, NXSIG_HOST, 4, bins, a.p.fft_length, 1, &f))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || bins < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length ||
-      w.size != (size_t)p.frame_length * 4 || f.size % 4 || f.size / 4 / (size_t)bins != (size_t)p.fft_length || f.size / 4 % (size_t)bins)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)m, (uint64_t)bins, 4)) return mk_oom(env);
-  int rc = nxsig_stft_mel_f32(c->ctx, (const float*)x.data, length, batch, length, (const float*)w.data, &p, bins, (const float*)f.data,
-                              (float*)ob.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &ob), enif_make_int64(env, m));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&o, c, NXSIG_HOST, 4, (uint64_t)a.batch, (uint64_t)a.out, (uint64_t)bins);
+  if (!rc)
+    rc = nxsig_stft_mel_f32(c->ctx, (const float*)x, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, bins, (const float*)f, (float*)o.data,
+                            NULL, NXSIG_HOST);
+  return res_ok2(env, &o, rc, a.out);
 }
 
 /* stft_magnitude(ctx, x_bin, length, batch, window_bin, params, kind) -> {:ok, f32[batch][M][fft_length / 2], M}
  * (fused |s| / |s|^2 / dBFS spectrogram of guides/spectrogram.livemd:76-92; kind 0 abs, 1 power, 2 dbfs) */
 static ERL_NIF_TERM nif_stft_magnitude(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  ErlNifBinary x, w, ob;
-  ErlNifSInt64 length;
-  int batch, kind;
-  nxsig_stft_params p;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_get_int(env, argv[6], &kind))
+  frames_args_t a;
+  int kind;
+  const void* x;
+  result_t o = {0};
+  if (argc != 7 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, 0, 0, &a) || !enif_get_int(env, argv[6], &kind) ||
+      a.p.fft_length < 2 || !get_rows(env, argv[1], c, NXSIG_HOST, 4, a.batch, a.len, 1, &x))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length || w.size != (size_t)p.frame_length * 4 ||
-      p.fft_length < 2)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)m, (uint64_t)(p.fft_length / 2), 4)) return mk_oom(env);
-  int rc = nxsig_stft_magnitude_f32(c->ctx, (const float*)x.data, length, batch, length, (const float*)w.data, &p, kind, (float*)ob.data, NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &ob), enif_make_int64(env, m));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&o, c, NXSIG_HOST, 4, (uint64_t)a.batch, (uint64_t)a.out, (uint64_t)(a.p.fft_length / 2));
+  if (!rc)
+    rc = nxsig_stft_magnitude_f32(c->ctx, (const float*)x, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, kind, (float*)o.data, NULL,
+                                  NXSIG_HOST);
+  return res_ok2(env, &o, rc, a.out);
 }
 
-/* ------------------------------------------------------------------------------------------------ device-resident tensors
- * keep stft -> edit -> istft chains in HBM (guides/filtering.livemd:137-159).  Device calls are
- * asynchronous on the context's stream; from_device synchronises. */
+/* ------------------------------------------------------------------------------------------------ device-resident tensors */
 static ERL_NIF_TERM nif_to_device(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
   ErlNifBinary b;
+  result_t d = {0};
   if (argc != 2 || !get_ctx(env, argv[0], &c) || !enif_inspect_binary(env, argv[1], &b)) return enif_make_badarg(env);
-  void* d = NULL;
-  int rc = nxsig_alloc(c->ctx, b.size, &d);
-  if (rc) return mk_error(env, rc);
-  if ((rc = nxsig_upload(c->ctx, d, b.data, b.size))) { nxsig_free(c->ctx, d); return mk_error(env, rc); }
-  return mk_ok(env, make_buf(env, c, d, b.size));
+  int rc = res_open(&d, c, NXSIG_DEVICE, 1, b.size, 1, 1);
+  if (!rc) rc = nxsig_upload(c->ctx, d.data, b.data, b.size);
+  return res_ok(env, &d, rc);
 }
 
 static ERL_NIF_TERM nif_from_device(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
@@ -1171,59 +1040,22 @@ static ERL_NIF_TERM nif_buf_size(ErlNifEnv* env, int argc, const ERL_NIF_TERM ar
   return enif_make_int64(env, (ErlNifSInt64)b->bytes);
 }
 
-/* stft_dev(ctx, x_buf, length, batch, window_bin, params) -> {:ok, z_buf, num_frames}; stft_c64_dev: x_buf holds c64 samples */
-static ERL_NIF_TERM stft_dev_impl(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], size_t elem) {
-  ctx_res_t* c;
-  buf_res_t* x;
-  ErlNifBinary w;
-  ErlNifSInt64 length;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p))
-    return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x->owner != c || x->bytes / elem / (size_t)batch < (size_t)length || w.size != (size_t)p.frame_length * 4)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  size_t zbytes = 8;
-  if (!mul_size(&zbytes, (uint64_t)batch) || !mul_size(&zbytes, (uint64_t)m) || !mul_size(&zbytes, (uint64_t)p.fft_length)) return mk_oom(env);
-  void* z = NULL;
-  int rc = nxsig_alloc(c->ctx, zbytes, &z);
-  if (rc) return mk_error(env, rc);
-  rc = elem == 8 ? nxsig_stft_c64(c->ctx, (const nxsig_c64*)x->dptr, length, batch, length, (const float*)w.data, &p, (nxsig_c64*)z, NULL, NXSIG_DEVICE)
-                 : nxsig_stft_f32(c->ctx, (const float*)x->dptr, length, batch, length, (const float*)w.data, &p, (nxsig_c64*)z, NULL, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, z); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), make_buf(env, c, z, zbytes), enif_make_int64(env, m));
-}
-static ERL_NIF_TERM nif_stft_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_dev_impl(env, argc, argv, 4); }
-static ERL_NIF_TERM nif_stft_c64_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_dev_impl(env, argc, argv, 8); }
-
 /* stft_onesided_dev / stft_packed_dev(ctx, x_buf, length, batch, window_bin, params) -> {:ok, z_buf, num_frames}
  * c64[batch][M][fft_length / 2]: bins 0 .. fft_length/2 - 1; packed: the imaginary part of bin 0 carries Re X[fft_length / 2] */
 static ERL_NIF_TERM stft_half_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[], int packed) {
   ctx_res_t* c;
-  buf_res_t* x;
-  ErlNifBinary w;
-  ErlNifSInt64 length;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p))
+  frames_args_t a;
+  const void* x;
+  result_t z = {0};
+  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, 0, 0, &a) || a.p.fft_length < 2 ||
+      !get_rows(env, argv[1], c, NXSIG_DEVICE, 4, a.batch, a.len, 1, &x))
     return enif_make_badarg(env);
-  if (p.fft_length < 2 || batch < 1 || length < 1 || x->owner != c || x->bytes / 4 / (size_t)batch < (size_t)length || w.size != (size_t)p.frame_length * 4)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  size_t zbytes = 8;
-  if (!mul_size(&zbytes, (uint64_t)batch) || !mul_size(&zbytes, (uint64_t)m) || !mul_size(&zbytes, (uint64_t)(p.fft_length / 2))) return mk_oom(env);
-  void* z = NULL;
-  int rc = nxsig_alloc(c->ctx, zbytes, &z);
-  if (rc) return mk_error(env, rc);
-  rc = packed ? nxsig_stft_packed_f32(c->ctx, (const float*)x->dptr, length, batch, length, (const float*)w.data, &p, (nxsig_c64*)z, NULL, NXSIG_DEVICE)
-              : nxsig_stft_onesided_f32(c->ctx, (const float*)x->dptr, length, batch, length, (const float*)w.data, &p, (nxsig_c64*)z, NULL, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, z); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), make_buf(env, c, z, zbytes), enif_make_int64(env, m));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&z, c, NXSIG_DEVICE, 8, (uint64_t)a.batch, (uint64_t)a.out, (uint64_t)(a.p.fft_length / 2));
+  if (!rc)
+    rc = packed ? nxsig_stft_packed_f32(c->ctx, (const float*)x, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, (nxsig_c64*)z.data, NULL, NXSIG_DEVICE)
+                : nxsig_stft_onesided_f32(c->ctx, (const float*)x, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, (nxsig_c64*)z.data, NULL, NXSIG_DEVICE);
+  return res_ok2(env, &z, rc, a.out);
 }
 static ERL_NIF_TERM nif_stft_onesided_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_half_dev(env, argc, argv, 0); }
 static ERL_NIF_TERM nif_stft_packed_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) { return stft_half_dev(env, argc, argv, 1); }
@@ -1232,231 +1064,95 @@ static ERL_NIF_TERM nif_stft_packed_dev(ErlNifEnv* env, int argc, const ERL_NIF_
  * y REAL f32[batch][M * hop + frame_length - hop] */
 static ERL_NIF_TERM nif_istft_packed_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  buf_res_t* z;
-  ErlNifBinary w;
-  ErlNifSInt64 m;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p))
+  frames_args_t a;
+  const void* z;
+  result_t y = {0};
+  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_frames_args(env, argv + 2, 0, 1, &a) || a.p.fft_length < 2 ||
+      !get_rows(env, argv[1], c, NXSIG_DEVICE, 8, a.batch, a.len, a.p.fft_length / 2, &z))
     return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || p.fft_length < 2 || z->owner != c || w.size != (size_t)p.frame_length * 4 ||
-      z->bytes / 8 / (size_t)batch / (size_t)m < (size_t)(p.fft_length / 2))
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  size_t ybytes = 4;
-  if (!mul_size(&ybytes, (uint64_t)batch) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
-  void* y = NULL;
-  int rc = nxsig_alloc(c->ctx, ybytes, &y);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_istft_packed_f32(c->ctx, (const nxsig_c64*)z->dptr, m, batch, (const float*)w.data, &p, (float*)y, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
-  return mk_ok(env, make_buf(env, c, y, ybytes));
-}
-
-/* istft_dev(ctx, z_buf, num_frames, batch, window_bin, params) -> {:ok, y_buf} */
-static ERL_NIF_TERM nif_istft_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  buf_res_t* z;
-  ErlNifBinary w;
-  ErlNifSInt64 m;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p))
-    return enif_make_badarg(env);
-  /* the window binary is read by the library: its size must match (ADVICE r1: a short window was read out of bounds) */
-  if (batch < 1 || m < 1 || z->owner != c || w.size != (size_t)p.frame_length * 4 ||
-      z->bytes / 8 / (size_t)batch / (size_t)m < (size_t)p.fft_length)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  size_t ybytes = 8;
-  if (!mul_size(&ybytes, (uint64_t)batch) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
-  void* y = NULL;
-  int rc = nxsig_alloc(c->ctx, ybytes, &y);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_istft_c64(c->ctx, (const nxsig_c64*)z->dptr, m, batch, (const float*)w.data, &p, (nxsig_c64*)y, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
-  return mk_ok(env, make_buf(env, c, y, ybytes));
-}
-
-/* istft_filtered_dev(ctx, z_buf, num_frames, batch, window_bin, params, h_bin) -> {:ok, y_buf}   (z_buf is left untouched) */
-static ERL_NIF_TERM nif_istft_filtered_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  buf_res_t* z;
-  ErlNifBinary w, h;
-  ErlNifSInt64 m;
-  int batch;
-  nxsig_stft_params p;
-  if (argc != 7 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_inspect_binary(env, argv[6], &h))
-    return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || p.fft_length < 1 || z->owner != c || w.size != (size_t)p.frame_length * 4 ||
-      h.size != (size_t)p.fft_length * 8 || z->bytes / 8 / (size_t)batch / (size_t)m < (size_t)p.fft_length)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  size_t ybytes = 8;
-  if (!mul_size(&ybytes, (uint64_t)batch) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
-  void* y = NULL;
-  int rc = nxsig_alloc(c->ctx, ybytes, &y);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_istft_filtered_c64(c->ctx, (const nxsig_c64*)z->dptr, m, batch, (const float*)w.data, &p, (const nxsig_c64*)h.data,
-                                (nxsig_c64*)y, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
-  return mk_ok(env, make_buf(env, c, y, ybytes));
-}
-
-/* fir_dev(ctx, x_buf, length, batch, taps_bin, mode) -> {:ok, y_buf, out_length} */
-static ERL_NIF_TERM nif_fir_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
-  ctx_res_t* c;
-  buf_res_t* x;
-  ErlNifBinary h;
-  ErlNifSInt64 length;
-  int batch, mode;
-  if (argc != 6 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &h) || !enif_get_int(env, argv[5], &mode))
-    return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x->owner != c || x->bytes / 4 / (size_t)batch < (size_t)length || h.size < 4 || h.size % 4 ||
-      h.size / 4 > 0x7fffffff)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_conv_length(length, (int64_t)(h.size / 4), mode);
-  if (n < 0) return mk_error(env, (int)n);
-  size_t ybytes = 4;
-  if (!mul_size(&ybytes, (uint64_t)batch) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
-  void* y = NULL;
-  int rc = nxsig_alloc(c->ctx, ybytes, &y);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_fir_f32(c->ctx, (const float*)x->dptr, length, batch, length, (const float*)h.data, (int)(h.size / 4), mode, (float*)y, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), make_buf(env, c, y, ybytes), enif_make_int64(env, n));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&y, c, NXSIG_DEVICE, 4, (uint64_t)a.batch, (uint64_t)a.out, 1);
+  if (!rc) rc = nxsig_istft_packed_f32(c->ctx, (const nxsig_c64*)z, a.len, a.batch, (const float*)a.w.data, &a.p, (float*)y.data, NXSIG_DEVICE);
+  return res_ok(env, &y, rc);
 }
 
 /* spectrum_mul_dev(ctx, z_buf, rows, fft_length, h_bin) -> {:ok, z_buf}   (in place: Nx.multiply(z, hfft), guides/filtering.livemd:141) */
 static ERL_NIF_TERM nif_spectrum_mul_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  buf_res_t* z;
   ErlNifBinary h;
   ErlNifSInt64 rows;
   int k;
-  if (argc != 5 || !get_ctx(env, argv[0], &c) || !get_buf(env, argv[1], &z) || !enif_get_int64(env, argv[2], &rows) ||
-      !enif_get_int(env, argv[3], &k) || !enif_inspect_binary(env, argv[4], &h))
+  const void* z;
+  if (argc != 5 || !get_ctx(env, argv[0], &c) || !enif_get_int64(env, argv[2], &rows) || !enif_get_int(env, argv[3], &k) ||
+      !enif_inspect_binary(env, argv[4], &h) || !get_rows(env, argv[1], c, NXSIG_DEVICE, 8, rows, k, 1, &z) || h.size != (size_t)k * 8)
     return enif_make_badarg(env);
-  if (rows < 1 || k < 1 || z->owner != c || h.size != (size_t)k * 8 || z->bytes / 8 / (size_t)rows < (size_t)k) return enif_make_badarg(env);
-  int rc = nxsig_spectrum_mul_c64(c->ctx, (const nxsig_c64*)z->dptr, rows, k, (const nxsig_c64*)h.data, (nxsig_c64*)z->dptr, NXSIG_DEVICE);
+  int rc = nxsig_spectrum_mul_c64(c->ctx, (const nxsig_c64*)z, rows, k, (const nxsig_c64*)h.data, (nxsig_c64*)z, NXSIG_DEVICE);
   return rc ? mk_error(env, rc) : mk_ok(env, argv[1]);
 }
 
 /* ---- time-frequency masks (nxsig_spectrum_mask_c64 / nxsig_istft_masked_c64).  z and mask are BOTH binaries (host result: a binary)
  * or BOTH device buffers of this context (result: a new buffer; the call is asynchronous).  mask_kind: 0 real f32[K], 1 one-sided
- * real f32[K/2 + 1], 2 c64[K] per frame; z_rows / mask_rows are equal or one of them is 1 (that operand is broadcast). */
-typedef struct {
-  const void *z, *mask;
-  size_t zbytes, mbytes;
-  int dev;
-} mask_operands_t;
-static int get_mask_operands(ErlNifEnv* env, ctx_res_t* c, ERL_NIF_TERM zt, ERL_NIF_TERM mt, mask_operands_t* o) {
-  ErlNifBinary zb, mb;
-  buf_res_t *zr, *mr;
-  if (enif_inspect_binary(env, zt, &zb) && enif_inspect_binary(env, mt, &mb)) {
-    o->z = zb.data; o->zbytes = zb.size; o->mask = mb.data; o->mbytes = mb.size; o->dev = 0;
-    return 1;
-  }
-  if (get_buf(env, zt, &zr) && get_buf(env, mt, &mr) && zr->owner == c && mr->owner == c) {
-    o->z = zr->dptr; o->zbytes = zr->bytes; o->mask = mr->dptr; o->mbytes = mr->bytes; o->dev = 1;
-    return 1;
-  }
-  return 0;
-}
-/* the sizes the two operands must have (binaries: exactly; buffers: at least); *rows = rows of the result */
-static int mask_sizes_ok(const mask_operands_t* o, int z_rows, int mask_kind, int mask_rows, ErlNifSInt64 m, int k, int* rows) {
-  if (z_rows < 1 || mask_rows < 1 || m < 1 || k < 1 || mask_kind < 0 || mask_kind > 2) return 0;
+ * real f32[K/2 + 1], 2 c64[K] per frame; z_rows / mask_rows are equal or one of them is 1 (that operand is broadcast).
+ * Reads both operands (binaries: exactly the size the counts give; buffers: at least); *mem = where they live, *rows = rows of the result */
+static int get_masked(ErlNifEnv* env, ctx_res_t* c, ERL_NIF_TERM zt, int z_rows, ERL_NIF_TERM mt, int mask_kind, int mask_rows, int64_t m, int k,
+                      const void** z, const void** mask, int* mem, int* rows) {
+  if (mask_kind < 0 || mask_kind > 2 || (mask_kind == 1 && (k & 1))) return 0;
   if (z_rows != mask_rows && z_rows != 1 && mask_rows != 1) return 0;
-  if (mask_kind == 1 && (k & 1)) return 0;
-  size_t zneed = 8, mneed = mask_kind == 2 ? 8 : 4;
-  if (!mul_size(&zneed, (uint64_t)z_rows) || !mul_size(&zneed, (uint64_t)m) || !mul_size(&zneed, (uint64_t)k)) return 0;
-  if (!mul_size(&mneed, (uint64_t)mask_rows) || !mul_size(&mneed, (uint64_t)m) ||
-      !mul_size(&mneed, (uint64_t)(mask_kind == 1 ? k / 2 + 1 : k)))
-    return 0;
-  if (o->dev ? (o->zbytes < zneed || o->mbytes < mneed) : (o->zbytes != zneed || o->mbytes != mneed)) return 0;
+  *mem = term_mem(env, zt);
   *rows = z_rows > mask_rows ? z_rows : mask_rows;
-  return 1;
+  return get_rows(env, zt, c, *mem, 8, z_rows, m, k, z) &&
+         get_rows(env, mt, c, *mem, mask_kind == 2 ? 8 : 4, mask_rows, m, mask_kind == 1 ? k / 2 + 1 : k, mask);
 }
 
 /* spectrum_mask(ctx, z, z_rows, mask, mask_kind, mask_rows, num_frames, fft_length) -> {:ok, out}   (Nx.multiply(z, mask)) */
 static ERL_NIF_TERM nif_spectrum_mask(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  mask_operands_t o;
   ErlNifSInt64 m;
-  int z_rows, kind, mask_rows, k, rows;
-  if (argc != 8 || !get_ctx(env, argv[0], &c) || !get_mask_operands(env, c, argv[1], argv[3], &o) || !enif_get_int(env, argv[2], &z_rows) ||
-      !enif_get_int(env, argv[4], &kind) || !enif_get_int(env, argv[5], &mask_rows) || !enif_get_int64(env, argv[6], &m) ||
-      !enif_get_int(env, argv[7], &k))
+  int z_rows, kind, mask_rows, k, rows, mem;
+  const void *z, *mask;
+  result_t o = {0};
+  if (argc != 8 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[2], &z_rows) || !enif_get_int(env, argv[4], &kind) ||
+      !enif_get_int(env, argv[5], &mask_rows) || !enif_get_int64(env, argv[6], &m) || !enif_get_int(env, argv[7], &k) ||
+      !get_masked(env, c, argv[1], z_rows, argv[3], kind, mask_rows, m, k, &z, &mask, &mem, &rows))
     return enif_make_badarg(env);
-  if (!mask_sizes_ok(&o, z_rows, kind, mask_rows, m, k, &rows)) return enif_make_badarg(env);
-  if (!o.dev) {
-    ErlNifBinary ob;
-    if (!out_bin(&ob, (uint64_t)rows, (uint64_t)m, (uint64_t)k, 8)) return mk_oom(env);
-    int rc = nxsig_spectrum_mask_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, o.mask, kind, mask_rows, m, k, (nxsig_c64*)ob.data, NXSIG_HOST);
-    if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-    return mk_ok(env, enif_make_binary(env, &ob));
-  }
-  size_t obytes = 8;
-  if (!mul_size(&obytes, (uint64_t)rows) || !mul_size(&obytes, (uint64_t)m) || !mul_size(&obytes, (uint64_t)k)) return mk_oom(env);
-  void* out = NULL;
-  int rc = nxsig_alloc(c->ctx, obytes, &out);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_spectrum_mask_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, o.mask, kind, mask_rows, m, k, (nxsig_c64*)out, NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, out); return mk_error(env, rc); }
-  return mk_ok(env, make_buf(env, c, out, obytes));
+  int rc = res_open(&o, c, mem, 8, (uint64_t)rows, (uint64_t)m, (uint64_t)k);
+  if (!rc) rc = nxsig_spectrum_mask_c64(c->ctx, (const nxsig_c64*)z, z_rows, mask, kind, mask_rows, m, k, (nxsig_c64*)o.data, mem);
+  return res_ok(env, &o, rc);
 }
 
 /* istft_masked(ctx, z, z_rows, num_frames, window_bin, params, mask, mask_kind, mask_rows) -> {:ok, y}
  * NxSignal.istft(Nx.multiply(z, mask), window, opts) in one library call; z and mask are left untouched */
 static ERL_NIF_TERM nif_istft_masked(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   ctx_res_t* c;
-  mask_operands_t o;
   ErlNifBinary w;
   ErlNifSInt64 m;
-  int z_rows, kind, mask_rows, rows;
+  int z_rows, kind, mask_rows, rows, mem;
   nxsig_stft_params p;
-  if (argc != 9 || !get_ctx(env, argv[0], &c) || !get_mask_operands(env, c, argv[1], argv[6], &o) || !enif_get_int(env, argv[2], &z_rows) ||
-      !enif_get_int64(env, argv[3], &m) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_get_int(env, argv[7], &kind) || !enif_get_int(env, argv[8], &mask_rows))
+  const void *z, *mask;
+  result_t y = {0};
+  if (argc != 9 || !get_ctx(env, argv[0], &c) || !enif_get_int(env, argv[2], &z_rows) || !enif_get_int64(env, argv[3], &m) ||
+      !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) || !enif_get_int(env, argv[7], &kind) ||
+      !enif_get_int(env, argv[8], &mask_rows) || w.size != (size_t)p.frame_length * 4 ||
+      !get_masked(env, c, argv[1], z_rows, argv[6], kind, mask_rows, m, p.fft_length, &z, &mask, &mem, &rows))
     return enif_make_badarg(env);
-  if (!mask_sizes_ok(&o, z_rows, kind, mask_rows, m, p.fft_length, &rows) || w.size != (size_t)p.frame_length * 4) return enif_make_badarg(env);
   int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
   if (n < 0) return mk_error(env, (int)n);
-  if (!o.dev) {
-    ErlNifBinary yb;
-    if (!out_bin(&yb, (uint64_t)rows, (uint64_t)n, 1, 8)) return mk_oom(env);
-    int rc = nxsig_istft_masked_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, m, (const float*)w.data, &p, o.mask, kind, mask_rows,
-                                    (nxsig_c64*)yb.data, NXSIG_HOST);
-    if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-    return mk_ok(env, enif_make_binary(env, &yb));
-  }
-  size_t ybytes = 8;
-  if (!mul_size(&ybytes, (uint64_t)rows) || !mul_size(&ybytes, (uint64_t)n)) return mk_oom(env);
-  void* y = NULL;
-  int rc = nxsig_alloc(c->ctx, ybytes, &y);
-  if (rc) return mk_error(env, rc);
-  rc = nxsig_istft_masked_c64(c->ctx, (const nxsig_c64*)o.z, z_rows, m, (const float*)w.data, &p, o.mask, kind, mask_rows, (nxsig_c64*)y,
-                              NXSIG_DEVICE);
-  if (rc) { nxsig_free(c->ctx, y); return mk_error(env, rc); }
-  return mk_ok(env, make_buf(env, c, y, ybytes));
+  int rc = res_open(&y, c, mem, 8, (uint64_t)rows, (uint64_t)n, 1);
+  if (!rc)
+    rc = nxsig_istft_masked_c64(c->ctx, (const nxsig_c64*)z, z_rows, m, (const float*)w.data, &p, mask, kind, mask_rows, (nxsig_c64*)y.data, mem);
+  return res_ok(env, &y, rc);
 }
 
 /* ------------------------------------------------------------------------------------------------ multi-GPU groups
  * One BEAM process drives every GPU of the node: a LOCAL group (ncclCommInitAll).  The vectorized (multichannel) axis of the
  * reference (lib/nx_signal.ex:358-363) is what `axis = 0` shards. */
+#define NXSIG_MAX_MEMBERS 64
+
 /* group_create([device_id]) -> {:ok, group} */
 static ERL_NIF_TERM nif_group_create(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   unsigned len;
-  int32_t devs[64];
-  if (argc != 1 || !enif_get_list_length(env, argv[0], &len) || len < 1 || len > 64) return enif_make_badarg(env);
+  int32_t devs[NXSIG_MAX_MEMBERS];
+  if (argc != 1 || !enif_get_list_length(env, argv[0], &len) || len < 1 || len > NXSIG_MAX_MEMBERS) return enif_make_badarg(env);
   ERL_NIF_TERM head, tail = argv[0];
   for (unsigned i = 0; i < len; ++i) {
     int d;
@@ -1481,130 +1177,111 @@ static ERL_NIF_TERM nif_group_info(ErlNifEnv* env, int argc, const ERL_NIF_TERM 
                           enif_make_int(env, nxsig_group_has_rccl(g->grp)));
 }
 
+/* The sharded calls over HOST tensors: the whole tensor goes in as element 0 of the per-member pointer array, the whole result comes
+ * back the same way (include/nxsig.h, mem == NXSIG_HOST); the library splits and assembles. */
 /* stft_sharded(group, x_bin, length, batch, window_bin, params, axis, gather) -> {:ok, z_bin, num_frames} */
 static ERL_NIF_TERM nif_stft_sharded(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary x, w, zb;
-  ErlNifSInt64 length;
-  int batch, axis, gather;
-  nxsig_stft_params p;
-  if (argc != 8 || !get_grp(env, argv[0], &g) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_get_int(env, argv[6], &axis) || !enif_get_int(env, argv[7], &gather))
+  frames_args_t a;
+  int axis, gather;
+  const void* x;
+  result_t z = {0};
+  if (argc != 8 || !get_grp(env, argv[0], &g) || !get_frames_args(env, argv + 2, 0, 0, &a) || !enif_get_int(env, argv[6], &axis) ||
+      !enif_get_int(env, argv[7], &gather) || !get_rows(env, argv[1], NULL, NXSIG_HOST, 4, a.batch, a.len, 1, &x))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length || w.size != (size_t)p.frame_length * 4)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&zb, (uint64_t)batch, (uint64_t)m, (uint64_t)p.fft_length, 8)) return mk_oom(env);
-  const float* xs[64] = {(const float*)x.data};
-  nxsig_c64* zs[64] = {(nxsig_c64*)zb.data};
-  int rc = nxsig_stft_sharded_f32(g->grp, xs, length, batch, length, (const float*)w.data, &p, axis, gather, zs, NXSIG_HOST);
-  if (rc) { enif_release_binary(&zb); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &zb), enif_make_int64(env, m));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&z, NULL, NXSIG_HOST, 8, (uint64_t)a.batch, (uint64_t)a.out, (uint64_t)a.p.fft_length);
+  const float* xs[NXSIG_MAX_MEMBERS] = {(const float*)x};
+  nxsig_c64* zs[NXSIG_MAX_MEMBERS] = {(nxsig_c64*)z.data};
+  if (!rc) rc = nxsig_stft_sharded_f32(g->grp, xs, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, axis, gather, zs, NXSIG_HOST);
+  return res_ok2(env, &z, rc, a.out);
 }
 
 /* istft_sharded(group, z_bin, num_frames, batch, window_bin, params, axis, gather) -> {:ok, y_bin} */
 static ERL_NIF_TERM nif_istft_sharded(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary z, w, yb;
-  ErlNifSInt64 m;
-  int batch, axis, gather;
-  nxsig_stft_params p;
-  if (argc != 8 || !get_grp(env, argv[0], &g) || !enif_inspect_binary(env, argv[1], &z) || !enif_get_int64(env, argv[2], &m) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_get_int(env, argv[6], &axis) || !enif_get_int(env, argv[7], &gather))
+  frames_args_t a;
+  int axis, gather;
+  const void* z;
+  result_t y = {0};
+  if (argc != 8 || !get_grp(env, argv[0], &g) || !get_frames_args(env, argv + 2, 0, 1, &a) || !enif_get_int(env, argv[6], &axis) ||
+      !enif_get_int(env, argv[7], &gather) || !get_rows(env, argv[1], NULL, NXSIG_HOST, 8, a.batch, a.len, a.p.fft_length, &z))
     return enif_make_badarg(env);
-  if (batch < 1 || m < 1 || p.fft_length < 1 || z.size % 8 || z.size / 8 / (size_t)batch / (size_t)m != (size_t)p.fft_length ||
-      z.size / 8 % ((size_t)batch * (size_t)m) || w.size != (size_t)p.frame_length * 4)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 8)) return mk_oom(env);
-  const nxsig_c64* zs[64] = {(const nxsig_c64*)z.data};
-  nxsig_c64* ys[64] = {(nxsig_c64*)yb.data};
-  int rc = nxsig_istft_sharded_c64(g->grp, zs, m, batch, (const float*)w.data, &p, axis, gather, ys, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&y, NULL, NXSIG_HOST, 8, (uint64_t)a.batch, (uint64_t)a.out, 1);
+  const nxsig_c64* zs[NXSIG_MAX_MEMBERS] = {(const nxsig_c64*)z};
+  nxsig_c64* ys[NXSIG_MAX_MEMBERS] = {(nxsig_c64*)y.data};
+  if (!rc) rc = nxsig_istft_sharded_c64(g->grp, zs, a.len, a.batch, (const float*)a.w.data, &a.p, axis, gather, ys, NXSIG_HOST);
+  return res_ok(env, &y, rc);
 }
 
 /* stft_mel_sharded(group, x_bin, length, batch, window_bin, params, mel_bins, filters_bin, axis) -> {:ok, f32[batch][M][mel_bins], M}
  * (the sharded log-mel: the members' maxima are all-reduced between the two passes) */
 static ERL_NIF_TERM nif_stft_mel_sharded(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary x, w, f, ob;
-  ErlNifSInt64 length;
-  int batch, bins, axis;
-  nxsig_stft_params p;
-  if (argc != 9 || !get_grp(env, argv[0], &g) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) ||
-      !enif_get_int(env, argv[6], &bins) || !enif_inspect_binary(env, argv[7], &f) || !enif_get_int(env, argv[8], &axis))
+  frames_args_t a;
+  int bins, axis;
+  const void *x, *f;
+  result_t o = {0};
+  if (argc != 9 || !get_grp(env, argv[0], &g) || !get_frames_args(env, argv + 2, 0, 0, &a) || !enif_get_int(env, argv[6], &bins) ||
+      !enif_get_int(env, argv[8], &axis) || a.p.fft_length < 2 || !get_rows(env, argv[1], NULL, NXSIG_HOST, 4, a.batch, a.len, 1, &x) ||
+      !get_rows(env, argv[7], NULL, NXSIG_HOST, 4, bins, a.p.fft_length, 1, &f))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || bins < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length ||
-      w.size != (size_t)p.frame_length * 4 || p.fft_length < 2 || f.size % 4 || f.size / 4 / (size_t)bins != (size_t)p.fft_length ||
-      f.size / 4 % (size_t)bins)
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)m, (uint64_t)bins, 4)) return mk_oom(env);
-  const float* xs[64] = {(const float*)x.data};
-  float* os[64] = {(float*)ob.data};
-  int rc = nxsig_stft_mel_sharded_f32(g->grp, xs, length, batch, length, (const float*)w.data, &p, bins, (const float*)f.data, axis, os,
-                                      NULL, NXSIG_HOST);
-  if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), enif_make_binary(env, &ob), enif_make_int64(env, m));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&o, NULL, NXSIG_HOST, 4, (uint64_t)a.batch, (uint64_t)a.out, (uint64_t)bins);
+  const float* xs[NXSIG_MAX_MEMBERS] = {(const float*)x};
+  float* os[NXSIG_MAX_MEMBERS] = {(float*)o.data};
+  if (!rc)
+    rc = nxsig_stft_mel_sharded_f32(g->grp, xs, a.len, a.batch, a.len, (const float*)a.w.data, &a.p, bins, (const float*)f, axis, os, NULL, NXSIG_HOST);
+  return res_ok2(env, &o, rc, a.out);
 }
 
 /* fir_sharded(group, x_bin, length, batch, taps_bin, mode, axis, gather) -> {:ok, y_bin} */
 static ERL_NIF_TERM nif_fir_sharded(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary x, h, yb;
-  ErlNifSInt64 length;
-  int batch, mode, axis, gather;
-  if (argc != 8 || !get_grp(env, argv[0], &g) || !enif_inspect_binary(env, argv[1], &x) || !enif_get_int64(env, argv[2], &length) ||
-      !enif_get_int(env, argv[3], &batch) || !enif_inspect_binary(env, argv[4], &h) || !enif_get_int(env, argv[5], &mode) ||
-      !enif_get_int(env, argv[6], &axis) || !enif_get_int(env, argv[7], &gather))
+  fir_args_t a;
+  int axis, gather;
+  const void* x;
+  result_t y = {0};
+  if (argc != 8 || !get_grp(env, argv[0], &g) || !get_fir_args(env, argv + 2, 4, &a) || !enif_get_int(env, argv[6], &axis) ||
+      !enif_get_int(env, argv[7], &gather) || !get_rows(env, argv[1], NULL, NXSIG_HOST, 4, a.batch, a.len, 1, &x))
     return enif_make_badarg(env);
-  if (batch < 1 || length < 1 || x.size % 4 || x.size / 4 / (size_t)batch != (size_t)length || h.size < 4 || h.size % 4 ||
-      h.size / 4 > 0x7fffffff)
-    return enif_make_badarg(env);
-  int64_t n = nxsig_conv_length(length, (int64_t)(h.size / 4), mode);
-  if (n < 0) return mk_error(env, (int)n);
-  if (!out_bin(&yb, (uint64_t)batch, (uint64_t)n, 1, 4)) return mk_oom(env);
-  const float* xs[64] = {(const float*)x.data};
-  float* ys[64] = {(float*)yb.data};
-  int rc = nxsig_fir_sharded_f32(g->grp, xs, length, batch, length, (const float*)h.data, (int)(h.size / 4), mode, axis, gather, ys, NXSIG_HOST);
-  if (rc) { enif_release_binary(&yb); return mk_error(env, rc); }
-  return mk_ok(env, enif_make_binary(env, &yb));
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  int rc = res_open(&y, NULL, NXSIG_HOST, 4, (uint64_t)a.batch, (uint64_t)a.out, 1);
+  const float* xs[NXSIG_MAX_MEMBERS] = {(const float*)x};
+  float* ys[NXSIG_MAX_MEMBERS] = {(float*)y.data};
+  if (!rc) rc = nxsig_fir_sharded_f32(g->grp, xs, a.len, a.batch, a.len, (const float*)a.h.data, a.taps, a.mode, axis, gather, ys, NXSIG_HOST);
+  return res_ok(env, &y, rc);
 }
 
 /* ------------------------------------------------------------------------------------------------ device-resident shards
  * NxSignalAMD.Sharded.Tensor: one dense device buffer per group member, the payload never visits the host between
  * group_scatter (Sharded.to_device) and group_gather (Sharded.from_device).  The reference axis being sharded is Nx's
  * vectorized axis (lib/nx_signal.ex:358-363) or, for one long stream, the frame / sample axis. */
-#define NXSIG_MAX_MEMBERS 64
 
 /* shard_range(kind, a, b, c, world, rank) -> {x0, x1, y0, y1}
  *   kind 0: nxsig_shard_range(total = a)            -> {begin, end, 0, 0}
  *   kind 1: nxsig_shard_frames(num_frames = a, frame_length = b, hop = c)   -> {m0, m1, s0, s1}
  *   kind 2: nxsig_shard_istft(num_frames = a, frame_length = b, hop = c)    -> {f0, f1, n0, n1}
  *   kind 3: nxsig_shard_fir(length = a, num_taps = b, mode = c)             -> {n0, n1, s0, s1} */
+enum { SHARD_RANGE = 0, SHARD_FRAMES = 1, SHARD_ISTFT = 2, SHARD_FIR = 3 };
+static int shard_plan(int kind, int64_t a, int32_t b, int32_t c, int world, int rank, int64_t r[4]) {
+  switch (kind) {
+    case SHARD_RANGE: return nxsig_shard_range(a, world, rank, &r[0], &r[1]);
+    case SHARD_FRAMES: return nxsig_shard_frames(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]);
+    case SHARD_ISTFT: return nxsig_shard_istft(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]);
+    default: return nxsig_shard_fir(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]);
+  }
+}
 static ERL_NIF_TERM nif_shard_range(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   int kind, world, rank;
   ErlNifSInt64 a, b, c;
   if (argc != 6 || !enif_get_int(env, argv[0], &kind) || !enif_get_int64(env, argv[1], &a) || !enif_get_int64(env, argv[2], &b) ||
       !enif_get_int64(env, argv[3], &c) || !enif_get_int(env, argv[4], &world) || !enif_get_int(env, argv[5], &rank))
     return enif_make_badarg(env);
-  if (b < -0x7fffffff || b > 0x7fffffff || c < -0x7fffffff || c > 0x7fffffff) return enif_make_badarg(env);
+  if (b < -0x7fffffff || b > 0x7fffffff || c < -0x7fffffff || c > 0x7fffffff || kind < SHARD_RANGE || kind > SHARD_FIR) return enif_make_badarg(env);
   int64_t r[4] = {0, 0, 0, 0};
-  int rc;
-  switch (kind) {
-    case 0: rc = nxsig_shard_range(a, world, rank, &r[0], &r[1]); break;
-    case 1: rc = nxsig_shard_frames(a, (int32_t)b, (int32_t)c, world, rank, &r[0], &r[1], &r[2], &r[3]); break;
-    case 2: rc = nxsig_shard_istft(a, (int32_t)b, (int32_t)c, world, rank, &r[0], &r[1], &r[2], &r[3]); break;
-    case 3: rc = nxsig_shard_fir(a, (int32_t)b, (int32_t)c, world, rank, &r[0], &r[1], &r[2], &r[3]); break;
-    default: return enif_make_badarg(env);
-  }
+  int rc = shard_plan(kind, a, (int32_t)b, (int32_t)c, world, rank, r);
   if (rc) return mk_error(env, rc);
   return mk_ok(env, enif_make_tuple4(env, enif_make_int64(env, r[0]), enif_make_int64(env, r[1]), enif_make_int64(env, r[2]),
                                      enif_make_int64(env, r[3])));
@@ -1681,10 +1358,10 @@ static ERL_NIF_TERM nif_group_scatter(ErlNifEnv* env, int argc, const ERL_NIF_TE
 /* group_gather(group, [buf], batch, row_bytes, parts) -> {:ok, bin}: the inverse of group_scatter for RESULT shards */
 static ERL_NIF_TERM nif_group_gather(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary ob;
   ErlNifSInt64 batch, row_bytes;
   part_t parts[NXSIG_MAX_MEMBERS];
   buf_res_t* bufs[NXSIG_MAX_MEMBERS];
+  result_t o = {0};
   if (argc != 5 || !get_grp(env, argv[0], &g) || !enif_get_int64(env, argv[2], &batch) || !enif_get_int64(env, argv[3], &row_bytes))
     return enif_make_badarg(env);
   const int n = nxsig_group_local_count(g->grp);
@@ -1694,72 +1371,74 @@ static ERL_NIF_TERM nif_group_gather(ErlNifEnv* env, int argc, const ERL_NIF_TER
     if (parts[i].row0 > batch || parts[i].rows > batch - parts[i].row0 || parts[i].off > row_bytes || parts[i].len > row_bytes - parts[i].off ||
         (parts[i].len > 0 && (uint64_t)parts[i].rows > (uint64_t)bufs[i]->bytes / (uint64_t)parts[i].len))
       return enif_make_badarg(env);
-  if (!out_bin(&ob, (uint64_t)batch, (uint64_t)row_bytes, 1, 1)) return mk_oom(env);
-  memset(ob.data, 0, ob.size);   /* positions no shard covers (none for the plans of nxsig_shard_*) read as zero */
-  for (int i = 0; i < n; ++i) {
+  int rc = res_open(&o, NULL, NXSIG_HOST, 1, (uint64_t)batch, (uint64_t)row_bytes, 1);
+  if (!rc) memset(o.data, 0, o.bytes);   /* positions no shard covers (none for the plans of nxsig_shard_*) read as zero */
+  for (int i = 0; !rc && i < n; ++i) {
     nxsig_ctx* c = nxsig_group_ctx(g->grp, i);
-    int rc = nxsig_sync(c);      /* the shard may still be in flight on the member's stream */
+    rc = nxsig_sync(c);          /* the shard may still be in flight on the member's stream */
     for (int64_t r = 0; !rc && r < parts[i].rows && parts[i].len > 0; ++r)
-      rc = nxsig_download(c, ob.data + (size_t)(parts[i].row0 + r) * (size_t)row_bytes + (size_t)parts[i].off,
+      rc = nxsig_download(c, (char*)o.data + (size_t)(parts[i].row0 + r) * (size_t)row_bytes + (size_t)parts[i].off,
                           (const char*)bufs[i]->dptr + (size_t)r * (size_t)parts[i].len, (size_t)parts[i].len);
-    if (rc) { enif_release_binary(&ob); return mk_error(env, rc); }
   }
-  return mk_ok(env, enif_make_binary(env, &ob));
+  return res_ok(env, &o, rc);
 }
 
-/* output shard sizes (bytes per member) of the sharded calls; gather: every member holds the whole tensor */
-static int out_sizes(grp_res_t* g, int n, int axis, int gather, int64_t batch, int64_t items_per_row, int64_t item_bytes, int kind, int64_t a,
-                     int32_t b, int32_t c, size_t* bytes) {
-  const int world = nxsig_group_world(g->grp);
-  for (int i = 0; i < n; ++i) {
-    const int rank = nxsig_group_rank(g->grp, i);
-    int64_t rows = batch, items = items_per_row;
-    if (!gather) {
-      int64_t r[4];
-      int rc;
-      if (axis == NXSIG_SHARD_CHANNELS) { if ((rc = nxsig_shard_range(batch, world, rank, &r[0], &r[1]))) return rc; rows = r[1] - r[0]; }
-      else if (kind == 1) { if ((rc = nxsig_shard_frames(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]))) return rc; items = r[1] - r[0]; }
-      else if (kind == 2) { if ((rc = nxsig_shard_istft(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]))) return rc; items = r[3] - r[2]; }
-      else { if ((rc = nxsig_shard_fir(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]))) return rc; items = r[1] - r[0]; }
-    }
-    size_t sz = (size_t)item_bytes;
-    if (!mul_size(&sz, (uint64_t)rows) || !mul_size(&sz, (uint64_t)items)) return NXSIG_ERR_OOM;
-    bytes[i] = sz;
-  }
-  return 0;
+/* The member buffers of a *_sharded_dev call and the result shards it allocates.  Shard sizes (bytes per member) follow the partition
+ * rules of the library: the channels axis splits the `batch` rows (nxsig_shard_range), any other axis splits every row by the plan of
+ * `kind` — SHARD_FRAMES stft (f32 samples in, frames out; a = num_frames, b = frame_length, c = hop), SHARD_ISTFT (frames in, samples
+ * out; the same a, b, c), SHARD_FIR (samples in, samples out; a = length, b = taps, c = mode).  Each plan answers {x0, x1, y0, y1}: the
+ * frames / fir plans give the OUTPUT range first and the input span second, the istft plan the input frames first. */
+typedef struct {
+  int n;
+  buf_res_t* in[NXSIG_MAX_MEMBERS];
+  void* out[NXSIG_MAX_MEMBERS];
+  size_t bytes[NXSIG_MAX_MEMBERS];
+} shards_t;
+static int get_shards(ErlNifEnv* env, ERL_NIF_TERM list, grp_res_t* g, shards_t* s) {
+  memset(s->out, 0, sizeof s->out);
+  s->n = nxsig_group_local_count(g->grp);
+  return s->n >= 1 && s->n <= NXSIG_MAX_MEMBERS && get_bufs(env, list, g, s->n, s->in);
 }
-/* INPUT shard sizes (bytes per member) the sharded calls will READ, from the same partition rules: kind 1 stft (f32 samples; a =
- * num_frames, b = frame_length, c = hop, items_per_row = length), kind 2 istft (c64 frames of item_bytes = K * 8; a = num_frames),
- * kind 3 fir (f32 samples; a = length, b = taps, c = mode).  A buffer smaller than this would be read out of bounds on the device:
- * the *_sharded_dev NIFs refuse it. */
-static int in_sizes(grp_res_t* g, int n, int axis, int64_t batch, int64_t items_per_row, int64_t item_bytes, int kind, int64_t a, int32_t b,
-                    int32_t c, size_t* bytes) {
+/* bytes per member of the input (output = 0) or output (1) shards; gather: every member holds the whole output tensor */
+static int shard_sizes(grp_res_t* g, int n, int output, int axis, int gather, int64_t batch, int64_t items_per_row, int64_t item_bytes, int kind,
+                       int64_t a, int32_t b, int32_t c, size_t* bytes) {
   const int world = nxsig_group_world(g->grp);
+  const int lo = (kind == SHARD_ISTFT) == output ? 2 : 0;   /* which pair of the plan's answer this side of the call reads */
   for (int i = 0; i < n; ++i) {
     const int rank = nxsig_group_rank(g->grp, i);
     int64_t rows = batch, items = items_per_row, r[4];
     int rc;
-    if (axis == NXSIG_SHARD_CHANNELS) { if ((rc = nxsig_shard_range(batch, world, rank, &r[0], &r[1]))) return rc; rows = r[1] - r[0]; }
-    else if (kind == 1) { if ((rc = nxsig_shard_frames(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]))) return rc; items = r[3] - r[2]; }
-    else if (kind == 2) { if ((rc = nxsig_shard_istft(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]))) return rc; items = r[1] - r[0]; }
-    else { if ((rc = nxsig_shard_fir(a, b, c, world, rank, &r[0], &r[1], &r[2], &r[3]))) return rc; items = r[3] - r[2]; }
+    if (!gather && axis == NXSIG_SHARD_CHANNELS) { if ((rc = shard_plan(SHARD_RANGE, batch, 0, 0, world, rank, r))) return rc; rows = r[1] - r[0]; }
+    else if (!gather) { if ((rc = shard_plan(kind, a, b, c, world, rank, r))) return rc; items = r[lo + 1] - r[lo]; }
     size_t sz = (size_t)item_bytes;
     if (rows < 0 || items < 0 || !mul_size(&sz, (uint64_t)rows) || !mul_size(&sz, (uint64_t)items)) return NXSIG_ERR_OOM;
     bytes[i] = sz;
   }
   return 0;
 }
-static int bufs_hold(int n, buf_res_t** b, const size_t* need) {
-  for (int i = 0; i < n; ++i)
-    if (b[i]->bytes < need[i]) return 0;
-  return 1;
-}
-static int alloc_members(grp_res_t* g, int n, const size_t* bytes, void** d) {
-  for (int i = 0; i < n; ++i) {
-    int rc = nxsig_alloc(nxsig_group_ctx(g->grp, i), bytes[i] ? bytes[i] : 4, &d[i]);
-    if (rc) { free_members(g, n, d); return rc; }
-  }
+/* What the four *_sharded_dev NIFs do between reading their terms and calling the library: refuse member buffers smaller than the
+ * shards the call will READ — they would be read out of bounds on the device, e.g. a shard scattered for another plan, or
+ * the frame shards of stft(axis: :frames) handed to istft, which needs halo frames too — then allocate the result shards.
+ * Returns 0 with s->out / s->bytes filled, or the error term in *err. */
+static int shards_open(ErlNifEnv* env, grp_res_t* g, shards_t* s, int axis, int gather, int64_t batch, int64_t in_items, int64_t in_item_bytes,
+                       int64_t out_items, int64_t out_item_bytes, int kind, int64_t a, int32_t b, int32_t c, ERL_NIF_TERM* err) {
+  int rc = shard_sizes(g, s->n, 0, axis, 0, batch, in_items, in_item_bytes, kind, a, b, c, s->bytes);
+  for (int i = 0; !rc && i < s->n; ++i)
+    if (s->in[i]->bytes < s->bytes[i]) { *err = enif_make_badarg(env); return 1; }
+  if (!rc) rc = shard_sizes(g, s->n, 1, axis, gather, batch, out_items, out_item_bytes, kind, a, b, c, s->bytes);
+  if (rc) { *err = rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc); return 1; }
+  for (int i = 0; i < s->n; ++i)
+    if ((rc = nxsig_alloc(nxsig_group_ctx(g->grp, i), s->bytes[i] ? s->bytes[i] : 4, &s->out[i]))) {
+      free_members(g, s->n, s->out);
+      *err = mk_error(env, rc);
+      return 1;
+    }
   return 0;
+}
+/* the error of a failed library call, once the result shards are returned */
+static ERL_NIF_TERM shards_fail(ErlNifEnv* env, grp_res_t* g, shards_t* s, int rc) {
+  free_members(g, s->n, s->out);
+  return mk_error(env, rc);
 }
 
 /* stft_sharded_dev(group, [x_buf], length, batch, window_bin, params, axis, gather) -> {:ok, [z_buf], num_frames}
@@ -1767,139 +1446,89 @@ static int alloc_members(grp_res_t* g, int n, const size_t* bytes, void** d) {
  * (or, gather = 1, the whole c64[batch][M][K] on every member, assembled by the RCCL all-gather) stay on their devices */
 static ERL_NIF_TERM nif_stft_sharded_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary w;
-  ErlNifSInt64 length;
-  int batch, axis, gather;
-  nxsig_stft_params p;
-  buf_res_t* xb[NXSIG_MAX_MEMBERS];
-  if (argc != 8 || !get_grp(env, argv[0], &g) || !enif_get_int64(env, argv[2], &length) || !enif_get_int(env, argv[3], &batch) ||
-      !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) || !enif_get_int(env, argv[6], &axis) ||
-      !enif_get_int(env, argv[7], &gather))
+  frames_args_t a;
+  int axis, gather;
+  shards_t s;
+  ERL_NIF_TERM err;
+  if (argc != 8 || !get_grp(env, argv[0], &g) || !get_frames_args(env, argv + 2, 0, 0, &a) || !enif_get_int(env, argv[6], &axis) ||
+      !enif_get_int(env, argv[7], &gather) || !get_shards(env, argv[1], g, &s))
     return enif_make_badarg(env);
-  const int n = nxsig_group_local_count(g->grp);
-  if (n < 1 || n > NXSIG_MAX_MEMBERS || batch < 1 || length < 1 || w.size != (size_t)p.frame_length * 4 || !get_bufs(env, argv[1], g, n, xb))
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  size_t bytes[NXSIG_MAX_MEMBERS];
-  void* z[NXSIG_MAX_MEMBERS] = {0};
-  int rc = in_sizes(g, n, axis, batch, length, 4, 1, m, p.frame_length, p.hop, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if (!bufs_hold(n, xb, bytes)) return enif_make_badarg(env);   /* a shard scattered for another plan: it would be read out of bounds */
-  rc = out_sizes(g, n, axis, gather, batch, m, (int64_t)p.fft_length * 8, 1, m, p.frame_length, p.hop, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if ((rc = alloc_members(g, n, bytes, z))) return mk_error(env, rc);
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  if (shards_open(env, g, &s, axis, gather, a.batch, a.len, 4, a.out, (int64_t)a.p.fft_length * 8, SHARD_FRAMES, a.out, a.p.frame_length, a.p.hop, &err))
+    return err;
   const float* xs[NXSIG_MAX_MEMBERS];
   nxsig_c64* zs[NXSIG_MAX_MEMBERS];
-  for (int i = 0; i < n; ++i) { xs[i] = (const float*)xb[i]->dptr; zs[i] = (nxsig_c64*)z[i]; }
+  for (int i = 0; i < s.n; ++i) { xs[i] = (const float*)s.in[i]->dptr; zs[i] = (nxsig_c64*)s.out[i]; }
   /* channel shards: rows of the full length; frame shards: dense per-member spans (batch_stride 0, see nxsig.h) */
-  rc = nxsig_stft_sharded_f32(g->grp, xs, length, batch, axis == NXSIG_SHARD_CHANNELS ? length : 0, (const float*)w.data, &p, axis, gather, zs,
-                              NXSIG_DEVICE);
-  if (rc) { free_members(g, n, z); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), bufs_to_list(env, g, n, z, bytes), enif_make_int64(env, m));
+  int rc = nxsig_stft_sharded_f32(g->grp, xs, a.len, a.batch, axis == NXSIG_SHARD_CHANNELS ? a.len : 0, (const float*)a.w.data, &a.p, axis, gather,
+                                  zs, NXSIG_DEVICE);
+  if (rc) return shards_fail(env, g, &s, rc);
+  return mk_ok2(env, bufs_to_list(env, g, s.n, s.out, s.bytes), enif_make_int64(env, a.out));
 }
 
 /* istft_sharded_dev(group, [z_buf], num_frames, batch, window_bin, params, axis, gather) -> {:ok, [y_buf]} */
 static ERL_NIF_TERM nif_istft_sharded_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary w;
-  ErlNifSInt64 m;
-  int batch, axis, gather;
-  nxsig_stft_params p;
-  buf_res_t* zb[NXSIG_MAX_MEMBERS];
-  if (argc != 8 || !get_grp(env, argv[0], &g) || !enif_get_int64(env, argv[2], &m) || !enif_get_int(env, argv[3], &batch) ||
-      !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) || !enif_get_int(env, argv[6], &axis) ||
-      !enif_get_int(env, argv[7], &gather))
+  frames_args_t a;
+  int axis, gather;
+  shards_t s;
+  ERL_NIF_TERM err;
+  if (argc != 8 || !get_grp(env, argv[0], &g) || !get_frames_args(env, argv + 2, 0, 1, &a) || !enif_get_int(env, argv[6], &axis) ||
+      !enif_get_int(env, argv[7], &gather) || !get_shards(env, argv[1], g, &s))
     return enif_make_badarg(env);
-  const int n = nxsig_group_local_count(g->grp);
-  if (n < 1 || n > NXSIG_MAX_MEMBERS || batch < 1 || m < 1 || w.size != (size_t)p.frame_length * 4 || !get_bufs(env, argv[1], g, n, zb))
-    return enif_make_badarg(env);
-  int64_t out_len = nxsig_ola_length(m, p.frame_length, p.hop);
-  if (out_len < 0) return mk_error(env, (int)out_len);
-  size_t bytes[NXSIG_MAX_MEMBERS];
-  void* y[NXSIG_MAX_MEMBERS] = {0};
-  int rc = in_sizes(g, n, axis, batch, m, (int64_t)p.frame_length * 8, 2, m, p.frame_length, p.hop, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if (!bufs_hold(n, zb, bytes)) return enif_make_badarg(env);   /* e.g. the frame shards of stft(axis: :frames): istft needs halo frames too */
-  rc = out_sizes(g, n, axis, gather, batch, out_len, 8, 2, m, p.frame_length, p.hop, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if ((rc = alloc_members(g, n, bytes, y))) return mk_error(env, rc);
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  if (shards_open(env, g, &s, axis, gather, a.batch, a.len, (int64_t)a.p.frame_length * 8, a.out, 8, SHARD_ISTFT, a.len, a.p.frame_length, a.p.hop, &err))
+    return err;
   const nxsig_c64* zs[NXSIG_MAX_MEMBERS];
   nxsig_c64* ys[NXSIG_MAX_MEMBERS];
-  for (int i = 0; i < n; ++i) { zs[i] = (const nxsig_c64*)zb[i]->dptr; ys[i] = (nxsig_c64*)y[i]; }
-  rc = nxsig_istft_sharded_c64(g->grp, zs, m, batch, (const float*)w.data, &p, axis, gather, ys, NXSIG_DEVICE);
-  if (rc) { free_members(g, n, y); return mk_error(env, rc); }
-  return mk_ok(env, bufs_to_list(env, g, n, y, bytes));
+  for (int i = 0; i < s.n; ++i) { zs[i] = (const nxsig_c64*)s.in[i]->dptr; ys[i] = (nxsig_c64*)s.out[i]; }
+  int rc = nxsig_istft_sharded_c64(g->grp, zs, a.len, a.batch, (const float*)a.w.data, &a.p, axis, gather, ys, NXSIG_DEVICE);
+  if (rc) return shards_fail(env, g, &s, rc);
+  return mk_ok(env, bufs_to_list(env, g, s.n, s.out, s.bytes));
 }
 
 /* fir_sharded_dev(group, [x_buf], length, batch, taps_bin, mode, axis, gather) -> {:ok, [y_buf]} */
 static ERL_NIF_TERM nif_fir_sharded_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary h;
-  ErlNifSInt64 length;
-  int batch, mode, axis, gather;
-  buf_res_t* xb[NXSIG_MAX_MEMBERS];
-  if (argc != 8 || !get_grp(env, argv[0], &g) || !enif_get_int64(env, argv[2], &length) || !enif_get_int(env, argv[3], &batch) ||
-      !enif_inspect_binary(env, argv[4], &h) || !enif_get_int(env, argv[5], &mode) || !enif_get_int(env, argv[6], &axis) ||
-      !enif_get_int(env, argv[7], &gather))
+  fir_args_t a;
+  int axis, gather;
+  shards_t s;
+  ERL_NIF_TERM err;
+  if (argc != 8 || !get_grp(env, argv[0], &g) || !get_fir_args(env, argv + 2, 4, &a) || !enif_get_int(env, argv[6], &axis) ||
+      !enif_get_int(env, argv[7], &gather) || !get_shards(env, argv[1], g, &s))
     return enif_make_badarg(env);
-  const int n = nxsig_group_local_count(g->grp);
-  if (n < 1 || n > NXSIG_MAX_MEMBERS || batch < 1 || length < 1 || h.size < 4 || h.size % 4 || h.size / 4 > 0x7fffffff ||
-      !get_bufs(env, argv[1], g, n, xb))
-    return enif_make_badarg(env);
-  const int taps = (int)(h.size / 4);
-  int64_t out_len = nxsig_conv_length(length, taps, mode);
-  if (out_len < 0) return mk_error(env, (int)out_len);
-  size_t bytes[NXSIG_MAX_MEMBERS];
-  void* y[NXSIG_MAX_MEMBERS] = {0};
-  int rc = in_sizes(g, n, axis, batch, length, 4, 3, length, taps, mode, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if (!bufs_hold(n, xb, bytes)) return enif_make_badarg(env);
-  rc = out_sizes(g, n, axis, gather, batch, out_len, 4, 3, length, taps, mode, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if ((rc = alloc_members(g, n, bytes, y))) return mk_error(env, rc);
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  if (shards_open(env, g, &s, axis, gather, a.batch, a.len, 4, a.out, 4, SHARD_FIR, a.len, a.taps, a.mode, &err)) return err;
   const float* xs[NXSIG_MAX_MEMBERS];
   float* ys[NXSIG_MAX_MEMBERS];
-  for (int i = 0; i < n; ++i) { xs[i] = (const float*)xb[i]->dptr; ys[i] = (float*)y[i]; }
-  rc = nxsig_fir_sharded_f32(g->grp, xs, length, batch, axis == NXSIG_SHARD_CHANNELS ? length : 0, (const float*)h.data, taps, mode, axis, gather,
-                             ys, NXSIG_DEVICE);
-  if (rc) { free_members(g, n, y); return mk_error(env, rc); }
-  return mk_ok(env, bufs_to_list(env, g, n, y, bytes));
+  for (int i = 0; i < s.n; ++i) { xs[i] = (const float*)s.in[i]->dptr; ys[i] = (float*)s.out[i]; }
+  int rc = nxsig_fir_sharded_f32(g->grp, xs, a.len, a.batch, axis == NXSIG_SHARD_CHANNELS ? a.len : 0, (const float*)a.h.data, a.taps, a.mode, axis,
+                                 gather, ys, NXSIG_DEVICE);
+  if (rc) return shards_fail(env, g, &s, rc);
+  return mk_ok(env, bufs_to_list(env, g, s.n, s.out, s.bytes));
 }
 
 /* stft_mel_sharded_dev(group, [x_buf], length, batch, window_bin, params, mel_bins, filters_bin, axis) -> {:ok, [o_buf], M} */
 static ERL_NIF_TERM nif_stft_mel_sharded_dev(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
   grp_res_t* g;
-  ErlNifBinary w, f;
-  ErlNifSInt64 length;
-  int batch, bins, axis;
-  nxsig_stft_params p;
-  buf_res_t* xb[NXSIG_MAX_MEMBERS];
-  if (argc != 9 || !get_grp(env, argv[0], &g) || !enif_get_int64(env, argv[2], &length) || !enif_get_int(env, argv[3], &batch) ||
-      !enif_inspect_binary(env, argv[4], &w) || !get_params(env, argv[5], &p) || !enif_get_int(env, argv[6], &bins) ||
-      !enif_inspect_binary(env, argv[7], &f) || !enif_get_int(env, argv[8], &axis))
+  frames_args_t a;
+  int bins, axis;
+  const void* f;
+  shards_t s;
+  ERL_NIF_TERM err;
+  if (argc != 9 || !get_grp(env, argv[0], &g) || !get_frames_args(env, argv + 2, 0, 0, &a) || !enif_get_int(env, argv[6], &bins) ||
+      !enif_get_int(env, argv[8], &axis) || a.p.fft_length < 2 || !get_rows(env, argv[7], NULL, NXSIG_HOST, 4, bins, a.p.fft_length, 1, &f) ||
+      !get_shards(env, argv[1], g, &s))
     return enif_make_badarg(env);
-  const int n = nxsig_group_local_count(g->grp);
-  if (n < 1 || n > NXSIG_MAX_MEMBERS || batch < 1 || length < 1 || bins < 1 || w.size != (size_t)p.frame_length * 4 || p.fft_length < 2 ||
-      f.size % 4 || f.size / 4 / (size_t)bins != (size_t)p.fft_length || f.size / 4 % (size_t)bins || !get_bufs(env, argv[1], g, n, xb))
-    return enif_make_badarg(env);
-  int64_t m = nxsig_num_frames(length, p.frame_length, p.hop, p.pad_mode, p.pad_lo, p.pad_hi);
-  if (m < 0) return mk_error(env, (int)m);
-  size_t bytes[NXSIG_MAX_MEMBERS];
-  void* o[NXSIG_MAX_MEMBERS] = {0};
-  int rc = in_sizes(g, n, axis, batch, length, 4, 1, m, p.frame_length, p.hop, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if (!bufs_hold(n, xb, bytes)) return enif_make_badarg(env);
-  rc = out_sizes(g, n, axis, 0, batch, m, (int64_t)bins * 4, 1, m, p.frame_length, p.hop, bytes);
-  if (rc) return rc == NXSIG_ERR_OOM ? mk_oom(env) : mk_error(env, rc);
-  if ((rc = alloc_members(g, n, bytes, o))) return mk_error(env, rc);
+  if (a.out < 0) return mk_error(env, (int)a.out);
+  if (shards_open(env, g, &s, axis, 0, a.batch, a.len, 4, a.out, (int64_t)bins * 4, SHARD_FRAMES, a.out, a.p.frame_length, a.p.hop, &err)) return err;
   const float* xs[NXSIG_MAX_MEMBERS];
   float* os[NXSIG_MAX_MEMBERS];
-  for (int i = 0; i < n; ++i) { xs[i] = (const float*)xb[i]->dptr; os[i] = (float*)o[i]; }
-  rc = nxsig_stft_mel_sharded_f32(g->grp, xs, length, batch, axis == NXSIG_SHARD_CHANNELS ? length : 0, (const float*)w.data, &p, bins,
-                                  (const float*)f.data, axis, os, NULL, NXSIG_DEVICE);
-  if (rc) { free_members(g, n, o); return mk_error(env, rc); }
-  return enif_make_tuple3(env, mk_atom(env, "ok"), bufs_to_list(env, g, n, o, bytes), enif_make_int64(env, m));
+  for (int i = 0; i < s.n; ++i) { xs[i] = (const float*)s.in[i]->dptr; os[i] = (float*)s.out[i]; }
+  int rc = nxsig_stft_mel_sharded_f32(g->grp, xs, a.len, a.batch, axis == NXSIG_SHARD_CHANNELS ? a.len : 0, (const float*)a.w.data, &a.p, bins,
+                                      (const float*)f, axis, os, NULL, NXSIG_DEVICE);
+  if (rc) return shards_fail(env, g, &s, rc);
+  return mk_ok2(env, bufs_to_list(env, g, s.n, s.out, s.bytes), enif_make_int64(env, a.out));
 }
 
 static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {

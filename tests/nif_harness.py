@@ -66,29 +66,34 @@ _lib = None
 _keep = None  # environment that owns resource terms handed back to Python
 
 
+def open_lib(so):
+    """load one build of the shim + term runtime and declare the fake_* / enif_* helpers the driver uses"""
+    L = C.CDLL(so)
+    vp, sz = C.c_void_p, C.c_size_t
+    for name, res, args in [
+        ("fake_env_new", vp, []), ("fake_env_free", None, [vp]), ("fake_load", C.c_int, []),
+        ("fake_num_funcs", C.c_int, []), ("fake_func_name", C.c_char_p, [C.c_int]), ("fake_func_arity", C.c_uint, [C.c_int]),
+        ("fake_func_flags", C.c_uint, [C.c_int]), ("fake_module_name", C.c_char_p, []),
+        ("fake_call", vp, [vp, C.c_char_p, C.c_int, C.POINTER(vp)]), ("fake_binary", vp, [vp, vp, sz]),
+        ("fake_copy_resource", vp, [vp, vp]), ("fake_tag", C.c_int, [vp]), ("fake_atom_name", C.c_char_p, [vp]),
+        ("fake_bin_data", vp, [vp]), ("fake_bin_size", sz, [vp]), ("fake_tuple_arity", C.c_int, [vp]),
+        ("fake_tuple_elem", vp, [vp, C.c_int]), ("fake_cons_head", vp, [vp]), ("fake_cons_tail", vp, [vp]), ("fake_live_resources", C.c_long, []), ("fake_dtor_calls", C.c_long, []),
+        ("fake_live_binaries", C.c_long, []), ("fake_set_alloc_limit", None, [sz]),
+        ("enif_make_int64", vp, [vp, C.c_int64]), ("enif_make_double", vp, [vp, C.c_double]), ("enif_make_atom", vp, [vp, C.c_char_p]),
+        ("enif_make_tuple_from_array", vp, [vp, C.POINTER(vp), C.c_uint]), ("enif_make_list_from_array", vp, [vp, C.POINTER(vp), C.c_uint]),
+        ("enif_get_int64", C.c_int, [vp, vp, C.POINTER(C.c_int64)]), ("enif_get_double", C.c_int, [vp, vp, C.POINTER(C.c_double)]),
+    ]:
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
+    assert L.fake_load() == 0
+    return L
+
+
 def lib():
     global _lib, _keep
     if _lib is None:
-        L = C.CDLL(build())
-        vp, sz = C.c_void_p, C.c_size_t
-        for name, res, args in [
-            ("fake_env_new", vp, []), ("fake_env_free", None, [vp]), ("fake_load", C.c_int, []),
-            ("fake_num_funcs", C.c_int, []), ("fake_func_name", C.c_char_p, [C.c_int]), ("fake_func_arity", C.c_uint, [C.c_int]),
-            ("fake_func_flags", C.c_uint, [C.c_int]), ("fake_module_name", C.c_char_p, []),
-            ("fake_call", vp, [vp, C.c_char_p, C.c_int, C.POINTER(vp)]), ("fake_binary", vp, [vp, vp, sz]),
-            ("fake_copy_resource", vp, [vp, vp]), ("fake_tag", C.c_int, [vp]), ("fake_atom_name", C.c_char_p, [vp]),
-            ("fake_bin_data", vp, [vp]), ("fake_bin_size", sz, [vp]), ("fake_tuple_arity", C.c_int, [vp]),
-            ("fake_tuple_elem", vp, [vp, C.c_int]), ("fake_cons_head", vp, [vp]), ("fake_cons_tail", vp, [vp]), ("fake_live_resources", C.c_long, []), ("fake_dtor_calls", C.c_long, []),
-            ("fake_live_binaries", C.c_long, []), ("fake_set_alloc_limit", None, [sz]),
-            ("enif_make_int64", vp, [vp, C.c_int64]), ("enif_make_double", vp, [vp, C.c_double]), ("enif_make_atom", vp, [vp, C.c_char_p]),
-            ("enif_make_tuple_from_array", vp, [vp, C.POINTER(vp), C.c_uint]), ("enif_make_list_from_array", vp, [vp, C.POINTER(vp), C.c_uint]),
-            ("enif_get_int64", C.c_int, [vp, vp, C.POINTER(C.c_int64)]), ("enif_get_double", C.c_int, [vp, vp, C.POINTER(C.c_double)]),
-        ]:
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        assert L.fake_load() == 0
-        _keep = L.fake_env_new()
-        _lib = L
+        _lib = open_lib(build())
+        _keep = _lib.fake_env_new()
     return _lib
 
 
