@@ -207,8 +207,9 @@ static int launch_istft_packed_R(Ctx* c, const IstftLaunch& s, const float* wind
   const int64_t total_segs = a.segs_per_row * s.batch;
   const int waves_per_cu = tune(c, kT_ISTFT_RUNS_PER_CU, 12);
   int64_t run_len = (total_segs + (int64_t)c->num_cus * waves_per_cu - 1) / ((int64_t)c->num_cus * waves_per_cu);
-  if (run_len < 8) run_len = 8;
-  run_len = (run_len + 1) & ~(int64_t)1;
+  const int min_run = tune(c, kT_ISTFT_MIN_RUN, 8);   // (no small-launch rule here: a packed launch keeps runs of 8 unless the switch says otherwise)
+  if (run_len < min_run) run_len = min_run;
+  run_len = (run_len + 1) & ~(int64_t)1;              // frame pairs: runs start at even segments
   a.run_len = run_len;
   a.runs_per_row = (a.segs_per_row + run_len - 1) / run_len;
   a.total_runs = a.runs_per_row * s.batch;

@@ -365,7 +365,7 @@ int launch_stft_r20(Ctx* c, const StftLaunch& s, bool* handled, const MelLaunch*
   int rc = ctx_table(c, 0x20A20ull, tw.data(), tw.size() * sizeof(float2), &dt);
   if (rc) return rc;
   b.tw = reinterpret_cast<const v2f*>(dt);
-  const int units_per_wave = fill_units_per_wave(c, b.total_units, W, sink == kSinkMel ? 8 : 2);  // the mel sink amortises its CSR preload
+  const int units_per_wave = tuned_units_per_wave(c, kT_WAVE_UNITS_PER_WAVE, b.total_units, W, sink == kSinkMel ? 8 : 2);  // the mel sink amortises its CSR preload
   a.chunk = (int64_t)W * (units_per_wave < 1 ? 1 : units_per_wave);
   const int64_t blocks = (b.total_units + a.chunk - 1) / a.chunk;
   if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "stft: too many frames for one launch");

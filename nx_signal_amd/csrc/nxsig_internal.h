@@ -224,6 +224,12 @@ static inline int fill_units_per_wave(const Ctx* c, int64_t total_units, int W, 
   const int64_t fill = (total_units + slots - 1) / slots;
   return fill < dflt ? (fill < 1 ? 1 : (int)fill) : dflt;
 }
+// ... behind the launcher's geometry switch (NXSIG_WAVE_UNITS_PER_WAVE for the forward and row kernels, NXSIG_FIR_UNITS_PER_WAVE for the
+// FIR streams): switch set -> its value (range-checked at the way in, tuning_in_range), else the heuristic above.  Every streaming kernel
+// walks its chunk with `for (u = begin + wave; u < end; u += W)`, so any value computes the same result (tests/test_gpu_launch_geometry.py)
+static inline int tuned_units_per_wave(const Ctx* c, TuneKey k, int64_t total_units, int W, int dflt) {
+  return c->tuning.set[k] ? (int)c->tuning.v[k] : fill_units_per_wave(c, total_units, W, dflt);
+}
 
 // Shortest run of the persistent inverse kernels (every run recomputes its halo, so long runs pay less of it — but a launch with fewer
 // units than two per wave slot is ONE partial round, and what sets its time is the length of a run: 1 s of audio, 184 frames, ran as 23

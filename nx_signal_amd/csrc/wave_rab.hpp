@@ -526,7 +526,7 @@ inline int launch_rab(Ctx* c, const StftLaunch& s, bool* handled, const MelLaunc
     b.tw = reinterpret_cast<const v2f*>(dt);
   }
   const int w = sink == kSinkMel ? WM : W;
-  a.chunk = (int64_t)w * fill_units_per_wave(c, b.total_units, w, sink == kSinkMel ? 8 : 4);   // four units per wave (two: -1 ... -3 %), short-lived workgroups; the mel sink amortises its CSR preload
+  a.chunk = (int64_t)w * tuned_units_per_wave(c, kT_WAVE_UNITS_PER_WAVE, b.total_units, w, sink == kSinkMel ? 8 : 4);   // four units per wave (two: -1 ... -3 %), short-lived workgroups; the mel sink amortises its CSR preload
   const int64_t blocks = (b.total_units + a.chunk - 1) / a.chunk;
   if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "stft: too many frames for one launch");
   const size_t lds = (size_t)TABS + (size_t)w * BUF * 8 + lds_extra;
@@ -741,7 +741,7 @@ inline int launch_rab_c64(Ctx* c, const StftLaunch& s, bool* handled) {
     c->memo[key] = {reinterpret_cast<uint64_t>(dt)};
     a.tw = reinterpret_cast<const v2f*>(dt);
   }
-  a.chunk = (int64_t)W * fill_units_per_wave(c, a.total_units, W, 4);
+  a.chunk = (int64_t)W * tuned_units_per_wave(c, kT_WAVE_UNITS_PER_WAVE, a.total_units, W, 4);
   const int64_t blocks = (a.total_units + a.chunk - 1) / a.chunk;
   if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "stft: too many frames for one launch");
   const size_t lds = (size_t)rab_tab_bytes(KB) + (size_t)W * BUF * 8;

@@ -1509,8 +1509,8 @@ static int launch_wave(Ctx* c, const StftLaunch& s, const MelLaunch* mel = nullp
   // dispatcher hands chunks out in order.  Many short-lived workgroups balance the load across CUs / XCDs
   // dynamically: measured +12 % over a static equal partition with long-lived workgroups (the slowest CU set
   // the kernel time), at the price of re-loading the 12 KB of tables per workgroup from L2.
-  const int units_per_wave = (mel && mel->mag_kind >= 0) ? (MODE == kModePair ? 16 : 8)
-                             : mel ? (MODE == kModePair ? 16 : 8)
+  const int units_per_wave = (mel && mel->mag_kind >= 0) ? tune(c, kT_WAVE_UNITS_PER_WAVE, MODE == kModePair ? 16 : 8)
+                             : mel ? tune(c, kT_WAVE_UNITS_PER_WAVE, MODE == kModePair ? 16 : 8)
                                  : tune(c, kT_WAVE_UNITS_PER_WAVE, MODE == kModePair ? 2 : (MODE == kModeQuad ? (J == 8 ? 8 : 4) : 8));  // measured optima, input
                                  // from HBM (round 3, tools/bench_configs.py gen512 / gen256 / gen128 with NXSIG_BENCH_ALT_INPUTS=4: 4 units per
                                  // wave 0.646 / 0.631 of 8 TB/s against 0.591 / 0.611 at round 2's 2 / 3; fft_length 128: 8 -> 0.593 against 0.572)
@@ -1807,7 +1807,7 @@ static int launch_blue_wave(Ctx* c, const StftLaunch& s, const MelLaunch* mel = 
     if ((rcm = launch_mel_init(c, &b.gmax))) return rcm;
     lds += (size_t)b.nnz * 4 + (size_t)(2 * mel->mel_bins + 1) * 4;
   }
-  const int units_per_wave = fill_units_per_wave(c, a.total_pairs, W, 4);
+  const int units_per_wave = tuned_units_per_wave(c, kT_WAVE_UNITS_PER_WAVE, a.total_pairs, W, 4);
   a.chunk = (int64_t)W * (units_per_wave < 1 ? 1 : units_per_wave);
   const int64_t blocks = (a.total_pairs + a.chunk - 1) / a.chunk;
   if (blocks > 0x7fffffffLL) return set_error(NXSIG_ERR_UNSUPPORTED, "stft: too many frames for one launch");
