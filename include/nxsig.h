@@ -762,6 +762,39 @@ int nxsig_sosfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t ba
 int nxsig_sosfiltfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* sos,
                           int32_t n_sections, int32_t padtype, int64_t padlen, float* y, int32_t mem);
 
+/*
+ * PeakFinding.find_peaks — scipy.signal.find_peaks 1.15 on every line of x along `axis`.  x: f32
+ * (NXSIG_DT_F32) or f64 (NXSIG_DT_F64), the shape limits of nxsig_argrelextrema.  All compares are plain IEEE compares in double on
+ * the exactly widened samples.
+ *   peaks       i in [1, n - 2] with x[i - 1] < x[i]; j the first index > i with x[j] != x[i] (or n - 1); x[j] < x[i].  Edges i and
+ *               j - 1, the peak their mean rounded down.  A plateau that reaches the end of a line is no peak.
+ *   conditions  one bit per condition given: 1 plateau_size, 2 height, 4 threshold, 8 distance, 16 prominence, 32 width; applied in
+ *               that order.  bounds: f64[5][2] HOST, the (min, max) of plateau_size, height, threshold, prominence, width, with
+ *               -inf / +inf for an open side; may be NULL when only the distance is given.  threshold: min <= min(left, right) and
+ *               max(left, right) <= max.
+ *   distance    d = ceil(distance) >= 1.  The peaks of a line are visited from the highest to the lowest, AMONG EQUAL HEIGHTS THE
+ *               LARGER INDEX FIRST (the library's own rule: SciPy leaves ties to an unstable sort); a peak still kept removes every
+ *               other within less than d.  The device plays rounds that give exactly this result; the call waits once per round.
+ *   prominence  wlen: ceil of the caller's window, >= 2, or -1 for the whole line; the walk covers peak -+ wlen / 2.  The base of a
+ *               side is the position of its minimum nearest to the peak.
+ *   width       at x[peak] - prominence * rel_height (rel_height >= 0), linear interpolation at both crossings, no fused
+ *               multiply-add.
+ * Results: indices s32[capacity][rank], the coordinates of the surviving peaks in row-major order, then -1 rows; *valid the true
+ * count, also when it exceeds capacity (0 <= capacity <= lines * ((n - 1) / 2), the most a tensor holds; only the first `capacity`
+ * rows are written).  want: one bit per property returned — bits 0 .. 7 peak_heights, left_thresholds, right_thresholds, prominences,
+ * width_heights, left_ips, right_ips, widths (f64); bits 8 .. 12 left_bases, right_bases, left_edges, right_edges, plateau_sizes (s32
+ * axis coordinates).  fprops: f64[rows][capacity], one row per f64 bit set, in bit order; iprops: s32[rows][capacity] likewise; NaN /
+ * -1 at and past valid.  Either may be NULL when it has no row.  The same bits from run to run and from both dispatch families:
+ * find_peaks.tables (min / max of every block of nxsig_find_peaks_block axis positions bound every walk) and find_peaks.generic
+ * (NXSIG_DISABLE_FIND_PEAKS_TABLES: the same walks element by element).  The only atomics are integer or / and on mask words.
+ */
+int32_t nxsig_find_peaks_block(void);
+/* rounds the distance stage of the calling thread's last nxsig_find_peaks took (0: it did not run) */
+int32_t nxsig_find_peaks_rounds(void);
+int nxsig_find_peaks(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t* shape, int32_t rank, int32_t axis, const double* bounds,
+                     uint32_t conditions, double distance, int64_t wlen, double rel_height, int64_t capacity, uint32_t want,
+                     int32_t* indices, uint32_t* valid, double* fprops, int32_t* iprops, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

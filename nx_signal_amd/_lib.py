@@ -89,7 +89,17 @@ class NxsigCtxIir(C.Structure):
 # with _ctx_spectral to its table in turn, so these two keep their rows in the probe's IIR_TABLE_ENTRIES and
 # tests/golden/abi_error_table_iir.json (tests/test_iir_host.py, tests/test_gpu_iir.py).
 _ctx_iir = C.POINTER(NxsigCtxIir)
-TYPED_CTX = (_ctx, _ctx_spectral, _ctx_iir)
+
+
+class NxsigCtxPeaks(C.Structure):
+    """the same opaque nxsig_ctx, under a fourth name"""
+
+
+# nxsig_ctx* of nxsig_find_peaks: the host tests hold the entry points declared with each earlier pointer type to their own recorded
+# tables, so this one keeps its rows in the probe's PEAKS_TABLE_ENTRIES and tests/golden/abi_error_table_find_peaks.json
+# (tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py).
+_ctx_peaks = C.POINTER(NxsigCtxPeaks)
+TYPED_CTX = (_ctx, _ctx_spectral, _ctx_iir, _ctx_peaks)
 
 
 def ctx_ptr(handle, typ=_ctx):
@@ -164,6 +174,10 @@ SIGNATURES = {
     "nxsig_wiener": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, C.POINTER(_i64), _i32, _f64, _p, C.POINTER(_f64), _i32]),
     "nxsig_argrelextrema": (C.c_int, [_p, _p, _i32, C.POINTER(_i64), _i32, _i32, _i64, _i32, _p, _p, _i32]),
     "nxsig_nonzero": (C.c_int, [_p, _p, C.POINTER(_i64), _i32, _p, _p, _i32]),
+    "nxsig_find_peaks_block": (_i32, []),
+    "nxsig_find_peaks_rounds": (_i32, []),
+    "nxsig_find_peaks": (C.c_int, [_ctx_peaks, _p, _i32, C.POINTER(_i64), _i32, _i32, C.POINTER(_f64), C.c_uint32, _f64, _i64, _f64, _i64,
+                                   C.c_uint32, _p, _p, _p, _p, _i32]),
     "nxsig_sawtooth": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _i32]),
     "nxsig_square": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _p, _i32]),
     "nxsig_gaussian_pulse": (C.c_int, [_p, _p, _i32, _i64, _f64, _f64, _f64, _p, _p, _p, _i32]),

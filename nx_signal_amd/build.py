@@ -55,6 +55,7 @@ UNITS = [
     ("kernels_resample.hip", []),  # Filters.resample_poly: polyphase rational resampling
     ("kernels_welch.hip", []),  # Spectral.welch / csd: Welch's averaged periodogram, the spectrum never in memory
     ("kernels_iir.hip", []),  # Filters.sosfilt / sosfiltfilt: biquad cascades in double, an exact scan over time
+    ("kernels_find_peaks.hip", []),  # PeakFinding.find_peaks: line summary, walks, distance rounds (no FMA contraction: the file says so itself)
 ]
 
 

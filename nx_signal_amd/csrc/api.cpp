@@ -2454,4 +2454,56 @@ int nxsig_sosfiltfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- PeakFinding.find_peaks */
+int32_t nxsig_find_peaks_block(void) { return kFindPeaksBlock; }
+
+int32_t nxsig_find_peaks_rounds(void) { return find_peaks_last_rounds(); }
+
+int nxsig_find_peaks(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t* shape, int32_t rank, int32_t axis, const double* bounds,
+                     uint32_t conditions, double distance, int64_t wlen, double rel_height, int64_t capacity, uint32_t want,
+                     int32_t* indices, uint32_t* valid, double* fprops, int32_t* iprops, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !valid) return set_error(NXSIG_ERR_INVALID_ARG, "find_peaks: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  int64_t total = 0;
+  if ((rc = peaks_shape("find_peaks", shape, rank, &total))) return rc;
+  if (axis < 0 || axis >= rank)
+    return set_error(NXSIG_ERR_INVALID_ARG, "find_peaks: axis " + std::to_string(axis) + " is out of range for rank " + std::to_string(rank));
+  if (dtype != NXSIG_DT_F32 && dtype != NXSIG_DT_F64) return set_error(NXSIG_ERR_INVALID_ARG, "find_peaks: dtype must be NXSIG_DT_F32 or NXSIG_DT_F64");
+  const int64_t n = shape[axis], most = find_peaks_capacity(total / n, n);
+  char msg[96];
+  if (const char* what = find_peaks_check(conditions, bounds, distance, wlen, rel_height, want, capacity, most, msg, sizeof msg))
+    return set_error(NXSIG_ERR_INVALID_ARG, std::string("find_peaks: ") + what);
+  const int nf = find_peaks_f64_rows(want), ni = find_peaks_s32_rows(want);
+  if (capacity > 0 && (!indices || (nf && !fprops) || (ni && !iprops))) return set_error(NXSIG_ERR_INVALID_ARG, "find_peaks: null pointer argument");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  const size_t es = dtype == NXSIG_DT_F64 ? 8 : 4;
+  FindPeaksLaunch a{};
+  a.f64 = dtype == NXSIG_DT_F64; a.shape = shape; a.rank = rank; a.axis = axis; a.conditions = conditions; a.bounds = bounds;
+  a.distance = distance; a.wlen = wlen; a.rel_height = rel_height; a.capacity = capacity; a.want = want;
+  HostIo io(c, mem);
+  // x in; out[0] = valid, out[1] = indices, out[2] = the f64 properties (a host call's s32 properties stay in the launcher's scratch)
+  const size_t ib = (size_t)capacity * rank * 4, fb = (size_t)capacity * nf * 8;
+  if (capacity == 0 || mem == NXSIG_DEVICE) rc = io.open({{x, (size_t)total * es, kScratchNdStageA}}, {{valid, 4, kScratchNdStageB}});
+  else if (nf) rc = io.open({{x, (size_t)total * es, kScratchNdStageA}}, {{valid, 4, kScratchNdStageB}, {indices, ib, kScratchNdStageOut}, {fprops, fb, kScratchNdStageOut}});
+  else rc = io.open({{x, (size_t)total * es, kScratchNdStageA}}, {{valid, 4, kScratchNdStageB}, {indices, ib, kScratchNdStageOut}});
+  if (rc) return rc;
+  const bool staged = mem == NXSIG_HOST && capacity > 0;
+  int32_t* ip_dev = nullptr;
+  a.x = io.in[0];
+  a.valid = static_cast<uint32_t*>(io.out[0]);
+  a.indices = staged ? static_cast<int32_t*>(io.out[1]) : indices;
+  a.fprops = staged ? (nf ? static_cast<double*>(io.out[2]) : nullptr) : fprops;
+  a.iprops = staged ? nullptr : iprops;
+  a.iprops_used = &ip_dev;
+  if ((rc = launch_find_peaks(c, a))) return rc;
+  if ((rc = io.close())) return rc;
+  if (staged && ni) return io.download(iprops, ip_dev, (size_t)capacity * ni * 4);
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
 }  // extern "C"

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -513,4 +513,33 @@ int launch_sosfilt(Ctx* c, const IirLaunch& a);
 // backward, the middle slice to y (dense [batch][n])
 int launch_sosfiltfilt(Ctx* c, const float* x, int64_t n, int64_t x_stride, int32_t batch, const double* sos_host, int32_t n_sections,
                        int32_t padtype, int64_t edge, float* y);
+}  // namespace nxsig
+
+#include "find_peaks_plan.hpp"
+
+namespace nxsig {
+// kernels_find_peaks.hip: PeakFinding.find_peaks over a device tensor (include/nxsig.h states the rules, DESIGN.md section 3.14 the
+// design; the argument checks are the caller's).  The mask words live in kScratchPeakTiles, the line summary and the survivors' positions
+// in kScratchPeakExtremes: find_peaks and argrelextrema never overlap on one stream.  A call with a distance condition waits once per
+// round of the distance stage; every other call only enqueues on c->stream
+struct FindPeaksLaunch {
+  const void* x;           // device f32, or f64 when f64
+  bool f64;
+  const int64_t* shape;
+  int32_t rank, axis;
+  uint32_t conditions;     // FindPeaksCondition bits
+  const double* bounds;    // host f64[5][2] or nullptr
+  double distance;
+  int64_t wlen;            // -1: none
+  double rel_height;
+  int64_t capacity;
+  uint32_t want;           // FindPeaksProperty bits
+  int32_t* indices;        // device s32[capacity][rank]
+  uint32_t* valid;         // device
+  double* fprops;          // device f64[f64 rows wanted][capacity]
+  int32_t* iprops;         // device s32[s32 rows wanted][capacity], or nullptr: the launcher keeps them in its scratch ...
+  int32_t** iprops_used;   // ... and says where (may be nullptr)
+};
+int launch_find_peaks(Ctx* c, const FindPeaksLaunch& a);
+int32_t find_peaks_last_rounds();   // rounds of the distance stage in the calling thread's last launch_find_peaks
 }  // namespace nxsig

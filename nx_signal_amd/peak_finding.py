@@ -1,6 +1,7 @@
 """NxSignal.PeakFinding: argrelmin/2, argrelmax/2, argrelextrema/3 (lib/nx_signal/peak_finding.ex) on the kernels of DESIGN.md
 section 3.9.  Each returns {"indices": s32 (size, rank), "valid_indices": u32 scalar}: the coordinates of the marked elements in
-row-major order, then -1 rows."""
+row-major order, then -1 rows.  find_peaks (an extension: scipy.signal.find_peaks on every line along an axis)
+returns the same pair for the surviving peaks and a dict of their properties; trim cuts both to valid_indices on the host."""
 from __future__ import annotations
 
 import ctypes as C
@@ -136,3 +137,7 @@ def argrelmax(data, ctx=None, **opts):
     """PeakFinding.argrelmax/2: argrelextrema(data, "greater", ...)"""
     axis, order = _axis_order(opts, "argrelmax")
     return _fused(data, "greater", ctx, axis, order, "argrelmax")
+
+
+# find_peaks / trim live in a module of their own (_find_peaks.py) and are part of this one's interface
+from ._find_peaks import find_peaks, trim  # noqa: E402,F401

@@ -5,6 +5,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --own [--real] [--write tests/golden/abi_error_table_resample.json]
     python tools/abi_error_probe.py --welch [--real] [--write tests/golden/abi_error_table_welch.json]
     python tools/abi_error_probe.py --iir [--real] [--write tests/golden/abi_error_table_iir.json]
+    python tools/abi_error_probe.py --peaks [--real] [--write tests/golden/abi_error_table_find_peaks.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -16,7 +17,8 @@ ENTRIES and that golden file are the recorded table of the entry points that exi
 keeps its rows in OWN_TABLE_ENTRIES and a golden file of its own (--own; tests/test_resample_host.py and tests/test_gpu_resample.py
 compare against it): the same probe, the same kinds of cases.  WELCH_TABLE_ENTRIES (--welch) does the same for nxsig_welch_f32 and
 nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py), IIR_TABLE_ENTRIES (--iir) for nxsig_sosfilt_f32 and
-nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py)."""
+nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TABLE_ENTRIES (--peaks) for nxsig_find_peaks
+(tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py)."""
 import argparse
 import ctypes as C
 import json
@@ -34,6 +36,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_error_table.json")
 GOLDEN_OWN = os.path.join(ROOT, "tests", "golden", "abi_error_table_resample.json")
 GOLDEN_WELCH = os.path.join(ROOT, "tests", "golden", "abi_error_table_welch.json")
 GOLDEN_IIR = os.path.join(ROOT, "tests", "golden", "abi_error_table_iir.json")
+GOLDEN_PEAKS = os.path.join(ROOT, "tests", "golden", "abi_error_table_find_peaks.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -308,6 +311,25 @@ IIR_TABLE_ENTRIES = [
                    ("pole at z=1", {"sos": _IIR_POLE1})]),
 ]
 
+# PeakFinding.find_peaks: the 8 samples of the argrelextrema row under height >= 1, distance 2, prominence >= 0.5 and width >= 0 (bounds is
+# a host array whatever `mem` says); wanted are peak_heights, prominences, the four width arrays and the two bases: 6 f64 and 2 s32 rows
+_FP_BOUNDS = np.array([[-np.inf, np.inf], [1.0, np.inf], [-np.inf, np.inf], [0.5, np.inf], [0.0, np.inf]], np.float64)
+_FP_NAN_BOUNDS = _FP_BOUNDS.copy()
+_FP_NAN_BOUNDS[3, 1] = np.nan
+_FP_WANT = 0b1111111001
+PEAKS_TABLE_ENTRIES = [
+    ("nxsig_find_peaks",
+     [("x", "in", _X8), ("dtype", "v", _lib.DT_F32), ("shape", "host", _i64(8)), ("rank", "v", 1), ("axis", "v", 0), ("bounds", "host", _FP_BOUNDS),
+      ("conditions", "v", 2 | 8 | 16 | 32), ("distance", "v", 2.0), ("wlen", "v", -1), ("rel_height", "v", 0.5), ("capacity", "v", 3),
+      ("want", "v", _FP_WANT), ("indices", "out", np.zeros((3, 1), np.int32)), ("valid", "out", np.zeros(1, np.uint32)),
+      ("fprops", "out", np.zeros((6, 3), np.float64)), ("iprops", "out", np.zeros((2, 3), np.int32)), ("mem", "mem", None)],
+     _PEAK_SHAPE_CASES + [("axis=1", {"axis": 1}), ("axis=-1", {"axis": -1}), ("dtype=2", {"dtype": _lib.DT_S32}), ("dtype=9", {"dtype": 9}),
+                          ("distance=0.5", {"distance": 0.5}), ("distance=nan", {"distance": float("nan")}), ("wlen=1", {"wlen": 1}),
+                          ("wlen=0", {"wlen": 0}), ("rel_height=-1", {"rel_height": -1.0}), ("rel_height=nan", {"rel_height": float("nan")}),
+                          ("conditions=64", {"conditions": 64}), ("want=8192", {"want": 8192}), ("capacity=4", {"capacity": 4}),
+                          ("capacity=-1", {"capacity": -1}), ("a border is nan", {"bounds": _FP_NAN_BOUNDS})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -421,9 +443,10 @@ def main():
     ap.add_argument("--own", action="store_true", help="the entry points of OWN_TABLE_ENTRIES instead of the recorded table's")
     ap.add_argument("--welch", action="store_true", help="the entry points of WELCH_TABLE_ENTRIES (Spectral.welch / csd)")
     ap.add_argument("--iir", action="store_true", help="the entry points of IIR_TABLE_ENTRIES (Filters.sosfilt / sosfiltfilt)")
+    ap.add_argument("--peaks", action="store_true", help="the entry point of PEAKS_TABLE_ENTRIES (PeakFinding.find_peaks)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
