@@ -101,7 +101,9 @@ void nxsig_ctx_destroy(nxsig_ctx* ctx);
 /* Dispatch / geometry switches of ONE context ("Switches").  nxsig_ctx_create reads the NXSIG_<NAME> variables of
  * the process environment once; after that no call looks at the environment — a launch only reads the context's switches, and
  * these three functions change them at run time (A/B sweeps, tests).  `name` is "NXSIG_FOO" or "FOO"; unknown names are
- * NXSIG_ERR_INVALID_ARG.  clear(name = NULL) returns every switch to the launchers' defaults. */
+ * NXSIG_ERR_INVALID_ARG.  clear(name = NULL) returns every switch to the launchers' defaults.  get alone also answers the read-only
+ * name "TABLE_REQUESTS": how often this context was asked for a cached device table so far, modulo 2^31 (is_set = 0) — a call served
+ * from a memo of table pointers asks for none, which is how the tests see that it formed nothing again. */
 int nxsig_ctx_set_tuning(nxsig_ctx* ctx, const char* name, int32_t value);
 int nxsig_ctx_get_tuning(nxsig_ctx* ctx, const char* name, int32_t* value, int32_t* is_set);
 int nxsig_ctx_clear_tuning(nxsig_ctx* ctx, const char* name);
@@ -794,6 +796,51 @@ int32_t nxsig_find_peaks_rounds(void);
 int nxsig_find_peaks(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t* shape, int32_t rank, int32_t axis, const double* bounds,
                      uint32_t conditions, double distance, int64_t wlen, double rel_height, int64_t capacity, uint32_t want,
                      int32_t* indices, uint32_t* valid, double* fprops, int32_t* iprops, int32_t mem);
+
+/*
+ * Filters.savgol_filter / savgol_coeffs — scipy.signal 1.15's Savitzky-Golay smoothing and smoothed derivatives over real f32 or f64
+ * rows (the reference has neither).  THE DEFINITION: with W = window_length, h = W / 2 (rounded down), L = h for
+ * an odd W and h - 1 for an even one, k[0 .. W) the correlation weights (nxsig_savgol_coeffs with pos = -1 and NXSIG_SAVGOL_DOT) and
+ * ext(i) the row extended by `mode`,
+ *     y[i] = sum over j = 0 .. W - 1 of k[j] * ext(i - L + j)
+ *   NXSIG_SAVGOL_MIRROR    period 2 (n - 1), the edge sample not repeated; n = 1 gives the sample itself
+ *   NXSIG_SAVGOL_NEAREST   the index clamped to [0, n - 1]
+ *   NXSIG_SAVGOL_WRAP      the index modulo n
+ *   NXSIG_SAVGOL_CONSTANT  cval outside the row
+ *   NXSIG_SAVGOL_INTERP    zero outside the row; then y[0 .. h) and y[n - h .. n) are replaced by the deriv-th derivative, divided by
+ *                          delta^deriv, of the degree-polyorder least-squares polynomial through the first / last W samples, evaluated
+ *                          at those positions: a fixed linear map E[h][W], y[i] = sum_j E[i][j] x[j] and
+ *                          y[n - 1 - i] = (-1)^deriv sum_j E[i][j] x[n - 1 - j].  Needs W <= n; the other modes take any n >= 1.
+ * Weights: k[j] is the weight of window sample j in the deriv-th derivative at window position pos (default: the centre, h for an odd
+ * W, h - 0.5 for an even one) of the least-squares polynomial of degree polyorder through W samples `delta` apart.  THEY ARE THE EXACT
+ * LEAST-SQUARES WEIGHTS ROUNDED TO DOUBLE, NOT SCIPY'S: each lies within 1e-12 max|k| of the rational solution (formed in long double on
+ * the polynomials orthogonal over the window); scipy's lstsq on the uncentred Vandermonde matrix loses digits as W grows (4.5e-6 at
+ * W = 512, polyorder 7, deriv 3).  At the default pos an even (odd) derivative has exactly symmetric (antisymmetric) weights and an odd
+ * derivative over an odd window a centre weight of exactly zero.  deriv > polyorder gives all-zero weights.  NXSIG_SAVGOL_CONV returns
+ * them reversed (scipy's default order).
+ * Limits: 1 <= W <= 1025, polyorder < W, polyorder <= 15 (beyond: NXSIG_ERR_UNSUPPORTED), deriv >= 0, delta finite and non-zero, cval
+ * finite.  x [batch][length] rows batch_stride >= length elements apart, f32 (is_f64 = 0) or f64 (1); y the same type, dense
+ * [batch][length]; x and y must not overlap.
+ * Arithmetic: every sample is widened to double; the sum is ONE chain acc = fma(k[j], ext(i - L + j), acc) from acc = 0 in ascending j,
+ * every weight included, zero ones too; an edge output of INTERP the same chain over E[i][j] in ascending j (the sign applied last); the
+ * result is rounded to the row type once.  Both dispatch families follow it, so they return the same bits: savgol.tiles (a workgroup per
+ * tile of nxsig_savgol_tile() outputs, samples in LDS) and savgol.generic (one lane per output; rows shorter than one tile and
+ * everything under NXSIG_DISABLE_SAVGOL_TILES).  No atomics; a row's bits do not depend on the batch.
+ * Non-finite rule: an output is non-finite exactly when its window, after extension, covers an Inf / NaN sample (under WRAP and MIRROR
+ * that includes the samples the extension brings in); under INTERP all h edge outputs of a side are non-finite when the first / last W
+ * samples hold one.  Which of NaN / Inf comes out is not specified.  Other outputs and other rows keep their bits.
+ * Every argument check comes ahead of the context; a device call returns without waiting (the first call of a parameter set on a
+ * context forms and uploads its tables).
+ */
+typedef enum nxsig_savgol_mode { NXSIG_SAVGOL_MIRROR = 0, NXSIG_SAVGOL_CONSTANT = 1, NXSIG_SAVGOL_NEAREST = 2, NXSIG_SAVGOL_WRAP = 3,
+                                 NXSIG_SAVGOL_INTERP = 4 } nxsig_savgol_mode;
+typedef enum nxsig_savgol_use { NXSIG_SAVGOL_CONV = 0, NXSIG_SAVGOL_DOT = 1 } nxsig_savgol_use;
+/* outputs per workgroup tile of savgol.tiles */
+int32_t nxsig_savgol_tile(void);
+/* out: f64[window_length]; pos = -1: the default; host only */
+int nxsig_savgol_coeffs(int32_t window_length, int32_t polyorder, int32_t deriv, double delta, double pos, int32_t use, double* out);
+int nxsig_savgol_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, int64_t length, int32_t batch, int64_t batch_stride,
+                        int32_t window_length, int32_t polyorder, int32_t deriv, double delta, int32_t mode, double cval, void* y, int32_t mem);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,9 @@ SIGNATURES = {
     "nxsig_find_peaks_rounds": (_i32, []),
     "nxsig_find_peaks": (C.c_int, [_ctx_peaks, _p, _i32, C.POINTER(_i64), _i32, _i32, C.POINTER(_f64), C.c_uint32, _f64, _i64, _f64, _i64,
                                    C.c_uint32, _p, _p, _p, _p, _i32]),
+    "nxsig_savgol_tile": (_i32, []),
+    "nxsig_savgol_coeffs": (C.c_int, [_i32, _i32, _i32, _f64, _f64, _i32, C.POINTER(_f64)]),
+    "nxsig_savgol_filter": (C.c_int, [_ctx_iir, _p, _i32, _i64, _i32, _i64, _i32, _i32, _i32, _f64, _i32, _f64, _p, _i32]),
     "nxsig_sawtooth": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _i32]),
     "nxsig_square": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _p, _i32]),
     "nxsig_gaussian_pulse": (C.c_int, [_p, _p, _i32, _i64, _f64, _f64, _f64, _p, _p, _p, _i32]),

@@ -56,6 +56,7 @@ UNITS = [
     ("kernels_welch.hip", []),  # Spectral.welch / csd: Welch's averaged periodogram, the spectrum never in memory
     ("kernels_iir.hip", []),  # Filters.sosfilt / sosfiltfilt: biquad cascades in double, an exact scan over time
     ("kernels_find_peaks.hip", []),  # PeakFinding.find_peaks: line summary, walks, distance rounds (no FMA contraction: the file says so itself)
+    ("kernels_savgol.hip", []),  # Filters.savgol_filter: Savitzky-Golay smoothing and derivatives, double sums over an LDS tile
 ]
 
 

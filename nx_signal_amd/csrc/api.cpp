@@ -132,7 +132,7 @@ int ctx_table(Ctx* c, uint64_t tag, const void* host, size_t bytes, const void**
   // content-addressed: key = fnv1a(tag, content) ^ size.  A hit on a table of up to 1 MiB is VERIFIED against the kept host copy
   // (size + content): on a 64-bit collision the next key is probed instead of silently handing out another table (a wrong
   // window / filter).  Larger tables keep no host copy and are matched on hash + size only.
-  uint64_t key = fnv1a(tag, host, bytes) ^ (uint64_t)bytes;
+  uint64_t key = fnv1a(tag, host, bytes) ^ (uint64_t)bytes; ++c->table_requests;
   for (int probe = 0; probe < 8; ++probe, key = key * 0x9E3779B97F4A7C15ull + 1) {
     auto it = c->tables.find(key);
     if (it == c->tables.end()) {
@@ -1187,7 +1187,7 @@ int nxsig_ctx_set_tuning(nxsig_ctx* ctx, const char* name, int32_t value) {
 int nxsig_ctx_get_tuning(nxsig_ctx* ctx, const char* name, int32_t* value, int32_t* is_set) {
   NXSIG_API_BEGIN
   NXSIG_CHECK_CTX(ctx)
-  const int k = tuning_index(name);
+  const int k = tuning_index(name); if (k < 0 && table_requests_query(c, name, value, is_set)) return NXSIG_OK;   // the read-only name
   if (k < 0) return set_error(NXSIG_ERR_INVALID_ARG, std::string("no such switch: ") + (name ? name : "(null)"));
   if (value) *value = c->tuning.v[k];
   if (is_set) *is_set = c->tuning.set[k] ? 1 : 0;
@@ -2506,4 +2506,63 @@ int nxsig_find_peaks(nxsig_ctx* ctx, const void* x, int32_t dtype, const int64_t
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Filters.savgol_filter / savgol_coeffs */
+int32_t nxsig_savgol_tile(void) { return kSavgolTile; }
+
+static int savgol_check_common(const char* fn, int32_t window_length, int32_t polyorder, int32_t deriv, double delta) {
+  bool unsupported = false;
+  if (const char* what = savgol_check_design(window_length, polyorder, deriv, delta, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string(fn) + ": " + what);
+  return NXSIG_OK;
+}
+
+int nxsig_savgol_coeffs(int32_t window_length, int32_t polyorder, int32_t deriv, double delta, double pos, int32_t use, double* out) {
+  NXSIG_API_BEGIN
+  if (!out) return set_error(NXSIG_ERR_INVALID_ARG, "savgol_coeffs: null pointer argument");
+  int rc = savgol_check_common("savgol_coeffs", window_length, polyorder, deriv, delta);
+  if (rc) return rc;
+  if (pos != -1.0 && !(pos >= 0.0 && pos < (double)window_length))
+    return set_error(NXSIG_ERR_INVALID_ARG, "savgol_coeffs: pos must be nonnegative and less than window_length.");
+  if (use != kSgConv && use != kSgDot) return set_error(NXSIG_ERR_INVALID_ARG, "savgol_coeffs: `use` must be 'conv' or 'dot'.");
+  savgol_coeffs(window_length, polyorder, deriv, delta, pos, use, out);
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
+int nxsig_savgol_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, int64_t length, int32_t batch, int64_t batch_stride, int32_t window_length,
+                        int32_t polyorder, int32_t deriv, double delta, int32_t mode, double cval, void* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !y) return set_error(NXSIG_ERR_INVALID_ARG, "savgol_filter: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  if (is_f64 != 0 && is_f64 != 1) return set_error(NXSIG_ERR_INVALID_ARG, "savgol_filter: is_f64 must be 0 or 1");
+  if ((rc = savgol_check_common("savgol_filter", window_length, polyorder, deriv, delta))) return rc;
+  if (const char* what = savgol_check_rows(window_length, mode, cval, length, batch, batch_stride))
+    return set_error(NXSIG_ERR_INVALID_ARG, std::string("savgol_filter: ") + what);
+  if (batch_stride > INT64_MAX / batch / 16) return set_error(NXSIG_ERR_UNSUPPORTED, "savgol_filter: the rows are too large");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  const size_t es = is_f64 ? sizeof(double) : sizeof(float);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, es), kScratchNdStageA}},
+                    {{y, (size_t)batch * length * es, kScratchNdStageOut}}))) return rc;
+  SavgolLaunch a;
+  a.x = io.in[0]; a.f64 = is_f64 != 0; a.n = length; a.x_stride = batch_stride; a.batch = batch;
+  a.W = window_length; a.p = polyorder; a.deriv = deriv; a.delta = delta; a.mode = mode; a.cval = cval;
+  a.y = io.out[0];
+  if ((rc = launch_savgol(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"
+
+namespace nxsig {
+bool table_requests_query(const Ctx* c, const char* name, int32_t* value, int32_t* is_set) {
+  if (!name || (std::strcmp(name, "TABLE_REQUESTS") != 0 && std::strcmp(name, "NXSIG_TABLE_REQUESTS") != 0)) return false;
+  if (value) *value = (int32_t)(c->table_requests & 0x7fffffff);
+  if (is_set) *is_set = 0;
+  return true;
+}
+}  // namespace nxsig

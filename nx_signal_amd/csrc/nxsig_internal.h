@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -174,7 +174,7 @@ struct Ctx {
   // twiddle tables w_K^j = exp(-2 pi i j / K), j in [0,K), generated in double, stored as float2
   std::map<int, DeviceTable> twiddles;
   // content-addressed small tables (windows, filter spectra ...): key = fnv1a(tag, bytes)
-  std::map<uint64_t, DeviceTable> tables;
+  std::map<uint64_t, DeviceTable> tables; uint64_t table_requests = 0;   // ... and the calls of ctx_table so far ("TABLE_REQUESTS")
   // f64 tier (kernels_f64.hip): device pointers of its twiddle / chirp tables by (kind << 32 | length); the storage belongs to `tables`
   std::map<int64_t, const void*> f64_tables;
   // device scratch buffers reused from call to call, one per ScratchSlot (the enum names every slot and its owner); grown on demand
@@ -542,4 +542,31 @@ struct FindPeaksLaunch {
 };
 int launch_find_peaks(Ctx* c, const FindPeaksLaunch& a);
 int32_t find_peaks_last_rounds();   // rounds of the distance stage in the calling thread's last launch_find_peaks
+}  // namespace nxsig
+
+#include "savgol_plan.hpp"
+
+namespace nxsig {
+// kernels_savgol.hip: Filters.savgol_filter over device rows (include/nxsig.h states the definition, DESIGN.md section 3.15 the design;
+// the argument checks are the caller's).  The weights and the edge table of mode "interp" are cached tables of the context, formed once
+// per parameter set.  No scratch; everything is enqueued on c->stream and nothing waits (the first call of a parameter set uploads)
+struct SavgolLaunch {
+  const void* x;           // device f32, or f64 when f64: [batch][n], rows x_stride elements apart
+  bool f64;
+  int64_t n, x_stride;
+  int32_t batch;
+  int32_t W, p, deriv;     // window_length, polyorder, deriv
+  double delta;
+  int32_t mode;            // SavgolMode
+  double cval;
+  void* y;                 // device, dense [batch][n]
+};
+int launch_savgol(Ctx* c, const SavgolLaunch& a);
+}  // namespace nxsig
+
+namespace nxsig {
+// nxsig_ctx_get_tuning's read-only name "TABLE_REQUESTS" (or "NXSIG_TABLE_REQUESTS"): how often ctx_table was called on the context,
+// modulo 2^31, is_set = 0.  A call served from a memo of table pointers makes no request, which is how the tests see that a repeated
+// call formed nothing again.  False for any other name (api.cpp)
+bool table_requests_query(const Ctx* c, const char* name, int32_t* value, int32_t* is_set);
 }  // namespace nxsig

@@ -311,3 +311,7 @@ def sosfiltfilt(x, sos, ctx=None, axis=-1, padtype="odd", padlen=None):
     _lib.check(_lib.load().nxsig_sosfiltfilt_f32(_lib.ctx_ptr(c.handle, _lib._ctx_iir), x.ptr, n, batch, n, ptr(s), s.shape[0],
                                                  _SOS_PADTYPES[padtype], edge, ptr(out), x.mem))
     return out if x.device else np.ascontiguousarray(np.moveaxis(out, -1, axis))
+
+
+# savgol_filter / savgol_coeffs live in a module of their own (_savgol.py) and are part of this one's interface
+from ._savgol import savgol_coeffs, savgol_filter  # noqa: E402,F401

@@ -6,6 +6,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --welch [--real] [--write tests/golden/abi_error_table_welch.json]
     python tools/abi_error_probe.py --iir [--real] [--write tests/golden/abi_error_table_iir.json]
     python tools/abi_error_probe.py --peaks [--real] [--write tests/golden/abi_error_table_find_peaks.json]
+    python tools/abi_error_probe.py --savgol [--real] [--write tests/golden/abi_error_table_savgol.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -18,7 +19,8 @@ keeps its rows in OWN_TABLE_ENTRIES and a golden file of its own (--own; tests/t
 compare against it): the same probe, the same kinds of cases.  WELCH_TABLE_ENTRIES (--welch) does the same for nxsig_welch_f32 and
 nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py), IIR_TABLE_ENTRIES (--iir) for nxsig_sosfilt_f32 and
 nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TABLE_ENTRIES (--peaks) for nxsig_find_peaks
-(tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py)."""
+(tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py), SAVGOL_TABLE_ENTRIES (--savgol) for nxsig_savgol_filter
+(tests/test_savgol_host.py, tests/test_gpu_savgol.py)."""
 import argparse
 import ctypes as C
 import json
@@ -37,6 +39,7 @@ GOLDEN_OWN = os.path.join(ROOT, "tests", "golden", "abi_error_table_resample.jso
 GOLDEN_WELCH = os.path.join(ROOT, "tests", "golden", "abi_error_table_welch.json")
 GOLDEN_IIR = os.path.join(ROOT, "tests", "golden", "abi_error_table_iir.json")
 GOLDEN_PEAKS = os.path.join(ROOT, "tests", "golden", "abi_error_table_find_peaks.json")
+GOLDEN_SAVGOL = os.path.join(ROOT, "tests", "golden", "abi_error_table_savgol.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -330,6 +333,21 @@ PEAKS_TABLE_ENTRIES = [
                           ("capacity=-1", {"capacity": -1}), ("a border is nan", {"bounds": _FP_NAN_BOUNDS})]),
 ]
 
+# Filters.savgol_filter: 2 rows of 24 samples, a window of 7 and a cubic, first derivative, mode interp (4)
+SL = 24
+SAVGOL_TABLE_ENTRIES = [
+    ("nxsig_savgol_filter",
+     [("x", "in", _f32(B, SL)), ("is_f64", "v", 0), ("length", "v", SL), ("batch", "v", B), ("batch_stride", "v", SL), ("window_length", "v", 7),
+      ("polyorder", "v", 3), ("deriv", "v", 1), ("delta", "v", 0.5), ("mode", "v", 4), ("cval", "v", 0.0), ("y", "out", np.zeros((B, SL), np.float32)),
+      ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": SL - 1}), ("is_f64=2", {"is_f64": 2}),
+      ("window_length=0", {"window_length": 0}), ("window_length=1027", {"window_length": 1027, "polyorder": 3}),
+      ("polyorder=window_length", {"polyorder": 7}), ("polyorder=-1", {"polyorder": -1}), ("polyorder=16", {"polyorder": 16, "window_length": 23}),
+      ("deriv=-1", {"deriv": -1}), ("delta=0", {"delta": 0.0}), ("delta=nan", {"delta": float("nan")}), ("delta=inf", {"delta": float("inf")}),
+      ("mode=5", {"mode": 5}), ("mode=-1", {"mode": -1}), ("cval=nan", {"cval": float("nan"), "mode": 1}), ("cval=inf", {"cval": float("inf")}),
+      ("interp window > length", {"window_length": 25}), ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -444,9 +462,10 @@ def main():
     ap.add_argument("--welch", action="store_true", help="the entry points of WELCH_TABLE_ENTRIES (Spectral.welch / csd)")
     ap.add_argument("--iir", action="store_true", help="the entry points of IIR_TABLE_ENTRIES (Filters.sosfilt / sosfiltfilt)")
     ap.add_argument("--peaks", action="store_true", help="the entry point of PEAKS_TABLE_ENTRIES (PeakFinding.find_peaks)")
+    ap.add_argument("--savgol", action="store_true", help="the entry point of SAVGOL_TABLE_ENTRIES (Filters.savgol_filter)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
