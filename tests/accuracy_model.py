@@ -22,9 +22,13 @@ tests/test_gpu_frame_accuracy.py share:
 * `REACH`: how many consecutive frames of a row can share one complex transform in every dispatch family, read off the kernels.
 * the mixed-level inputs of the isolation tests and numpy stand-ins for a kernel (textbook radix-2 in f32, its pair-packed form, and
   degraded variants) that show the metric bites.
+* the long rows of kernels_nd.hip (FFT_ROWS_LONG and the tables beside it): `fourstep_f32`, a four-step split like the kernel's with
+  its two-level twiddle table, the table re-seeded recurrence of pass A and degraded forms of it; `bluestein_f32`, the chirp-z chain in
+  single precision (the floor of fft.big.blue's algorithm, part of that family's model); `long_impulse_rows`.
 
 The margin of every test is 3 x the model's figure on the same data and statistic: correct f32 FFTs of different factorisation and
-packing lie within 1.2 x of each other, an f32 Bluestein built from scipy's transforms at 1.0-1.7 x of the direct transform, the
+packing lie within 1.2 x of each other, an f32 Bluestein built from scipy's transforms at 1.0-1.7 x of the direct transform (0.6-1.9 x at the
+lengths of fft.big.blue, where pocketfft's own transform of a prime length is the less accurate of the two), the
 sloppy variants at 2.2 x and above (tests/test_accuracy_model_host.py measures them)."""
 import os
 
@@ -77,6 +81,18 @@ REACH = {
     # ---- rows (the reference itself transforms a row once: no frame-level reach inside a row, none across rows)
     "fft.rows_wave": 1,        # kernels_wave_rows.hip:275 (one wave per row)
     "fft.rows_generic": 1,     # kernels_generic.hip:1420, :1438
+    # ---- rows, columns and frames beyond the LDS-resident kernels: the unit is always ONE row / column / frame
+    "fft.tiled": 1,            # kernels_nd.hip:287-289 (a tile is T columns of ONE batch row, sequence t in its own LDS lane p * TP + t), :474
+    "fft.tiled.columns": 1,    # kernels_nd.hip:502-504 (sequences = the `inner` columns of one plane, one pass of k_fft_tile)
+    "fft.big.blue": 1,         # kernels_nd.hip:553-559 (row r is its own P-point chirp-z convolution A[r][.], k_blue_in :134)
+    "fft.transpose": 1,        # kernels_nd.hip:236-244 (the five-pass four-step: rows * K2 transforms of K1 points, then rows * K1 of K2)
+    "stft.big": 1,             # kernels_nd.hip:1061-1062 (every windowed frame is a row of launch_fft_big)
+    "fir.long": 1,             # kernels_nd.hip:749-765 through api.cpp:307-308 (one launch_fftconvolve_nd per row)
+    "fftconvolve_nd": 1,       # kernels_nd.hip:749-765 (fft_nd of each operand, product, ifft_nd: a fold of row / column transforms)
+    # sinks of the two-frames-per-transform front-ends: the unit is the front-end's
+    "mag.r20": 2,              # kernels_wave_r20.hip:6-7, :376 (the r20 front-end feeding the magnitude / one-sided sink)
+    "mag.rab": 2,              # wave_rab.hpp:14, :536
+    "mag.blue": 2,             # wave_stft.hpp:1193-1194, :1817
 }
 
 _SUFFIXES = ("", ".1r", ".edge", ".1r.edge", ".deep", ".h4")
@@ -444,6 +460,123 @@ def stft_pair_packed_f32(fr, stride=1, across_rows=False, twiddles="exact"):
     return out.reshape(rows, M, K)
 
 
+def next_pow2(n):
+    return 1 << max(0, int(n) - 1).bit_length()
+
+
+def _pad_rows(x, K):
+    """rows of n_in samples as c64 rows of K (zero-padded / truncated, like a transform of length K)"""
+    x = np.asarray(x).astype(c64)
+    out = np.zeros(x.shape[:-1] + (K,), c64)
+    n = min(K, x.shape[-1])
+    out[..., :n] = x[..., :n]
+    return out
+
+
+def bluestein_f32(x, K, inverse=False):
+    """the chirp-z chain of fft.big.blue through scipy.fft on complex64: the floor of the ALGORITHM in single precision.  The chirp
+    exp(-i pi n^2 / K) from the exact phase index (n n) mod 2K, evaluated in double and rounded to c64; the spectrum of its conjugate
+    formed in double and rounded once (kernels_nd.hip:528-537); two P-point transforms, P the power of two >= 2K - 1.  x [..., n_in]"""
+    n = np.arange(K, dtype=np.int64)
+    ang = -np.pi * ((n * n) % (2 * K)).astype(f64) / K
+    chirp = np.exp(1j * ang).astype(c64)
+    P = next_pow2(2 * K - 1)
+    b = np.zeros(P, c128)
+    b[:K] = np.exp(-1j * ang)
+    b[P - K + 1:] = b[1:K][::-1]
+    Bf = np.fft.fft(b).astype(c64)
+    u = _pad_rows(x, K)
+    if inverse:
+        u = np.conj(u)
+    a = np.zeros(u.shape[:-1] + (P,), c64)
+    a[..., :K] = u * chirp
+    A = scipy.fft.fft(a, axis=-1)
+    assert A.dtype == c64
+    v = scipy.fft.ifft((A * Bf).astype(c64), axis=-1)
+    assert v.dtype == c64
+    z = (v[..., :K] * chirp).astype(c64)
+    if inverse:
+        z = (np.conj(z) / f32(K)).astype(c64)
+    return z
+
+
+def _fourstep_twiddles(lg, twiddles, reseed):
+    """c64 [K1, K2]: w_K^(k1 n2) as pass A of the four-step applies it (kernels_nd.hip:402-426).
+    "table": tw_hi[j >> 13] * tw_lo[j & 8191] in c64 at every element (:181-182, :420)
+    "recurrence": w[k1] = w[k1 - 1] * w[1] in c64 along k1, taken from the table product where k1 % reseed == 0 (reseed None: only k1 = 0)
+    "f32angle": cos / sin of the angle -2 pi j / K formed in f32"""
+    K = 1 << lg
+    K1 = 1 << ((lg + 1) // 2)
+    K2 = K // K1
+    j = np.arange(K1, dtype=np.int64)[:, None] * np.arange(K2, dtype=np.int64)[None, :]      # < K
+    if twiddles == "f32angle":
+        a = (f32(-2.0) * f32(np.pi) * j.astype(f32) / f32(K)).astype(f32)
+        return (np.cos(a.astype(f64)) + 1j * np.sin(a.astype(f64))).astype(c64)
+    t = np.arange(8192)
+    lo = np.exp(-2j * np.pi * (t % K) / K).astype(c64)
+    hi = np.exp(-2j * np.pi * ((np.arange((K + 8191) // 8192) * 8192) % K) / K).astype(c64)
+    table = (hi[j >> 13] * lo[j & 8191]).astype(c64)
+    if twiddles == "table":
+        return table
+    assert twiddles == "recurrence", twiddles
+    w = np.empty_like(table)
+    for k1 in range(K1):
+        w[k1] = table[k1] if (k1 == 0 or (reseed and k1 % reseed == 0)) else (w[k1 - 1] * table[1]).astype(c64)
+    return w
+
+
+def fourstep_f32(x, lg, reseed=8, twiddles="recurrence"):
+    """a forward transform of 2^lg points split like fft.tiled (K1 = 2^ceil(lg / 2) points down the columns n2, the twiddle
+    w_K^(n2 k1), K2 points along the rows k1, X[k1 + K1 k2]) with scipy's complex64 sub-transforms: only the twiddle differs
+    between the forms, see _fourstep_twiddles.  x c64 [..., 2^lg]"""
+    x = np.asarray(x).astype(c64)
+    K = 1 << lg
+    K1 = 1 << ((lg + 1) // 2)
+    K2 = K // K1
+    assert x.shape[-1] == K
+    y = scipy.fft.fft(x.reshape(x.shape[:-1] + (K1, K2)), axis=-2)             # [k1, n2]
+    y = (y * _fourstep_twiddles(lg, twiddles, reseed)).astype(c64)
+    z = scipy.fft.fft(y, axis=-1)                                              # [k1, k2]
+    assert z.dtype == c64
+    return np.ascontiguousarray(np.swapaxes(z, -1, -2)).reshape(x.shape)
+
+
+def long_impulse_positions(K, count, seed=0):
+    """1, K2 - 1, K2 + 1, K / 2 + 1, K - 1 (K2 = 2^floor(log2 K / 2): the row length of the four-step view), then seeded random ones.
+    n mod K2 is the column of pass A: at K2 - 1 and K - 1 the twiddle recurrence walks at its longest stride"""
+    K2 = 1 << ((int(K).bit_length() - 1) // 2)
+    fixed = [1, K2 - 1, K2 + 1, K // 2 + 1, K - 1]
+    rng = np.random.default_rng(seed)
+    return np.array((fixed + [int(v) for v in rng.integers(0, K, max(0, count - len(fixed)))])[:count], dtype=np.int64)
+
+
+def long_impulse_rows(K, rows, seed=0):
+    """c64 [rows, K]: one unit impulse per row, row r at long_impulse_positions(K, rows, seed)[r] — every output bin is one chain of
+    twiddles of magnitude 1, so the max norm is a per-bin figure"""
+    x = np.zeros((rows, K), c64)
+    x[np.arange(rows), long_impulse_positions(K, rows, seed)] = 1.0
+    return x
+
+
+def fft_rows_reference(x, K, inverse):
+    """c128 [rows, K]: np.fft in double on the rows zero-padded to K, with Nx.fft's clean-up"""
+    xd = np.asarray(x).astype(c64).astype(c128)
+    return clean(np.fft.ifft(xd, n=K, axis=-1) if inverse else np.fft.fft(xd, n=K, axis=-1))
+
+
+def fft_rows_model_errors(x, K, inverse, ref, family):
+    """(max, l2) of the model, worst row.  The direct complex64 transform; for fft.big.blue the larger, per statistic, of that and the
+    single-precision chirp-z chain (bluestein_f32), the floor of the algorithm the family is built on"""
+    x = np.asarray(x).astype(c64)
+    direct = clean(scipy.fft.ifft(x, n=K, axis=-1) if inverse else scipy.fft.fft(x, n=K, axis=-1))
+    assert direct.dtype == c64
+    m = worst(row_errors(direct, ref))
+    if family == "fft.big.blue":
+        b = worst(row_errors(clean(bluestein_f32(x, K, inverse)), ref))
+        m = (max(m[0], b[0]), max(m[1], b[1]))
+    return m
+
+
 # ------------------------------------------------------------------------------------------------ cases shared by the two GPU modules
 # the three launch geometries of tests/test_gpu_stft_pair_loop.py: HOP4 and the general loop both run
 PAIR_GEOMETRIES = {
@@ -484,7 +617,12 @@ FORWARD_EXTRA = {
     "pair-onesided": (1024, 256, "mag.pair", {"sink": "onesided", "M": 45}),
     "quad2-magnitude": (512, 128, "mag.quad2", {"sink": "magnitude"}),
     "quad2-onesided": (512, 128, "mag.quad2", {"sink": "onesided"}),
+    "r20-magnitude": (400, 100, "mag.r20", {"sink": "magnitude"}),
+    "rab960-onesided": (960, 240, "mag.rab", {"sink": "onesided"}),
+    "blue443-magnitude": (443, 110, "mag.blue", {"sink": "magnitude"}),
 }
+# the sinks of the r20 / rab / Bluestein front-ends: also measured on noise next to the FORWARD cases
+FORWARD_SINKS = ("r20-magnitude", "rab960-onesided", "blue443-magnitude")
 
 # id -> (N, hop, family, M, options)
 INVERSE = {
@@ -505,6 +643,50 @@ INVERSE = {
 FIR = {33: "fir.wave32", 257: "fir.pair", 513: "fir.r2k", 4097: "fir.dline"}
 FIR_L, FIR_BURST = 60000, 2000
 FFT_ROWS = {1024: "fft.rows_wave", 4096: "fft.rows_wave", 1000: "fft.rows_generic"}
+
+# rows beyond the LDS-resident kernels (kernels_nd.hip).  id -> (K, family, tuning switches, rows): the smallest shapes that reach
+# each distinct piece of arithmetic of launch_fft_big
+_NT256, _E2048 = {"NXSIG_FFT_TILE_NT": 256}, {"NXSIG_FFT_TILE_ELEMS": 2048}
+FFT_ROWS_LONG = {
+    "8192": (8192, "fft.tiled", {}, 2),                    # the smallest tiled length (launch_fft_big's `small` excludes it)
+    "2^14": (1 << 14, "fft.tiled", {}, 2),                 # even log2: K1 = K2
+    "2^15": (1 << 15, "fft.tiled", {}, 2),                 # odd log2: K1 = 2 K2
+    "2^20": (1 << 20, "fft.tiled", {}, 2),                 # the largest tiled length: the high table fully used
+    "2^14-nt256": (1 << 14, "fft.tiled", _NT256, 2),       # another stride of the pass-A twiddle recurrence
+    "2^17-nt256": (1 << 17, "fft.tiled", _NT256, 2),
+    "2^14-elems2048": (1 << 14, "fft.tiled", _E2048, 2),   # and another
+    "2^17-elems2048": (1 << 17, "fft.tiled", _E2048, 2),
+    "2^14-five-pass": (1 << 14, "fft.transpose", {"NXSIG_FFT_TILED": 0}, 2),
+    "2^21": (1 << 21, "fft.transpose", {}, 2),             # the five-pass form where it runs by default
+    "blue5000": (5000, "fft.big.blue", {}, 2),             # P = 16384, even
+    "blue10007": (10007, "fft.big.blue", {}, 2),           # prime
+    "blue4097": (4097, "fft.big.blue", {}, 2),             # the first length past the LDS Bluestein, P = 16384
+}
+LONG_IMPULSES = 6   # rows of the impulse input: the five named positions of long_impulse_positions and one seeded random one
+
+# id -> (shape [outer, na, inner] or any rank, axes, lengths, family): transforms along an axis that is not the fastest one
+COLUMNS = {
+    "2x1024x8": ((2, 1024, 8), [1], None, "fft.tiled.columns"),
+    "3x16x64": ((3, 16, 64), [1], None, "fft.tiled.columns"),
+    "2x100x24-to-128": ((2, 100, 24), [1], [128], "fft.tiled.columns"),
+    "2x64x72-two-axes": ((2, 64, 72), [0, 1], [4, 64], "fft.transpose"),   # axis 0 (4 points) goes through transposes, axis 1 is tiled
+}
+
+# id -> (N, K, hop, stft family, istft family): M = 5 frames, 2 rows
+LONG_FRAMES = {
+    "16384": (16384, 16384, 4096, "stft.big", "fft.tiled"),
+    "5000": (5000, 5000, 1250, "stft.big", "fft.big.blue"),
+}
+LONG_FRAMES_M = 5
+
+# id -> (taps, L, switches): more taps than the overlap-save kernels take; the record leads with fir.long
+FIR_LONG = {
+    "4097-generic": (4097, 30000, {"NXSIG_DISABLE_WAVE": 1}),
+    "32770": (32770, 1 << 15, {}),          # the smallest tap count that reaches fir.long by default (launch_fir: taps > 32769)
+}
+
+# (shape of in1, shape of in2)
+CONV_ND = [((40, 300), (7, 31)), ((64, 64), (9, 9)), ((6, 20, 33), (3, 5, 7))]
 
 
 def context(switches=None):
@@ -558,6 +740,14 @@ def assert_family(record, family, lead=None):
     assert family_of(record) == family, f"dispatched to [{record}], the case is about [{family}]"
     if lead:
         assert record.split("+")[0] == lead, (record, lead)
+
+
+def assert_noted(record, entry):
+    """a case whose kernel is not the record's first entry (an n-D fold leads with its first axis): the entry is in the record"""
+    if PROBE:
+        print(f"\nDISPATCH {entry:<18} [{record}]")
+        return
+    assert entry in record.split("+"), f"dispatched to [{record}], the case is about [{entry}]"
 
 
 # ---------------------------------------------------------------------------------------------------------------- probe / recording

@@ -170,6 +170,91 @@ def test_fir_model_and_reference():
     assert m[0].shape == (4,) and 1e-8 < m[1].max() < 1e-6, m
 
 
+@pytest.fixture(scope="module", params=[14, 17])
+def long_rows(request):
+    """rows of 2^lg points as the long-row GPU tests measure them: white noise and the impulse set (the five named positions and three
+    seeded random ones), each with its double reference and the model's (max, l2)"""
+    lg = request.param
+    K = 1 << lg
+    rng = np.random.default_rng(lg)
+    inputs = {"noise": (rng.standard_normal((2, K)) + 1j * rng.standard_normal((2, K))).astype(np.complex64),
+              "impulse": A.long_impulse_rows(K, 8, seed=lg)}
+    d = {"lg": lg}
+    for name, x in inputs.items():
+        ref = A.fft_rows_reference(x, K, False)
+        for v in (x, ref):
+            v.setflags(write=False)
+        d[name] = (x, ref, A.fft_rows_model_errors(x, K, False, ref, "fft.tiled"))
+    return d
+
+
+def _fourstep_errors(long_rows, kind, **form):
+    x, ref, m = long_rows[kind]
+    e = A.worst(A.row_errors(A.clean(A.fourstep_f32(x, long_rows["lg"], **form)), ref))
+    print(f"2^{long_rows['lg']} {kind} {form}: model {m}, four-step {e}, ratio max {e[0] / m[0]:.2f} l2 {e[1] / m[1]:.2f}")
+    return e, m
+
+
+@pytest.mark.parametrize("kind", ["noise", "impulse"])
+@pytest.mark.parametrize("form", [dict(twiddles="table"), dict(twiddles="recurrence", reseed=8)], ids=["table", "every-8"])
+def test_a_fourstep_with_the_kernels_twiddles_passes(long_rows, kind, form):
+    """the two-level table product at every element, and the recurrence re-seeded every eighth element (what k_fft_tile does)"""
+    e, m = _fourstep_errors(long_rows, kind, **form)
+    assert _within(e, m), (e, m)
+
+
+@pytest.mark.parametrize("reseed", [64, None], ids=["every-64", "never"])
+def test_a_fourstep_with_a_longer_twiddle_recurrence_fails(long_rows, reseed):
+    """a re-seed period of 64, or none: both pass the suite's whole-tensor 1e-5 and must not pass here.  On noise both norms exceed the
+    margin; on the impulse set the max norm (a per-bin figure) does"""
+    e, m = _fourstep_errors(long_rows, "noise", twiddles="recurrence", reseed=reseed)
+    assert e[0] > A.MARGIN * m[0] and e[1] > A.MARGIN * m[1], (e, m)
+    e, m = _fourstep_errors(long_rows, "impulse", twiddles="recurrence", reseed=reseed)
+    assert not _within(e, m) and e[0] > A.MARGIN * m[0], (e, m)
+
+
+def test_a_fourstep_twiddle_from_an_f32_angle_stays_inside_the_margin(long_rows):
+    """what the bound does NOT separate: one twiddle per element from an angle rounded to f32 reads 1.1 - 1.5 x the model here (the
+    per-frame radix-2 form of it, with a rounded angle in every stage, about 2 x) — recorded, like the f32-angle case above"""
+    for kind in ("noise", "impulse"):
+        e, m = _fourstep_errors(long_rows, kind, twiddles="f32angle")
+        assert _within(e, m), (e, m)
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("K", [5000, 10007])
+def test_a_single_precision_bluestein_stays_near_the_direct_transform(K, inverse):
+    """bluestein_f32 is the floor of fft.big.blue's algorithm: within the margin of the direct complex64 transform, under 2.5 x of it
+    in both norms, and (trivially, being part of it) within its own model"""
+    rng = np.random.default_rng(K)
+    for name, x in (("noise", (rng.standard_normal((2, K - 5)) + 1j * rng.standard_normal((2, K - 5))).astype(np.complex64)),
+                    ("impulse", A.long_impulse_rows(K, 8, seed=K))):
+        ref = A.fft_rows_reference(x, K, inverse)
+        direct = A.fft_rows_model_errors(x, K, inverse, ref, "fft.tiled")
+        own = A.fft_rows_model_errors(x, K, inverse, ref, "fft.big.blue")
+        e = A.worst(A.row_errors(A.clean(A.bluestein_f32(x, K, inverse)), ref))
+        print(f"K={K} {name} inverse={inverse}: direct {direct}, bluestein {e}, ratio max {e[0] / direct[0]:.2f} l2 {e[1] / direct[1]:.2f}")
+        assert 5e-8 < direct[1] < 3e-7, direct
+        assert _within(e, direct) and _within(e, own), (e, direct, own)
+        assert e[0] < 2.5 * direct[0] and e[1] < 2.5 * direct[1], (e, direct)
+        assert own[0] >= direct[0] and own[1] >= direct[1]
+
+
+def test_long_impulse_positions_are_the_named_ones():
+    p = A.long_impulse_positions(1 << 15, 8, seed=1)
+    assert list(p[:5]) == [1, 127, 129, (1 << 14) + 1, (1 << 15) - 1] and len(p) == 8 and (p < (1 << 15)).all()
+    x = A.long_impulse_rows(1 << 15, 8, seed=1)
+    assert x.shape == (8, 1 << 15) and (np.abs(x).sum(axis=-1) == 1).all() and (np.argmax(np.abs(x), axis=-1) == p).all()
+
+
+def test_every_long_case_names_a_family_with_a_reach():
+    for K, family, switches, rows in A.FFT_ROWS_LONG.values():
+        assert A.reach_of(family) == 1 and rows == 2 and K >= 4097
+    for key in A.FORWARD_SINKS:
+        K, hop, family, opts = A.FORWARD_EXTRA[key]
+        assert A.reach_of(family) == A.reach_of("stft." + family.split(".")[1]) and opts["sink"] in ("magnitude", "onesided")
+
+
 def test_family_of_reads_dispatch_records():
     assert A.family_of("stft.pair.1r+stft.pair.1r.edge") == "stft.pair"
     assert A.family_of("stft.pair+stft.pair.h4") == "stft.pair"
@@ -178,7 +263,9 @@ def test_family_of_reads_dispatch_records():
     assert A.family_of("istft.wave.mask+istft.edge_chunks") == "istft.wave.mask"
     assert A.family_of("istft.rab.q") == "istft.rab.q" and A.family_of("istft.rab+istft.edge_chunks") == "istft.rab"
     assert A.family_of("fft.rows_generic.blue+istft.generic+istft.edge_fix") == "fft.rows_generic"
-    assert A.family_of("stft.big") is None
+    assert A.family_of("stft.big+fft.tiled+fft.tiled") == "stft.big" and A.family_of("fft.tiled+fft.tiled") == "fft.tiled"
+    assert A.family_of("fft.tiled.columns") == "fft.tiled.columns" and A.family_of("fft.transpose+fft.rows_wave") == "fft.transpose"
+    assert A.family_of("mag.rab") == "mag.rab" and A.family_of("mel.rab") is None
     assert A.reach_of("istft.quad", 256) == 4 and A.reach_of("stft.quad8") == 16
 
 
