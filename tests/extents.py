@@ -6,6 +6,11 @@ lie `row_stride` elements apart; the gap after every row holds the pattern as we
 a NaN as f32, in either half of a c64 and — doubled — as f64, so a gap or guard element that reaches a result shows as a NaN the oracle
 does not have, and a result element nobody wrote still carries the pattern.
 
+Elements of one byte (the u8 mask of nxsig_nonzero) go by bytes: the guards stay whole words of the pattern, and the bytes between the
+tensor's last element and the next word boundary hold the pattern too — a tail gap, every byte of it non-zero.  Integer results (the s32
+[size][rank] table and the u32 count of nxsig_argrelextrema) are judged as tables: an element nobody wrote still holds POISON, which is
+neither -1 nor a coordinate of any shape the suite uses, and the exact comparison names the row and the column.
+
 After the call the whole arenas are read back and checked by the functions below, which work on plain numpy images: the same code
 judges a HIP kernel (tests/test_gpu_strided_rows.py, tests/test_gpu_output_extents.py) and the numpy stand-ins with planted faults of
 tests/test_extents_harness_host.py.  Every finding names its place: which guard and how far from the tensor, or which row and index.
@@ -39,11 +44,20 @@ class Arena:
         self.rows, self.row_len = int(rows), int(row_len)
         self.row_stride = self.row_len if row_stride is None else int(row_stride)
         assert self.row_stride >= self.row_len and 0 <= offset_elems <= 3
-        self.wpe = self.dtype.itemsize // 4                       # 32-bit words per element
+        self.wpe = self.dtype.itemsize // 4                       # 32-bit words per element (0: a one-byte type, laid out by bytes)
+        self.narrow = self.dtype.itemsize < 4
+        assert self.dtype.itemsize == 1 or self.dtype.itemsize % 4 == 0
         self.count = self.rows * self.row_stride                  # elements up to and including the gap of the last row
-        self.lead = WORDS + offset_elems * self.wpe               # words in front of the tensor
-        self.first = self.lead // self.wpe
-        self.image = np.full(self.lead + self.count * self.wpe + WORDS, POISON, np.uint32)
+        if self.narrow:
+            self.lead_bytes = GUARD + offset_elems                # bytes in front of the tensor
+            self.end_bytes = self.lead_bytes + (self.rows - 1) * self.row_stride + self.row_len    # first byte behind the last element
+            self.lead, self.first = WORDS, self.lead_bytes
+            self.image = np.full((self.lead_bytes + self.count + 3) // 4 + WORDS, POISON, np.uint32)   # the tail gap: up to the next word
+        else:
+            self.lead = WORDS + offset_elems * self.wpe           # words in front of the tensor
+            self.lead_bytes = self.lead * 4
+            self.first = self.lead // self.wpe
+            self.image = np.full(self.lead + self.count * self.wpe + WORDS, POISON, np.uint32)
         self.dev = None
         if data is not None:
             self.fill(data)
@@ -55,7 +69,7 @@ class Arena:
 
     @property
     def offset_bytes(self):
-        return self.lead * 4
+        return self.lead_bytes
 
     def view(self, image=None):
         """the whole arena as elements of the tensor's type (what a kernel indexes from `first`)"""
@@ -88,6 +102,19 @@ class Arena:
             return f"{self.name}: gap after row {row}, element {idx - self.row_len}{tail}"
         return f"{self.name}: row {row}, index {idx}{tail}"
 
+    def locate_byte(self, byte):
+        """where in the arena of a one-byte type a byte lies"""
+        byte = int(byte)
+        if byte < self.lead_bytes:
+            return f"{self.name}: front guard, {self.lead_bytes - byte} bytes before the tensor"
+        if byte >= self.end_bytes:
+            past = byte - self.end_bytes
+            return f"{self.name}: {'tail gap' if byte < -(-self.end_bytes // 4) * 4 else 'back guard'}, {past} bytes past the tensor"
+        row, idx = divmod(byte - self.lead_bytes, self.row_stride)
+        if idx >= self.row_len:
+            return f"{self.name}: gap after row {row}, element {idx - self.row_len}"
+        return f"{self.name}: row {row}, index {idx}"
+
     # ---- device side
     def upload(self, ctx):
         from nx_signal_amd import _lib
@@ -108,10 +135,22 @@ def _first(words, limit=4):
     return [int(w) for w in words[:limit]]
 
 
+def _byte_inside(arena, nbytes):
+    inside = np.zeros(nbytes, bool)
+    rows = inside[arena.lead_bytes:arena.lead_bytes + arena.count].reshape(arena.rows, arena.row_stride)
+    rows[:, :arena.row_len] = True
+    return inside
+
+
 def guard_findings(arena, image):
-    """words of the two guards (and of the gap behind the last row) that no longer hold the pattern"""
+    """words of the two guards (and of the gap behind the last row) that no longer hold the pattern; bytes for a one-byte type"""
     image = np.asarray(image, np.uint32)
     assert image.shape == arena.image.shape
+    if arena.narrow:
+        b, pat = image.view(np.uint8), np.full(image.size, POISON, np.uint32).view(np.uint8)
+        bad = np.flatnonzero(~_byte_inside(arena, b.size) & (b != pat))
+        return [f"store outside the result — {arena.locate_byte(w)} holds 0x{int(b[w]):02X}" for w in _first(bad)] + \
+               ([f"... {bad.size} guard bytes changed in all"] if bad.size > 4 else [])
     inside = np.zeros(image.size, bool)
     rows = inside[arena.lead:arena.lead + arena.count * arena.wpe].reshape(arena.rows, arena.row_stride * arena.wpe)
     rows[:, :arena.row_len * arena.wpe] = True
@@ -124,6 +163,11 @@ def unchanged_findings(arena, image):
     """an input arena must come back bit for bit as it was uploaded"""
     image = np.asarray(image, np.uint32)
     assert image.shape == arena.image.shape
+    if arena.narrow:
+        b, was = image.view(np.uint8), arena.image.view(np.uint8)
+        bad = np.flatnonzero(b != was)
+        return [f"input modified — {arena.locate_byte(w)}: 0x{int(was[w]):02X} became 0x{int(b[w]):02X}" for w in _first(bad)] + \
+               ([f"... {bad.size} input bytes changed in all"] if bad.size > 4 else [])
     bad = np.flatnonzero(image != arena.image)
     return [f"input modified — {arena.locate(w)}: 0x{int(arena.image[w]):08X} became 0x{int(image[w]):08X}" for w in _first(bad)] + \
            ([f"... {bad.size} input words changed in all"] if bad.size > 4 else [])
@@ -204,14 +248,37 @@ def bit_findings(arena, got, want, unit=1):
     return out
 
 
-def findings(inputs, out, out_image, expected=None, tol=None, unit=1, absolute=False, same_bits_as=None, where=None, by_frame=False):
+def _table(arena, a):
+    assert arena.dtype in (np.dtype(np.int32), np.dtype(np.uint32)), arena.dtype
+    return np.ascontiguousarray(np.asarray(a).astype(arena.dtype, copy=False).reshape(arena.rows, arena.row_len))
+
+
+def table_unwritten_findings(arena, image):
+    """elements of an integer result ([rows][columns], s32 or u32) that still hold the 32-bit pattern"""
+    bad = np.argwhere(_table(arena, arena.tensor(image)).view(np.uint32) == np.uint32(POISON))
+    return [f"result element never written — {arena.name}: row {r}, column {c}" for r, c in bad[:4].tolist()] + \
+           ([f"... {len(bad)} result elements unwritten in all"] if len(bad) > 4 else [])
+
+
+def table_findings(arena, got, want):
+    """an integer result against the expected table, exactly; elements still unwritten are table_unwritten_findings' to report"""
+    g, w = _table(arena, got), _table(arena, want)
+    bad = np.argwhere((g != w) & (g.view(np.uint32) != np.uint32(POISON)))
+    return [f"{arena.name}: row {r}, column {c} holds {int(g[r, c])}, expected {int(w[r, c])}" for r, c in bad[:4].tolist()] + \
+           ([f"... {len(bad)} elements differ from the expected table in all"] if len(bad) > 4 else [])
+
+
+def findings(inputs, out, out_image, expected=None, tol=None, unit=1, absolute=False, same_bits_as=None, where=None, by_frame=False, table=None):
     """every check of one call: `inputs` = [(arena, image after the call)], `out` the result arena and its image after the call.
-    expected + tol: the reference and its bound (finite mask exact); same_bits_as: a result the call must reproduce bit for bit."""
+    expected + tol: the reference and its bound (finite mask exact); same_bits_as: a result the call must reproduce bit for bit;
+    table: the expected integer result of an s32 / u32 arena, compared exactly."""
     found = []
     for arena, image in inputs:
         found += unchanged_findings(arena, image)
     found += guard_findings(out, out_image)
     got = out.tensor(out_image)
+    if table is not None:
+        found += table_unwritten_findings(out, out_image) + table_findings(out, got, table)
     if expected is not None:
         found += unwritten_findings(out, out_image, expected)
         found += finite_findings(out, got, expected, unit, by_frame=by_frame)
