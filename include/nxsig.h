@@ -842,6 +842,41 @@ int nxsig_savgol_coeffs(int32_t window_length, int32_t polyorder, int32_t deriv,
 int nxsig_savgol_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, int64_t length, int32_t batch, int64_t batch_stride,
                         int32_t window_length, int32_t polyorder, int32_t deriv, double delta, int32_t mode, double cval, void* y, int32_t mem);
 
+/*
+ * Filters.hilbert — scipy.signal.hilbert(x, N=None, axis=-1) of SciPy 1.15 over real f32 rows: the analytic signal, its magnitude (the
+ * envelope) or its imaginary part (the Hilbert transform proper).  The reference has none of them; DESIGN.md section 3.16.
+ * THE DEFINITION: a row of `length` samples is truncated or zero-padded to N = n_fft points (SciPy's default is N = length),
+ *     X = DFT_N(row),   a = IDFT_N(X h) with its 1 / N,
+ *     h[0] = 1;  N even: h[N / 2] = 1 and h[k] = 2 for 0 < k < N / 2;  N odd: h[k] = 2 for 0 < k < (N + 1) / 2;  every other h[k] = 0.
+ * The gains of a row sum to N.  No Nx.fft-style clean-up of small values is applied, to either transform.
+ *   NXSIG_HILBERT_ANALYTIC    out = a, c64 [batch][n_fft]
+ *   NXSIG_HILBERT_ENVELOPE    out = |a| = sqrtf(re * re + im * im) in f32 on the rounded components of a, f32 [batch][n_fft] (the expression
+ *                             of nxsig_stft_magnitude_f32's NXSIG_MAG_ABS, the same in both dispatch families)
+ *   NXSIG_HILBERT_QUADRATURE  out = Im a, f32 [batch][n_fft]
+ * x [batch][length] rows batch_stride >= length elements apart, of which the first min(length, n_fft) samples are read; out dense; x
+ * and out must not overlap.  batch = 0 succeeds and launches nothing.  Limits: length >= 1, 1 <= n_fft < 2^31; lengths the row
+ * transforms of nxsig_fft refuse, rows whose byte counts overflow and f64 rows (there is no f64 entry point) are
+ * NXSIG_ERR_UNSUPPORTED.
+ * Dispatch families: hilbert.wave (n_fft = 1024, 2048: one wave per row, both transforms and the gain in registers and LDS, the row
+ * read once and the result written once) and hilbert.generic (every other n_fft, and every n_fft under NXSIG_DISABLE_HILBERT_WAVE or
+ * NXSIG_DISABLE_WAVE: nxsig_fft's row transforms around an in-place gain, the spectrum in scratch memory).  Both are single-precision
+ * transforms: a row is within 1e-5 max|a| of the definition evaluated in double; the two families need not agree to the bit.  No
+ * atomics; a row's bits do not depend on the batch.
+ * Arithmetic: a row that fills the transform (length >= n_fft: no zero padding) is transformed as row - c, c the row's mean as f32 sums
+ * give it, and c is added to Re a afterwards.  Algebraically that is the same a (only X[0] changes, and h[0] = 1); numerically the
+ * rounding of the two transforms then scales with the row's variation, not with its offset: Im a of a 1000 + N(0, 1) row stays within
+ * 1e-5 max|Im a|, where the plain transforms leave 6e-5.  A zero-padded row is transformed as it stands.
+ * Non-finite rule: a row that holds an Inf / NaN among the min(length, n_fft) samples read has no finite output element (SciPy's
+ * transforms behave alike); which of NaN / Inf comes out is not specified.  The rule is carried out on X[0], the sum of the samples as the
+ * forward transform forms it: when it is not finite the whole spectrum of the row is replaced by NaN.  (Finite samples whose sum
+ * overflows f32 therefore poison their row, whose outputs overflow anyway.)  No other row of the batch is affected, and samples at or
+ * past min(length, n_fft) are not read.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+typedef enum nxsig_hilbert_kind { NXSIG_HILBERT_ANALYTIC = 0, NXSIG_HILBERT_ENVELOPE = 1, NXSIG_HILBERT_QUADRATURE = 2 } nxsig_hilbert_kind;
+int nxsig_hilbert_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, int64_t n_fft, int32_t kind,
+                      void* out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,7 @@ UNITS = [
     ("kernels_iir.hip", []),  # Filters.sosfilt / sosfiltfilt: biquad cascades in double, an exact scan over time
     ("kernels_find_peaks.hip", []),  # PeakFinding.find_peaks: line summary, walks, distance rounds (no FMA contraction: the file says so itself)
     ("kernels_savgol.hip", []),  # Filters.savgol_filter: Savitzky-Golay smoothing and derivatives, double sums over an LDS tile
+    ("kernels_hilbert.hip", []),  # Filters.hilbert: analytic signal, envelope, quadrature; forward core, gain, inverse core in one wave
 ]
 
 

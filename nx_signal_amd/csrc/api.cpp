@@ -2556,6 +2556,31 @@ int nxsig_savgol_filter(nxsig_ctx* ctx, const void* x, int32_t is_f64, int64_t l
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Filters.hilbert */
+int nxsig_hilbert_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, int64_t n_fft, int32_t kind,
+                      void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !out) return set_error(NXSIG_ERR_INVALID_ARG, "hilbert: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = hilbert_check(length, batch, batch_stride, n_fft, kind, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("hilbert: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(float)), kScratchNdStageA}},
+                    {{out, (size_t)batch * n_fft * hilbert_out_elem(kind), kScratchNdStageOut}}))) return rc;
+  HilbertLaunch a;
+  a.x = static_cast<const float*>(io.in[0]); a.length = length; a.x_stride = batch_stride; a.batch = batch; a.n_fft = n_fft; a.kind = kind;
+  a.out = io.out[0];
+  if ((rc = launch_hilbert(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"
 
 namespace nxsig {

@@ -315,3 +315,5 @@ def sosfiltfilt(x, sos, ctx=None, axis=-1, padtype="odd", padlen=None):
 
 # savgol_filter / savgol_coeffs live in a module of their own (_savgol.py) and are part of this one's interface
 from ._savgol import savgol_coeffs, savgol_filter  # noqa: E402,F401
+# ... and so does hilbert (_hilbert.py)
+from ._hilbert import hilbert  # noqa: E402,F401

@@ -7,6 +7,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --iir [--real] [--write tests/golden/abi_error_table_iir.json]
     python tools/abi_error_probe.py --peaks [--real] [--write tests/golden/abi_error_table_find_peaks.json]
     python tools/abi_error_probe.py --savgol [--real] [--write tests/golden/abi_error_table_savgol.json]
+    python tools/abi_error_probe.py --hilbert [--real] [--write tests/golden/abi_error_table_hilbert.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -20,7 +21,8 @@ compare against it): the same probe, the same kinds of cases.  WELCH_TABLE_ENTRI
 nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py), IIR_TABLE_ENTRIES (--iir) for nxsig_sosfilt_f32 and
 nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TABLE_ENTRIES (--peaks) for nxsig_find_peaks
 (tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py), SAVGOL_TABLE_ENTRIES (--savgol) for nxsig_savgol_filter
-(tests/test_savgol_host.py, tests/test_gpu_savgol.py)."""
+(tests/test_savgol_host.py, tests/test_gpu_savgol.py), HILBERT_TABLE_ENTRIES (--hilbert) for nxsig_hilbert_f32
+(tests/test_hilbert_host.py, tests/test_gpu_hilbert.py)."""
 import argparse
 import ctypes as C
 import json
@@ -40,6 +42,7 @@ GOLDEN_WELCH = os.path.join(ROOT, "tests", "golden", "abi_error_table_welch.json
 GOLDEN_IIR = os.path.join(ROOT, "tests", "golden", "abi_error_table_iir.json")
 GOLDEN_PEAKS = os.path.join(ROOT, "tests", "golden", "abi_error_table_find_peaks.json")
 GOLDEN_SAVGOL = os.path.join(ROOT, "tests", "golden", "abi_error_table_savgol.json")
+GOLDEN_HILBERT = os.path.join(ROOT, "tests", "golden", "abi_error_table_hilbert.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -348,6 +351,18 @@ SAVGOL_TABLE_ENTRIES = [
       ("interp window > length", {"window_length": 25}), ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16})]),
 ]
 
+# Filters.hilbert: 2 rows of 24 samples, zero-padded to 32 points, the envelope (kind 1).  batch = 0 is valid and launches nothing, so it
+# runs with ctx = NULL alone, where it shows that the argument checks let it through to the context
+HL = 24
+HILBERT_TABLE_ENTRIES = [
+    ("nxsig_hilbert_f32",
+     [("x", "in", _f32(B, HL)), ("length", "v", HL), ("batch", "v", B), ("batch_stride", "v", HL), ("n_fft", "v", 32), ("kind", "v", 1),
+      ("out", "out", np.zeros((B, 32), np.float32)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}, NULL_ONLY), ("batch=-1", {"batch": -1}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": HL - 1}),
+      ("n_fft=0", {"n_fft": 0}), ("n_fft=-1", {"n_fft": -1}), ("n_fft=2^31", {"n_fft": 1 << 31}), ("kind=3", {"kind": 3}), ("kind=-1", {"kind": -1}),
+      ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16}), ("result too large", {"n_fft": (1 << 31) - 1, "batch": 1 << 30})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -463,9 +478,10 @@ def main():
     ap.add_argument("--iir", action="store_true", help="the entry points of IIR_TABLE_ENTRIES (Filters.sosfilt / sosfiltfilt)")
     ap.add_argument("--peaks", action="store_true", help="the entry point of PEAKS_TABLE_ENTRIES (PeakFinding.find_peaks)")
     ap.add_argument("--savgol", action="store_true", help="the entry point of SAVGOL_TABLE_ENTRIES (Filters.savgol_filter)")
+    ap.add_argument("--hilbert", action="store_true", help="the entry point of HILBERT_TABLE_ENTRIES (Filters.hilbert)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
