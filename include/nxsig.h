@@ -877,6 +877,45 @@ typedef enum nxsig_hilbert_kind { NXSIG_HILBERT_ANALYTIC = 0, NXSIG_HILBERT_ENVE
 int nxsig_hilbert_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, int64_t n_fft, int32_t kind,
                       void* out, int32_t mem);
 
+/*
+ * Transforms.dct / idct — scipy.fft.dct(x, type, n, axis, norm) and idct of SciPy 1.15 over real f32 rows, types 2 and 3, and the mfcc
+ * front end built on them.  The reference has neither; DESIGN.md section 3.17.
+ * THE DEFINITION: a row of `length` samples is truncated or zero-padded to n points (SciPy's default is n = length), then
+ *   type 2   y[k] = 2 sum_{j=0}^{n-1} x[j] cos(pi k (2 j + 1) / (2 n))
+ *            norm NXSIG_DCT_ORTHO: y[0] * sqrt(1 / (4 n)), y[k > 0] * sqrt(1 / (2 n));  NXSIG_DCT_FORWARD: y / (2 n)
+ *   type 3   y[k] = x[0] + 2 sum_{j=1}^{n-1} x[j] cos(pi (2 k + 1) j / (2 n))
+ *            norm NXSIG_DCT_ORTHO: y[k] = x[0] / sqrt(n) + sqrt(2 / n) sum_{j>=1} x[j] cos(...);  NXSIG_DCT_FORWARD: y / (2 n)
+ * idct(x, type t, norm) is the transform of the other type (2 <-> 3) with NXSIG_DCT_BACKWARD and NXSIG_DCT_FORWARD exchanged and
+ * NXSIG_DCT_ORTHO kept, so idct(dct(x)) = x for every norm; the caller makes the exchange (there is no inverse flag).  Types 1 and 4
+ * are valid in SciPy and not built: NXSIG_ERR_UNSUPPORTED; any other type is an argument error.  SciPy's orthogonalize=, overwrite_x= and
+ * workers= are not offered.  No Nx.fft-style clean-up of small values is applied.
+ * keep (the one extension): only the leading keep coefficients y[0 .. keep) are computed and stored, 1 <= keep <= n; they carry the
+ * bits of the leading slice of the full result.
+ * x [batch][length] rows batch_stride >= length elements apart, of which the first min(length, n) samples are read; out dense
+ * [batch][keep]; x and out must not overlap.  batch = 0 succeeds and launches nothing.  Limits: length >= 1, 1 <= n < 2^31; lengths the
+ * row transforms of nxsig_fft refuse, rows whose byte counts overflow and f64 rows (there is no f64 entry point) are
+ * NXSIG_ERR_UNSUPPORTED.
+ * Dispatch families: dct.direct (n <= 256, any keep — the cepstral path: every output is one sum over ascending j against a cosine
+ * table, several rows per workgroup through LDS) and dct.fft (every other n, and every n under NXSIG_DISABLE_DCT_DIRECT: Makhoul's
+ * n-point form — a permutation, one row transform of nxsig_fft, a twiddle; the other way round for type 3).  The tables are built on the
+ * host in double from an integer argument reduced mod 4 n, so no argument of cos is rounded and cos of an odd multiple of pi / 2 is an
+ * exact zero.  Both families are single precision: a row is within 1e-5 max_k |y[k]| of the definition evaluated in double; the two
+ * families need not agree to the bit.  No atomics: a row's bits depend neither on the batch nor on where the tensors live.
+ * Arithmetic: both families compute type 2 on row - c, c the mean of the n points as f32 sums give it, and add c * 2 n (times the
+ * norm's factor of y[0]) to y[0].  Algebraically nothing changes (sum_j cos(pi k (2 j + 1) / (2 n)) = 0 for 0 < k < n); numerically the
+ * coefficients k >= 1 of a 1000 + N(0, 1) row then stay within 1e-5 max_{k>=1} |y[k]|, where plain f32 sums against an f32 table
+ * leave 5e-4 to 1e-3 and a plain single-precision transform of Makhoul's form 2.5e-4.  Type 3 is computed as it stands.
+ * Non-finite rule: a row that holds an Inf / NaN among the min(length, n) samples read has no finite output element (SciPy's
+ * transforms behave alike); which of NaN / Inf comes out is not specified.  dct.direct: every output is a sum over every sample.
+ * dct.fft: when bin 0 of the forward transform (type 2: the sum of the samples) or point 0 of the inverse one (type 3: the sum of the
+ * spectrum) is not finite, the row leaves as NaN.  No other row of the batch is affected, and samples at or past min(length, n) are
+ * not read.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+typedef enum nxsig_dct_norm { NXSIG_DCT_BACKWARD = 0, NXSIG_DCT_ORTHO = 1, NXSIG_DCT_FORWARD = 2 } nxsig_dct_norm;
+int nxsig_dct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch, int64_t batch_stride, int64_t n, int32_t type, int32_t norm,
+                  int64_t keep, float* out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,7 @@ from ._marshal import Operand, _as_tensor, is_device, ptr, rows_last, validate a
 from .device import Context, DeviceBuffer, default_context
 
 __all__ = [
-    "stft", "istft", "as_windowed", "overlap_and_add", "fft_frequencies", "mel_filters", "stft_to_mel", "mel_spectrogram",
+    "stft", "istft", "as_windowed", "overlap_and_add", "fft_frequencies", "mel_filters", "stft_to_mel", "mel_spectrogram", "mfcc",
     "spectrum_multiply", "istft_filtered", "spectrum_mask", "istft_masked", "stft_onesided", "spectrogram",
     "Context", "DeviceBuffer", "default_context", "ArgumentError",
     "NxSignalDeviceError", "NxSignalLibraryError", "NxSignalUnsupported",
@@ -616,3 +616,4 @@ def spectrogram(data, window, ctx: Context | None = None, **opts):
 
 
 from . import convolution, filters, peak_finding, spectral, transforms, waveforms, windows  # noqa: E402,F401
+from ._dct import mfcc  # noqa: E402,F401  (mel_spectrogram, then transforms.dct: _dct.py)

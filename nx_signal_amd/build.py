@@ -58,6 +58,7 @@ UNITS = [
     ("kernels_find_peaks.hip", []),  # PeakFinding.find_peaks: line summary, walks, distance rounds (no FMA contraction: the file says so itself)
     ("kernels_savgol.hip", []),  # Filters.savgol_filter: Savitzky-Golay smoothing and derivatives, double sums over an LDS tile
     ("kernels_hilbert.hip", []),  # Filters.hilbert: analytic signal, envelope, quadrature; forward core, gain, inverse core in one wave
+    ("kernels_dct.hip", []),  # Transforms.dct / idct (and mfcc): cosine table sums over LDS tiles of rows; Makhoul's form around one row transform
 ]
 
 

@@ -2581,6 +2581,31 @@ int nxsig_hilbert_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t ba
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Transforms.dct / idct */
+int nxsig_dct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch, int64_t batch_stride, int64_t n, int32_t type, int32_t norm,
+                  int64_t keep, float* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !out) return set_error(NXSIG_ERR_INVALID_ARG, "dct: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = dct_check(length, batch, batch_stride, n, type, norm, keep, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("dct: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, ((size_t)(batch - 1) * batch_stride + length) * sizeof(float), kScratchNdStageA}},
+                    {{out, (size_t)batch * keep * sizeof(float), kScratchNdStageOut}}))) return rc;
+  DctLaunch a;
+  a.x = static_cast<const float*>(io.in[0]); a.length = length; a.x_stride = batch_stride; a.batch = batch; a.n = n; a.type = type; a.norm = norm;
+  a.keep = keep; a.out = static_cast<float*>(io.out[0]);
+  if ((rc = launch_dct(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"
 
 namespace nxsig {

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -119,7 +119,7 @@ enum ScratchSlot : int {
   kScratchStageIn = 1,           // host staging: the first input of a NXSIG_HOST call (HostIo, api.cpp)
   kScratchStageOut = 2,          // host staging: the result of a NXSIG_HOST call; nxsig_fftconvolve_c64's second input (HostIo, api.cpp)
   kScratchWaveSink = 3,          // dummy sink the wave kernels' unused output pointers aim at (kernels_wave*.hip, wave_stft.hpp, wave_rab.hpp)
-  kScratchFusedSpectrum = 4,     // spectrum of the two-step fall-back of the fused sinks (welch.generic / csd.generic: the frames' spectra); staged result of nxsig_fftconvolve_c64 (api.cpp); hilbert.generic: the rows' spectra (kernels_hilbert.hip)
+  kScratchFusedSpectrum = 4,     // spectrum of the two-step fall-back of the fused sinks (welch.generic / csd.generic: the frames' spectra); staged result of nxsig_fftconvolve_c64 (api.cpp); hilbert.generic: the rows' spectra (kernels_hilbert.hip); dct.fft: the result of its one row transform (kernels_dct.hip)
   kScratchReductionCells = 5,    // running maximum + non-finite flag of the log-mel / dBFS paths (kernels_generic.hip, group.cpp)
   kScratchFourStepA = 6,         // four-step rows: first buffer, also the tiled form's only one (kernels_nd.hip)
   kScratchFourStepB = 7,         // four-step rows: second buffer (kernels_nd.hip)
@@ -135,7 +135,7 @@ enum ScratchSlot : int {
   kScratchNdStageA = 17,         // host staging of the n-D / filter / peak / waveform calls: first input; the mask of the masked istft (api.cpp)
   kScratchNdStageB = 18,         // the same: second input; peak finding's `valid` cell (api.cpp)
   kScratchNdStageOut = 19,       // the same: results, several packed at a 256-byte stride (api.cpp)
-  kScratchIstftProduct = 20,     // z * H / z * mask of the filtered and masked istft's two-step fall-back (launch_istft, api.cpp); hilbert.generic: the means of the rows that fill the transform, the dense (centred or gathered) rows, later the complex signal ahead of the sink — every output of a centred row, the f32 outputs of the others (kernels_hilbert.hip)
+  kScratchIstftProduct = 20,     // z * H / z * mask of the filtered and masked istft's two-step fall-back (launch_istft, api.cpp); hilbert.generic: the means of the rows that fill the transform, the dense (centred or gathered) rows, later the complex signal ahead of the sink — every output of a centred row, the f32 outputs of the others (kernels_hilbert.hip); dct.fft: the input of its one row transform — the row means and the permuted, centred rows (type 2) or the Hermitian spectra (type 3) (kernels_dct.hip)
   kScratchFirLong = 21,          // long FIR: full convolution row, partition outputs, delay-line spectra (api.cpp, kernels_wave_firlong.hip); sosfiltfilt: the extended rows and the forward result (kernels_iir.hip)
   kScratchFirRowFlags = 22,      // per-row non-finite flags of the FIR kernels (fir_row_flags, kernels_generic.hip)
   kScratchIstftNfList = 23,      // units with a non-finite bin reported by the multi-frame inverse kernels (istft_nf_list, kernels_generic.hip)
@@ -587,4 +587,22 @@ namespace nxsig {
 // modulo 2^31, is_set = 0.  A call served from a memo of table pointers makes no request, which is how the tests see that a repeated
 // call formed nothing again.  False for any other name (api.cpp)
 bool table_requests_query(const Ctx* c, const char* name, int32_t* value, int32_t* is_set);
+}  // namespace nxsig
+
+#include "dct_plan.hpp"
+
+namespace nxsig {
+// kernels_dct.hip: Transforms.dct / idct over device rows (include/nxsig.h states the definition, DESIGN.md section 3.17 the design; the
+// argument checks are the caller's).  dct.direct uses no scratch; dct.fft keeps the input of its row transform (type 2: behind the row means) in
+// kScratchIstftProduct and the transform's result in kScratchFusedSpectrum.  The cosine / twiddle table goes through ctx_table once per context and
+// parameter set.  Everything is enqueued on c->stream and nothing waits
+struct DctLaunch {
+  const float* x;          // device f32[batch][length], rows x_stride elements apart
+  int64_t length, x_stride, batch;
+  int64_t n;               // points of the transform: the row is truncated or zero-padded
+  int32_t type, norm;      // 2 or 3; DctNorm
+  int64_t keep;            // leading coefficients stored, 1 <= keep <= n
+  float* out;              // device, dense [batch][keep]
+};
+int launch_dct(Ctx* c, const DctLaunch& a);
 }  // namespace nxsig

@@ -78,3 +78,7 @@ def fft_nd(tensor, ctx=None, **opts):
 
 def ifft_nd(tensor, ctx=None, **opts):
     return _run(tensor, True, opts, ctx)
+
+
+# dct / idct live in a module of their own (_dct.py) and are part of this one's interface
+from ._dct import dct, idct  # noqa: E402,F401

@@ -8,6 +8,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --peaks [--real] [--write tests/golden/abi_error_table_find_peaks.json]
     python tools/abi_error_probe.py --savgol [--real] [--write tests/golden/abi_error_table_savgol.json]
     python tools/abi_error_probe.py --hilbert [--real] [--write tests/golden/abi_error_table_hilbert.json]
+    python tools/abi_error_probe.py --dct [--real] [--write tests/golden/abi_error_table_dct.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -22,7 +23,8 @@ nxsig_csd_f32 (tests/test_welch_host.py, tests/test_gpu_welch.py), IIR_TABLE_ENT
 nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TABLE_ENTRIES (--peaks) for nxsig_find_peaks
 (tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py), SAVGOL_TABLE_ENTRIES (--savgol) for nxsig_savgol_filter
 (tests/test_savgol_host.py, tests/test_gpu_savgol.py), HILBERT_TABLE_ENTRIES (--hilbert) for nxsig_hilbert_f32
-(tests/test_hilbert_host.py, tests/test_gpu_hilbert.py)."""
+(tests/test_hilbert_host.py, tests/test_gpu_hilbert.py), DCT_TABLE_ENTRIES (--dct) for nxsig_dct_f32 (tests/test_dct_host.py,
+tests/test_gpu_dct.py)."""
 import argparse
 import ctypes as C
 import json
@@ -43,6 +45,7 @@ GOLDEN_IIR = os.path.join(ROOT, "tests", "golden", "abi_error_table_iir.json")
 GOLDEN_PEAKS = os.path.join(ROOT, "tests", "golden", "abi_error_table_find_peaks.json")
 GOLDEN_SAVGOL = os.path.join(ROOT, "tests", "golden", "abi_error_table_savgol.json")
 GOLDEN_HILBERT = os.path.join(ROOT, "tests", "golden", "abi_error_table_hilbert.json")
+GOLDEN_DCT = os.path.join(ROOT, "tests", "golden", "abi_error_table_dct.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -363,6 +366,18 @@ HILBERT_TABLE_ENTRIES = [
       ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16}), ("result too large", {"n_fft": (1 << 31) - 1, "batch": 1 << 30})]),
 ]
 
+# Transforms.dct: 2 rows of 24 samples, zero-padded to 32 points, type 2, norm "ortho" (1), the leading 13 coefficients.  batch = 0 is
+# valid and launches nothing, so it runs with ctx = NULL alone, where it shows that the argument checks let it through to the context
+DCT_TABLE_ENTRIES = [
+    ("nxsig_dct_f32",
+     [("x", "in", _f32(B, HL)), ("length", "v", HL), ("batch", "v", B), ("batch_stride", "v", HL), ("n", "v", 32), ("type", "v", 2), ("norm", "v", 1),
+      ("keep", "v", 13), ("out", "out", np.zeros((B, 13), np.float32)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}, NULL_ONLY), ("batch=-1", {"batch": -1}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": HL - 1}),
+      ("n=0", {"n": 0}), ("n=-1", {"n": -1}), ("n=2^31", {"n": 1 << 31}), ("type=1", {"type": 1}), ("type=4", {"type": 4}), ("type=5", {"type": 5}),
+      ("type=0", {"type": 0}), ("norm=3", {"norm": 3}), ("norm=-1", {"norm": -1}), ("keep=0", {"keep": 0}), ("keep=n+1", {"keep": 33}),
+      ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16}), ("result too large", {"n": (1 << 31) - 1, "batch": 1 << 30})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -479,9 +494,10 @@ def main():
     ap.add_argument("--peaks", action="store_true", help="the entry point of PEAKS_TABLE_ENTRIES (PeakFinding.find_peaks)")
     ap.add_argument("--savgol", action="store_true", help="the entry point of SAVGOL_TABLE_ENTRIES (Filters.savgol_filter)")
     ap.add_argument("--hilbert", action="store_true", help="the entry point of HILBERT_TABLE_ENTRIES (Filters.hilbert)")
+    ap.add_argument("--dct", action="store_true", help="the entry point of DCT_TABLE_ENTRIES (Transforms.dct / idct)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
