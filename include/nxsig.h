@@ -916,6 +916,50 @@ typedef enum nxsig_dct_norm { NXSIG_DCT_BACKWARD = 0, NXSIG_DCT_ORTHO = 1, NXSIG
 int nxsig_dct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch, int64_t batch_stride, int64_t n, int32_t type, int32_t norm,
                   int64_t keep, float* out, int32_t mem);
 
+/*
+ * Filters.lfilter / lfilter_zi / filtfilt — scipy.signal 1.15's transfer-function filter over real f32 rows (the reference has no
+ * recursive filter).  b = f64[nb] and a = f64[na] are HOST pointers, finite, a[0] != 0; both are divided by a[0]
+ * and the shorter is filled up with zeros.  The order is n = max(nb, na) - 1, and a row runs in transposed direct form II,
+ *     y = b0 x + z[0];   z[i] = z[i + 1] + b[i + 1] x - a[i + 1] y  (i < n - 1);   z[n - 1] = b[n] x - a[n] y
+ * with z, n doubles, scipy's zi / zf.  Coefficients, states and the recurrence are double on the device; a sample is widened on load
+ * and an output rounded to f32 once.  n = 0 is a gain.  n > 16 returns NXSIG_ERR_UNSUPPORTED: a recursive filter of such an order belongs
+ * in second-order sections (nxsig_sosfilt_f32), an FIR one (na == 1) in nxsig_fir_f32.
+ *   x [batch][length] rows batch_stride >= length elements apart, y f32[batch][length] dense; x and y must not overlap.
+ *   zi   f64[zi_rows][n] HOST or NULL (zero state); zi_rows is 1 (every row starts alike) or batch; a call that brings it synchronises
+ *        (it is uploaded through scratch, never cached: feeding zf back as zi block after block keeps no table)
+ *   zf_out f64[batch][n] HOST or NULL: the states after the last sample; a call that asks for it synchronises
+ *   direction 0: samples in order; 1: the same filter run from the end of each row towards its start (y[i] still belongs to x[i])
+ * nxsig_filtfilt_f32: scipy.signal.filtfilt(b, a, x, method="pad") in one call, device resident: each row is extended by `edge` samples
+ * per side (padlen < 0: scipy's default 3 max(na, nb); NXSIG_SOS_PAD_NONE: 0), filtered forward from the state lfilter_zi * x_ext[0],
+ * filtered backward from lfilter_zi * y_fwd[last], and the middle `length` samples are kept.  The extension and the forward result are
+ * f32 rows.  padlen >= length is an error, worded as scipy's; so is a filter with a pole at z = 1 (lfilter_zi is singular).
+ * Non-finite rule: outputs ahead of the first Inf / NaN sample of a row are bit for bit those of the row with that sample and
+ * everything after it zeroed; every output from it on is non-finite, because 0 * Inf and 0 * NaN keep every state NaN; a gain (n = 0) runs as an
+ * order-1 filter with zero coefficients and follows the same rule (scipy's gain touches that one sample only).  THAT IS THE
+ * RECURRENCE'S BEHAVIOUR, ALSO FOR na == 1, NOT SCIPY'S: scipy runs such a filter as a convolution, after which a non-finite sample
+ * reaches only the nb outputs whose taps cover it.  Other rows and the gaps between strided rows are untouched.  A zi row with a
+ * non-finite entry counts as a non-finite sample 0.  Under filtfilt such a row is non-finite everywhere.
+ * Deterministic: no atomics, one order of additions; chunk and tile depend on the order only, a row's bits do not depend on the batch.
+ * Dispatch: lfilter.scan (sosfilt's time-parallel scan on the dense n x n companion matrix: chunks of nxsig_lfilter_chunk samples per
+ * lane, tiles of nxsig_lfilter_tile samples per workgroup) and lfilter.generic (one lane per row, the plain recurrence) for rows of at
+ * most one chunk, under NXSIG_DISABLE_LFILTER_SCAN, and for every filter the conditioning guard keeps off the scan: a direct form with
+ * clustered poles (a 20 Hz high-pass of order 4 at 48 kHz, a Bessel low-pass of order 14) has matrix powers too badly conditioned for
+ * the scan while the plain recurrence is still accurate.  The guard is a rule of the normalised (b, a) and the tiles per lane alone:
+ * with G the largest |entry| among A^1 .. A^chunk of the companion matrix A and among the tables, every entry finite,
+ * G x sum |a[k]| <= 1e4, and the table's A^chunk within 1e-11 G of chunk steps of the recurrence.  The tiers agree within tolerance,
+ * not bit for bit.
+ * Every argument check comes ahead of the context.
+ */
+/* samples per lane / per workgroup tile of lfilter.scan for a filter of `order` (0 .. 16); negative status otherwise */
+int32_t nxsig_lfilter_chunk(int32_t order);
+int32_t nxsig_lfilter_tile(int32_t order);
+/* scipy.signal.lfilter_zi: the state of a settled step response, f64[max(nb, na) - 1]; host only */
+int nxsig_lfilter_zi(const double* b, int32_t nb, const double* a, int32_t na, double* zi_out);
+int nxsig_lfilter_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* b, int32_t nb,
+                      const double* a, int32_t na, const double* zi, int32_t zi_rows, double* zf_out, int32_t direction, float* y, int32_t mem);
+int nxsig_filtfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* b, int32_t nb,
+                       const double* a, int32_t na, int32_t padtype, int64_t padlen, float* y, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@ UNITS = [
     ("kernels_savgol.hip", []),  # Filters.savgol_filter: Savitzky-Golay smoothing and derivatives, double sums over an LDS tile
     ("kernels_hilbert.hip", []),  # Filters.hilbert: analytic signal, envelope, quadrature; forward core, gain, inverse core in one wave
     ("kernels_dct.hip", []),  # Transforms.dct / idct (and mfcc): cosine table sums over LDS tiles of rows; Makhoul's form around one row transform
+    ("kernels_lfilter.hip", []),  # Filters.lfilter / filtfilt: a transfer function (b, a) in double, sosfilt's scan on a dense companion matrix
 ]
 
 

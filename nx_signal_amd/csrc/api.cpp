@@ -2454,6 +2454,91 @@ int nxsig_sosfiltfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Filters.lfilter / filtfilt */
+int32_t nxsig_lfilter_chunk(int32_t order) {
+  const int32_t v = lf_chunk(order);
+  return v ? v : set_error(NXSIG_ERR_INVALID_ARG, "lfilter_chunk: order must be in [0, 16]");
+}
+
+int32_t nxsig_lfilter_tile(int32_t order) {
+  const int32_t v = lf_tile(order);
+  return v ? v : set_error(NXSIG_ERR_INVALID_ARG, "lfilter_tile: order must be in [0, 16]");
+}
+
+// what the two entry points check alike, ahead of the context: pointers, mem, the coefficients, the rows
+static int lf_check_common(const char* fn, const void* x, const void* y, const double* b, int32_t nb, const double* a, int32_t na, int32_t mem,
+                           int64_t length, int32_t batch, int64_t batch_stride) {
+  if (!x || !b || !a || !y) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = lf_check_ba(b, nb, a, na, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string(fn) + ": " + what);
+  if (const char* what = lf_check_args(length, batch, batch_stride, 1, false, 0)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(fn) + ": " + what);
+  if (length > INT64_MAX / batch / 16) return set_error(NXSIG_ERR_UNSUPPORTED, std::string(fn) + ": the rows are too large");
+  return NXSIG_OK;
+}
+
+int nxsig_lfilter_zi(const double* b, int32_t nb, const double* a, int32_t na, double* zi_out) {
+  NXSIG_API_BEGIN
+  if (!b || !a || !zi_out) return set_error(NXSIG_ERR_INVALID_ARG, "lfilter_zi: null pointer argument");
+  bool unsupported = false;
+  if (const char* what = lf_check_ba(b, nb, a, na, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("lfilter_zi: ") + what);
+  if (!lf_zi(lf_normalise(b, nb, a, na), zi_out)) return set_error(NXSIG_ERR_INVALID_ARG, "lfilter_zi: singular matrix (the filter has a pole at z = 1)");
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
+int nxsig_lfilter_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* b, int32_t nb,
+                      const double* a, int32_t na, const double* zi, int32_t zi_rows, double* zf_out, int32_t direction, float* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  int rc = lf_check_common("lfilter", x, y, b, nb, a, na, mem, length, batch, batch_stride);
+  if (rc) return rc;
+  if (const char* what = lf_check_args(length, batch, batch_stride, zi_rows, zi != nullptr, direction))
+    return set_error(NXSIG_ERR_INVALID_ARG, std::string("lfilter: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(float)), kScratchNdStageA}},
+                    {{y, (size_t)batch * length * sizeof(float), kScratchNdStageOut}}))) return rc;
+  LfLaunch l;
+  l.x = static_cast<const float*>(io.in[0]); l.n = length; l.x_stride = batch_stride; l.batch = batch;
+  l.cf = lf_normalise(b, nb, a, na);
+  const bool states = l.cf.n > 0;   // a gain has no state: zi and zf_out are empty arrays
+  l.zi_host = states ? zi : nullptr; l.zi_rows = zi ? zi_rows : 1; l.zi_times_first = false;
+  l.zf_host = states ? zf_out : nullptr; l.direction = direction;
+  l.y = static_cast<float*>(io.out[0]); l.y_stride = length; l.out_off = 0; l.out_len = length;
+  if ((rc = launch_lfilter(c, l))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+int nxsig_filtfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* b, int32_t nb,
+                       const double* a, int32_t na, int32_t padtype, int64_t padlen, float* y, int32_t mem) {
+  NXSIG_API_BEGIN
+  int rc = lf_check_common("filtfilt", x, y, b, nb, a, na, mem, length, batch, batch_stride);
+  if (rc) return rc;
+  const int64_t edge = lf_edge(nb, na, padtype, padlen, length);
+  if (edge == -1) return set_error(NXSIG_ERR_INVALID_ARG, "filtfilt: padtype must be NXSIG_SOS_PAD_NONE, _ODD, _EVEN or _CONSTANT");
+  if (edge == -2)
+    return set_error(NXSIG_ERR_INVALID_ARG, "filtfilt: the length of the input vector x must be greater than padlen, which is " +
+                                                std::to_string(padlen < 0 ? lf_default_padlen(nb, na) : padlen));
+  if (length + 2 * edge > INT64_MAX / batch / 16) return set_error(NXSIG_ERR_UNSUPPORTED, "filtfilt: the rows are too large");
+  const LfCoefs cf = lf_normalise(b, nb, a, na);
+  double zi_probe[kLfMaxOrder];
+  if (!lf_zi(cf, zi_probe)) return set_error(NXSIG_ERR_INVALID_ARG, "filtfilt: singular matrix (the filter has a pole at z = 1)");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, rows_bytes(batch, batch_stride, length, sizeof(float)), kScratchNdStageA}},
+                    {{y, (size_t)batch * length * sizeof(float), kScratchNdStageOut}}))) return rc;
+  if ((rc = launch_filtfilt(c, static_cast<const float*>(io.in[0]), length, batch_stride, batch, cf, padtype, edge, static_cast<float*>(io.out[0]))))
+    return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 /* ---------------------------------------------------------------- PeakFinding.find_peaks */
 int32_t nxsig_find_peaks_block(void) { return kFindPeaksBlock; }
 

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -131,12 +131,12 @@ enum ScratchSlot : int {
   kScratchConvNdA = 13,          // n-D fftconvolve: padded A, later the inverse transform's result (kernels_nd.hip)
   kScratchConvNdB = 14,          // n-D fftconvolve: padded B (kernels_nd.hip)
   kScratchConvNdC = 15,          // n-D fftconvolve: the product (kernels_nd.hip)
-  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip); welch / csd: row flags, partial sums, the generic tier's frames (kernels_welch.hip); sosfilt: chunk and tile states, zi, zf (kernels_iir.hip)
+  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip); welch / csd: row flags, partial sums, the generic tier's frames (kernels_welch.hip); sosfilt: chunk and tile states, zi, zf (kernels_iir.hip); lfilter: the same (kernels_lfilter.hip)
   kScratchNdStageA = 17,         // host staging of the n-D / filter / peak / waveform calls: first input; the mask of the masked istft (api.cpp)
   kScratchNdStageB = 18,         // the same: second input; peak finding's `valid` cell (api.cpp)
   kScratchNdStageOut = 19,       // the same: results, several packed at a 256-byte stride (api.cpp)
   kScratchIstftProduct = 20,     // z * H / z * mask of the filtered and masked istft's two-step fall-back (launch_istft, api.cpp); hilbert.generic: the means of the rows that fill the transform, the dense (centred or gathered) rows, later the complex signal ahead of the sink — every output of a centred row, the f32 outputs of the others (kernels_hilbert.hip); dct.fft: the input of its one row transform — the row means and the permuted, centred rows (type 2) or the Hermitian spectra (type 3) (kernels_dct.hip)
-  kScratchFirLong = 21,          // long FIR: full convolution row, partition outputs, delay-line spectra (api.cpp, kernels_wave_firlong.hip); sosfiltfilt: the extended rows and the forward result (kernels_iir.hip)
+  kScratchFirLong = 21,          // long FIR: full convolution row, partition outputs, delay-line spectra (api.cpp, kernels_wave_firlong.hip); sosfiltfilt: the extended rows and the forward result (kernels_iir.hip); filtfilt: the same (kernels_lfilter.hip)
   kScratchFirRowFlags = 22,      // per-row non-finite flags of the FIR kernels (fir_row_flags, kernels_generic.hip)
   kScratchIstftNfList = 23,      // units with a non-finite bin reported by the multi-frame inverse kernels (istft_nf_list, kernels_generic.hip)
   kScratchPackedSpectrum = 24,   // packed istft fall-back: the Hermitian rows written out (launch_istft, api.cpp)
@@ -605,4 +605,31 @@ struct DctLaunch {
   float* out;              // device, dense [batch][keep]
 };
 int launch_dct(Ctx* c, const DctLaunch& a);
+}  // namespace nxsig
+
+#include "lfilter_plan.hpp"
+
+namespace nxsig {
+// kernels_lfilter.hip: Filters.lfilter / filtfilt (include/nxsig.h states the definition, DESIGN.md section 3.18 the design; the argument
+// checks are the caller's).  One run of the filter over `batch` rows, with IirLaunch's conventions: logical sample i of a row is physical
+// sample i (direction 0) or n - 1 - i (direction 1); output sample p (physical) goes to y[row * y_stride + p - out_off] when
+// 0 <= p - out_off < out_len.  Temporaries (chunk and tile states, zi, zf) live in sosfilt's slot kScratchLongStftFrames.  Enqueued on
+// c->stream; only a call that returns zf or brings a zi of the caller's waits
+struct LfLaunch {
+  const float* x;          // device f32[batch][n], rows x_stride elements apart
+  int64_t n, x_stride;
+  int32_t batch;
+  LfCoefs cf;              // b and a divided by a[0], zero-padded; cf.n the order 0 .. kLfMaxOrder
+  const double* zi_host;   // f64[zi_rows][order] or nullptr (zero state)
+  int32_t zi_rows;         // 1 or batch
+  bool zi_times_first;     // the start state of a row is zi * (its first logical sample): filtfilt
+  double* zf_host;         // f64[batch][order] or nullptr
+  int32_t direction;
+  float* y;                // device
+  int64_t y_stride, out_off, out_len;
+};
+int launch_lfilter(Ctx* c, const LfLaunch& a);
+// filtfilt: x rows -> extended rows (padtype 1 odd, 2 even, 3 constant; edge samples each side) in kScratchFirLong, forward, backward,
+// the middle slice to y (dense [batch][n])
+int launch_filtfilt(Ctx* c, const float* x, int64_t n, int64_t x_stride, int32_t batch, const LfCoefs& cf, int32_t padtype, int64_t edge, float* y);
 }  // namespace nxsig

@@ -317,3 +317,5 @@ def sosfiltfilt(x, sos, ctx=None, axis=-1, padtype="odd", padlen=None):
 from ._savgol import savgol_coeffs, savgol_filter  # noqa: E402,F401
 # ... and so does hilbert (_hilbert.py)
 from ._hilbert import hilbert  # noqa: E402,F401
+# ... and the transfer-function filters lfilter / lfilter_zi / filtfilt / lfiltic (_lfilter.py)
+from ._lfilter import filtfilt, lfilter, lfilter_zi, lfiltic  # noqa: E402,F401

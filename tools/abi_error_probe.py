@@ -9,6 +9,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --savgol [--real] [--write tests/golden/abi_error_table_savgol.json]
     python tools/abi_error_probe.py --hilbert [--real] [--write tests/golden/abi_error_table_hilbert.json]
     python tools/abi_error_probe.py --dct [--real] [--write tests/golden/abi_error_table_dct.json]
+    python tools/abi_error_probe.py --lfilter [--real] [--write tests/golden/abi_error_table_lfilter.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -24,7 +25,8 @@ nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TAB
 (tests/test_find_peaks_host.py, tests/test_gpu_find_peaks.py), SAVGOL_TABLE_ENTRIES (--savgol) for nxsig_savgol_filter
 (tests/test_savgol_host.py, tests/test_gpu_savgol.py), HILBERT_TABLE_ENTRIES (--hilbert) for nxsig_hilbert_f32
 (tests/test_hilbert_host.py, tests/test_gpu_hilbert.py), DCT_TABLE_ENTRIES (--dct) for nxsig_dct_f32 (tests/test_dct_host.py,
-tests/test_gpu_dct.py)."""
+tests/test_gpu_dct.py), LFILTER_TABLE_ENTRIES (--lfilter) for nxsig_lfilter_f32 and nxsig_filtfilt_f32 (tests/test_lfilter_host.py,
+tests/test_gpu_lfilter.py)."""
 import argparse
 import ctypes as C
 import json
@@ -46,6 +48,7 @@ GOLDEN_PEAKS = os.path.join(ROOT, "tests", "golden", "abi_error_table_find_peaks
 GOLDEN_SAVGOL = os.path.join(ROOT, "tests", "golden", "abi_error_table_savgol.json")
 GOLDEN_HILBERT = os.path.join(ROOT, "tests", "golden", "abi_error_table_hilbert.json")
 GOLDEN_DCT = os.path.join(ROOT, "tests", "golden", "abi_error_table_dct.json")
+GOLDEN_LFILTER = os.path.join(ROOT, "tests", "golden", "abi_error_table_lfilter.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -378,6 +381,32 @@ DCT_TABLE_ENTRIES = [
       ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16}), ("result too large", {"n": (1 << 31) - 1, "batch": 1 << 30})]),
 ]
 
+# Filters.lfilter / filtfilt: 2 rows of 40 samples through a third-order filter with a[0] = 2 (b, a, zi and zf are host arrays whatever
+# `mem` says)
+_LF_B = np.array([0.2, 0.3, -0.1], np.float64)
+_LF_A = np.array([2.0, -1.0, 0.5, -0.1], np.float64)
+_LF_A0 = _LF_A.copy()
+_LF_A0[0] = 0.0
+_LF_NAN = _LF_B.copy()
+_LF_NAN[1] = np.nan
+_LF_LONG = np.r_[1.0, np.full(17, 0.01)]
+_LF_CASES = [("batch=0", {"batch": 0}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": IL - 1}),
+             ("nb=0", {"nb": 0}), ("na=0", {"na": 0}), ("a[0]=0", {"a": _LF_A0}), ("b not finite", {"b": _LF_NAN}),
+             ("order 17, recursive", {"a": _LF_LONG, "na": 18}), ("order 17, fir", {"b": _LF_LONG, "nb": 18, "a": np.ones(1), "na": 1}),
+             ("rows too large", {"length": 1 << 59, "batch_stride": 1 << 59, "batch": 16})]
+LFILTER_TABLE_ENTRIES = [
+    ("nxsig_lfilter_f32",
+     [("x", "in", _f32(B, IL)), ("length", "v", IL), ("batch", "v", B), ("batch_stride", "v", IL), ("b", "host", _LF_B), ("nb", "v", 3),
+      ("a", "host", _LF_A), ("na", "v", 4), ("zi", "host?", 0.1 * _f32(B, 3).astype(np.float64)), ("zi_rows", "v", B),
+      ("zf_out", "hout?", np.zeros((B, 3), np.float64)), ("direction", "v", 0), ("y", "out", np.zeros((B, IL), np.float32)), ("mem", "mem", None)],
+     _LF_CASES + [("zi_rows=3", {"zi_rows": 3}), ("direction=2", {"direction": 2})]),
+    ("nxsig_filtfilt_f32",
+     [("x", "in", _f32(B, IL)), ("length", "v", IL), ("batch", "v", B), ("batch_stride", "v", IL), ("b", "host", _LF_B), ("nb", "v", 3),
+      ("a", "host", _LF_A), ("na", "v", 4), ("padtype", "v", 1), ("padlen", "v", -1), ("y", "out", np.zeros((B, IL), np.float32)), ("mem", "mem", None)],
+     _LF_CASES + [("padtype=4", {"padtype": 4}), ("padlen=length", {"padlen": IL}), ("default padlen >= length", {"length": 12, "batch_stride": 12}),
+                  ("pole at z=1", {"b": np.ones(1), "nb": 1, "a": np.array([1.0, -1.0]), "na": 2})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -495,9 +524,10 @@ def main():
     ap.add_argument("--savgol", action="store_true", help="the entry point of SAVGOL_TABLE_ENTRIES (Filters.savgol_filter)")
     ap.add_argument("--hilbert", action="store_true", help="the entry point of HILBERT_TABLE_ENTRIES (Filters.hilbert)")
     ap.add_argument("--dct", action="store_true", help="the entry point of DCT_TABLE_ENTRIES (Transforms.dct / idct)")
+    ap.add_argument("--lfilter", action="store_true", help="the entry points of LFILTER_TABLE_ENTRIES (Filters.lfilter / filtfilt)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
