@@ -6,6 +6,7 @@ blocks and pinned staging slots between calls.  Here the calls of tests/context_
 every result must be the words and the dispatch record a context created for that one call gives (context_calls.fresh):
 
   * seeded sequences of every (entry, size, mode) on one context, with refused calls, non-finite twins and dispatch switches between;
+  * every user of a shared scratch slot behind every other user of it (context_calls.user_pairs);
   * the trim of the table cache (NXSIG_TABLE_CACHE_MAX lowered, the default bound crossed for real, a trim inside a sharded call);
   * four threads on one context;
   * host staging of two large operands and of more than two chunks, under NXSIG_HOST_PIPE = 0 / 1 / 3;
@@ -107,6 +108,40 @@ def test_a_long_lived_context_gives_what_a_fresh_one_gives(seed):
     ctx.close()
 
 
+# ------------------------------------------------------------------------------------------------ 2b. the users of a shared slot
+def _pair(ctx, a, b, mode):
+    """A at "large", A's non-finite twin (A again where it has none), then B at "small", on ctx -> "" or how B differs from a fresh context"""
+    A, B = CC.BY_NAME[a], CC.BY_NAME[b]
+    mode_a = mode if mode in A.modes else A.modes[0]
+    CC.run(S, A, "large", mode_a, ctx)
+    CC.run(S, A, "large", mode_a, ctx, twin=bool(A.twin))
+    return CC.same(CC.run(S, B, "small", mode, ctx), CC.fresh(S, B, "small", mode))
+
+
+@pytest.mark.parametrize("slot", sorted(CC.user_pairs()))
+def test_every_user_of_a_shared_slot_after_every_other(slot):
+    """Several families live in one scratch slot, with layouts of their own (nxsig_internal.h: "Two users of one slot ... overwrite each
+    other silently").  A kernel that reads past what its own call wrote, or counts on the slot being zero, picks up the user before it:
+    every ordered pair (A, B) of the slot's claimants (context_calls.THINNED: one claimant per source file) on one long-lived context,
+    B's words and record against a fresh context's"""
+    ctx = S.Context(0)
+    done = []
+    for a, b in CC.user_pairs()[slot]:
+        for mode in CC.MODES[::-1]:   # device mode, then host mode where B has it
+            if mode not in CC.BY_NAME[b].modes:
+                continue
+            diff = _pair(ctx, a, b, mode)
+            if diff:
+                new = S.Context(0)   # do the three calls alone show it, or does it take the pairs before them?
+                alone = _pair(new, a, b, mode)
+                new.close()
+                replay = ("these three calls on a new context replay it" if alone else
+                          f"these three calls on a new context do NOT replay it; the pairs before them on this context: {done[-6:]}")
+                raise AssertionError(f"{slot}: {b} (small, {mode}) after {a} (large, then its {'twin' if CC.BY_NAME[a].twin else 'repeat'}): {diff}\n{replay}")
+            done.append((a, b, mode))
+    ctx.close()
+
+
 # ------------------------------------------------------------------------------------------------ 3. the table-cache trim
 SR = 48000
 
@@ -192,12 +227,14 @@ def test_a_trim_in_the_middle_of_a_sharded_call():
 
 # ------------------------------------------------------------------------------------------------ 4. one context, several threads
 THREADED = ("stft1024", "stft512", "stft400", "istft1024", "istft512-half", "istft1024-masked", "fir257", "mel1024", "dbfs1024", "median-rows",
-            "resample-3-2", "fft1024-rows")
+            "resample-3-2", "fft1024-rows",
+            # users of slots 4, 16 and 20 that came later: they share those slots with each other under the context's mutex
+            "welch400-in-512-generic", "sosfilt-scan", "lfilter-scan-zi-zf", "hilbert1000-generic", "dct400-fft")
 
 
 def test_four_threads_on_one_context():
-    """DESIGN.md promises a mutex per context (dirty schedulers may call concurrently): every thread runs its own order of twelve
-    entries, host and device mode, and checks its own results and its own (thread-local) record"""
+    """DESIGN.md promises a mutex per context (dirty schedulers may call concurrently): every thread runs its own order of the
+    THREADED entries, host and device mode, and checks its own results and its own (thread-local) record"""
     want = {(n, m): CC.fresh(S, CC.BY_NAME[n], "small", m) for n in THREADED for m in CC.MODES}   # computed before the threads start
     ctx = S.Context(0)
     failures = []
