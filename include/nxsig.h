@@ -960,6 +960,39 @@ int nxsig_lfilter_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t ba
 int nxsig_filtfilt_f32(nxsig_ctx* ctx, const float* x, int64_t length, int32_t batch, int64_t batch_stride, const double* b, int32_t nb,
                        const double* a, int32_t na, int32_t padtype, int64_t padlen, float* y, int32_t mem);
 
+/*
+ * Spectral.lombscargle — scipy.signal.lombscargle of SciPy 1.15 (the generalised Lomb-Scargle periodogram, with weights, floating_mean
+ * and the three normalisations), batched over real f32 / f64 rows that share one time base (the reference has no such estimator;
+ * DESIGN.md section 3.19).  x = f64[n] sample times (unsorted is fine), freqs = f64[num_freqs] ANGULAR frequencies (0 allowed) and
+ * weights = f64[n] or NULL (ones) are always HOST pointers and must be finite; weights >= 0 with a positive sum, normalised to sum 1 as
+ * scipy does.  `mem` describes y and out only.
+ *   y [batch][n] rows batch_stride >= n elements apart, dtype NXSIG_DT_F32 or NXSIG_DT_F64
+ *   out [batch][num_freqs] dense: f32 for f32 rows, f64 for f64 rows; c64 / c128 when normalize == 2
+ *   precenter 1: the plain mean of a row is subtracted from it first (on load, never as a correction of finished sums)
+ *   normalize 0 "power": 2 (a YC + b YS) n / 4;  1 "normalize": 2 (a YC + b YS) 0.5 / YY;  2 "amplitude": (a + i b) e^{i tau}
+ *   floating_mean 1: the fitted model carries a constant (the corrections by C, S and Y of scipy's Eq. 8 - 15)
+ * With w the normalised weights and every sum over the row's samples: Y = sum w y, YY = sum w y y, C = sum w cos(wt), S = sum w sin(wt),
+ * CC = sum w cos^2, SS = 1 - CC, CS = sum w cos sin; tau = atan2(2 CS, CC - SS) / 2; YC, YS, CC, SS at the phase wt - tau;
+ * CC and SS are clamped from below at 2^-53 (numpy's finfo(float64).epsneg, for both result types); a = YC / CC, b = YS / SS.
+ * Every sum, tau, the divisions and the normalisation are double on the device; a sample is widened on load and a result rounded to
+ * its type once.  The phase is fl(freqs[k] * x[i]) in double, fed to the double sincos, as numpy does: no f32 phase, no fast intrinsic.
+ * Non-finite rule: a row of y that holds an Inf / NaN is NaN at every frequency (both parts under "amplitude"); a zero weight does
+ * not shield it.  Other rows keep their bits; the gaps between strided rows and everything outside the result are untouched.
+ * Deterministic: no atomics, one order of additions per tier; within a tier the bits of out[r][k] depend neither on the batch nor on
+ * which other rows run beside row r.
+ * Dispatch: lombscargle.tile (a workgroup owns nxsig_lombscargle_block(0) frequencies and (1) rows, walks the time axis in tiles of (2)
+ * samples staged through LDS, one sincos per (t, w) for all its rows; tau from the unshifted sums, which are then rotated by tau
+ * instead of summed again) on every shape and option set; lombscargle.generic (one lane per (row, frequency), scipy's two passes as
+ * written) under NXSIG_LOMBSCARGLE_TILE=0.  A rule of the switch alone, never of the batch.  The tiers agree within tolerance, not bit
+ * for bit.  x, freqs and the normalised weights go through the context's table cache: a repeated call uploads nothing.
+ * Every argument check comes ahead of the context.
+ */
+/* 0: frequencies per workgroup, 1: rows per workgroup, 2: samples per staged tile of lombscargle.tile; negative status otherwise */
+int32_t nxsig_lombscargle_block(int32_t which);
+int nxsig_lombscargle(nxsig_ctx* ctx, const void* y, int32_t dtype, int64_t n, int32_t batch, int64_t batch_stride,
+                      const double* x, const double* freqs, int64_t num_freqs, const double* weights /* or NULL */,
+                      int32_t precenter, int32_t normalize, int32_t floating_mean, void* out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

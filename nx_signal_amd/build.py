@@ -60,6 +60,7 @@ UNITS = [
     ("kernels_hilbert.hip", []),  # Filters.hilbert: analytic signal, envelope, quadrature; forward core, gain, inverse core in one wave
     ("kernels_dct.hip", []),  # Transforms.dct / idct (and mfcc): cosine table sums over LDS tiles of rows; Makhoul's form around one row transform
     ("kernels_lfilter.hip", []),  # Filters.lfilter / filtfilt: a transfer function (b, a) in double, sosfilt's scan on a dense companion matrix
+    ("kernels_lombscargle.hip", []),  # Spectral.lombscargle: periodograms of unevenly sampled rows, one double sincos per (t, w) shared by a block of rows
 ]
 
 

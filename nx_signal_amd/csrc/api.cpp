@@ -2701,3 +2701,41 @@ bool table_requests_query(const Ctx* c, const char* name, int32_t* value, int32_
   return true;
 }
 }  // namespace nxsig
+
+/* ---------------------------------------------------------------- Spectral.lombscargle */
+extern "C" {
+
+int32_t nxsig_lombscargle_block(int32_t which) {
+  const int32_t v = ls_block(which);
+  return v ? v : set_error(NXSIG_ERR_INVALID_ARG, "lombscargle_block: which must be 0 (frequencies), 1 (rows) or 2 (samples per tile)");
+}
+
+int nxsig_lombscargle(nxsig_ctx* ctx, const void* y, int32_t dtype, int64_t n, int32_t batch, int64_t batch_stride, const double* x,
+                      const double* freqs, int64_t num_freqs, const double* weights, int32_t precenter, int32_t normalize, int32_t floating_mean,
+                      void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!y || !x || !freqs || !out) return set_error(NXSIG_ERR_INVALID_ARG, "lombscargle: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = ls_check_shape(dtype, n, batch, batch_stride, num_freqs, precenter, normalize, floating_mean, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("lombscargle: ") + what);
+  if (const char* what = ls_check_arrays(x, n, freqs, num_freqs, weights)) return set_error(NXSIG_ERR_INVALID_ARG, std::string("lombscargle: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  const size_t es = dtype == NXSIG_DT_F64 ? sizeof(double) : sizeof(float);
+  HostIo io(c, mem);
+  if ((rc = io.open({{y, rows_bytes(batch, batch_stride, n, es), kScratchNdStageA}},
+                    {{out, (size_t)batch * num_freqs * ls_out_elem(dtype, normalize), kScratchNdStageOut}}))) return rc;
+  LsLaunch a;
+  a.y = io.in[0]; a.f64 = dtype == NXSIG_DT_F64; a.n = n; a.y_stride = batch_stride; a.batch = batch;
+  a.x_host = x; a.freqs_host = freqs; a.num_freqs = num_freqs; a.weights_host = weights;
+  a.precenter = precenter; a.normalize = normalize; a.floating_mean = floating_mean;
+  a.out = io.out[0];
+  if ((rc = launch_lombscargle(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+}  // extern "C"

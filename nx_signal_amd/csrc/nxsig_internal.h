@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(LOMBSCARGLE_TILE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -632,4 +632,25 @@ int launch_lfilter(Ctx* c, const LfLaunch& a);
 // filtfilt: x rows -> extended rows (padtype 1 odd, 2 even, 3 constant; edge samples each side) in kScratchFirLong, forward, backward,
 // the middle slice to y (dense [batch][n])
 int launch_filtfilt(Ctx* c, const float* x, int64_t n, int64_t x_stride, int32_t batch, const LfCoefs& cf, int32_t padtype, int64_t edge, float* y);
+}  // namespace nxsig
+
+#include "lombscargle_plan.hpp"
+
+namespace nxsig {
+// kernels_lombscargle.hip: Spectral.lombscargle (include/nxsig.h states the definition, DESIGN.md section 3.19 the design; the argument
+// checks are the caller's).  x, freqs and the weights are HOST arrays: they reach the device through ctx_table, the weights normalised
+// to sum 1 (ones where weights_host is null).  No scratch.  Enqueued on c->stream; nothing waits once the tables are cached
+struct LsLaunch {
+  const void* y;             // device f32 / f64 [batch][n], rows y_stride elements apart
+  bool f64;
+  int64_t n, y_stride;
+  int32_t batch;
+  const double* x_host;      // f64[n]
+  const double* freqs_host;  // f64[num_freqs], angular
+  int64_t num_freqs;
+  const double* weights_host;   // f64[n] or nullptr
+  int32_t precenter, normalize, floating_mean;
+  void* out;                 // device, dense [batch][num_freqs]: f32 / f64, c64 / c128 under kLsAmplitude
+};
+int launch_lombscargle(Ctx* c, const LsLaunch& a);
 }  // namespace nxsig

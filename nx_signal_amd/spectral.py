@@ -129,3 +129,7 @@ def coherence(x, y, window, ctx=None, **opts):
         num = pxy.real.astype(np.float64) ** 2 + pxy.imag.astype(np.float64) ** 2
         cxy = (num / (pxx.astype(np.float64) * pyy.astype(np.float64))).astype(np.float32)
     return f, (DeviceBuffer.from_numpy(c, cxy) if device else cxy)
+
+
+# lombscargle lives in a module of its own (_lombscargle.py)
+from ._lombscargle import lombscargle  # noqa: E402,F401

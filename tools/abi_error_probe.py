@@ -10,6 +10,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --hilbert [--real] [--write tests/golden/abi_error_table_hilbert.json]
     python tools/abi_error_probe.py --dct [--real] [--write tests/golden/abi_error_table_dct.json]
     python tools/abi_error_probe.py --lfilter [--real] [--write tests/golden/abi_error_table_lfilter.json]
+    python tools/abi_error_probe.py --lombscargle [--real] [--write tests/golden/abi_error_table_lombscargle.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -26,7 +27,8 @@ nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TAB
 (tests/test_savgol_host.py, tests/test_gpu_savgol.py), HILBERT_TABLE_ENTRIES (--hilbert) for nxsig_hilbert_f32
 (tests/test_hilbert_host.py, tests/test_gpu_hilbert.py), DCT_TABLE_ENTRIES (--dct) for nxsig_dct_f32 (tests/test_dct_host.py,
 tests/test_gpu_dct.py), LFILTER_TABLE_ENTRIES (--lfilter) for nxsig_lfilter_f32 and nxsig_filtfilt_f32 (tests/test_lfilter_host.py,
-tests/test_gpu_lfilter.py)."""
+tests/test_gpu_lfilter.py), LOMBSCARGLE_TABLE_ENTRIES (--lombscargle) for nxsig_lombscargle (tests/test_lombscargle_host.py,
+tests/test_gpu_lombscargle.py)."""
 import argparse
 import ctypes as C
 import json
@@ -49,6 +51,7 @@ GOLDEN_SAVGOL = os.path.join(ROOT, "tests", "golden", "abi_error_table_savgol.js
 GOLDEN_HILBERT = os.path.join(ROOT, "tests", "golden", "abi_error_table_hilbert.json")
 GOLDEN_DCT = os.path.join(ROOT, "tests", "golden", "abi_error_table_dct.json")
 GOLDEN_LFILTER = os.path.join(ROOT, "tests", "golden", "abi_error_table_lfilter.json")
+GOLDEN_LOMBSCARGLE = os.path.join(ROOT, "tests", "golden", "abi_error_table_lombscargle.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -407,6 +410,32 @@ LFILTER_TABLE_ENTRIES = [
                   ("pole at z=1", {"b": np.ones(1), "nb": 1, "a": np.array([1.0, -1.0]), "na": 2})]),
 ]
 
+# Spectral.lombscargle: 2 rows of 40 samples at 5 angular frequencies, weighted, precentred (x, freqs and weights are host arrays whatever
+# `mem` says; weights may be NULL)
+_LS_X = np.sort(_rng.uniform(0.0, 10.0, IL))
+_LS_F = np.array([0.0, 0.5, 1.0, 2.5, 7.0], np.float64)
+_LS_W = _rng.uniform(0.5, 2.0, IL)
+
+
+def _ls_broken(arr, at, value):
+    out = arr.copy()
+    out[at] = value
+    return out
+
+
+LOMBSCARGLE_TABLE_ENTRIES = [
+    ("nxsig_lombscargle",
+     [("y", "in", _f32(B, IL)), ("dtype", "v", 0), ("n", "v", IL), ("batch", "v", B), ("batch_stride", "v", IL), ("x", "host", _LS_X),
+      ("freqs", "host", _LS_F), ("num_freqs", "v", 5), ("weights", "host?", _LS_W), ("precenter", "v", 1), ("normalize", "v", 0),
+      ("floating_mean", "v", 0), ("out", "out", np.zeros((B, 5), np.float32)), ("mem", "mem", None)],
+     [("dtype=2", {"dtype": 2}), ("n=0", {"n": 0}), ("num_freqs=0", {"num_freqs": 0}), ("batch=0", {"batch": 0}),
+      ("batch_stride=n-1", {"batch_stride": IL - 1}), ("precenter=2", {"precenter": 2}), ("normalize=3", {"normalize": 3}),
+      ("floating_mean=-1", {"floating_mean": -1}), ("rows too large", {"n": 1 << 59, "batch_stride": 1 << 59, "batch": 16}),
+      ("x not finite", {"x": _ls_broken(_LS_X, 3, np.inf)}), ("freqs not finite", {"freqs": _ls_broken(_LS_F, 1, np.nan)}),
+      ("weights not finite", {"weights": _ls_broken(_LS_W, 0, np.nan)}), ("negative weight", {"weights": _ls_broken(_LS_W, 2, -1.0)}),
+      ("zero weights", {"weights": np.zeros(IL)})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -525,9 +554,10 @@ def main():
     ap.add_argument("--hilbert", action="store_true", help="the entry point of HILBERT_TABLE_ENTRIES (Filters.hilbert)")
     ap.add_argument("--dct", action="store_true", help="the entry point of DCT_TABLE_ENTRIES (Transforms.dct / idct)")
     ap.add_argument("--lfilter", action="store_true", help="the entry points of LFILTER_TABLE_ENTRIES (Filters.lfilter / filtfilt)")
+    ap.add_argument("--lombscargle", action="store_true", help="the entry point of LOMBSCARGLE_TABLE_ENTRIES (Spectral.lombscargle)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
