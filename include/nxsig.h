@@ -993,6 +993,55 @@ int nxsig_lombscargle(nxsig_ctx* ctx, const void* y, int32_t dtype, int64_t n, i
                       const double* x, const double* freqs, int64_t num_freqs, const double* weights /* or NULL */,
                       int32_t precenter, int32_t normalize, int32_t floating_mean, void* out, int32_t mem);
 
+/*
+ * Transforms.czt / zoom_fft — scipy.signal.czt and zoom_fft of SciPy 1.15 over real f32 or c64 rows: the chirp z-transform, a DFT of
+ * any length, any start and any step, and the narrow-band zoom built on it.  The reference has neither; DESIGN.md section 3.20.
+ * THE DEFINITION: for a row x[0 .. n) (n = length) and m output points
+ *     X[k] = sum_{j<n} x[j] a^(-j) w^(j k),   k = 0 .. m - 1,
+ *     w = w_abs exp(-2 pi i w_step / w_den),   a = a_abs exp(2 pi i a_turns).
+ * Angles are carried as turns, and the step as a double over a positive integer, so that every phase the transform needs, such as
+ * k^2 w_step / (2 w_den), is reduced mod 1 in integer arithmetic before it meets a sine (csrc/czt_plan.hpp: a 128-bit binary fraction
+ * and a wrapping product; what is lost is under 2^-66 of a turn).  SciPy's ZoomFFT forms exp(-i pi scale k^2 / m) from an unreduced
+ * double and loses the tail of long rows; that is not copied.  How SciPy's three calls map onto the definition:
+ *     czt(x, m)                        w_abs 1, w_step 1, w_den m, a_abs 1, a_turns 0
+ *     czt(x, m, w, a)                  w_abs |w|, w_step -arg(w) / 2 pi, w_den 1, a_abs |a|, a_turns arg(a) / 2 pi
+ *     zoom_fft(x, [f1, f2], m, fs)     w_abs 1, w_step scale, w_den m, a_abs 1, a_turns f1 / fs;  scale = (f2 - f1) / fs, or
+ *                                      (f2 - f1) m / (fs (m - 1)) with endpoint, exactly as SciPy computes it
+ * x [batch][length] rows batch_stride >= length elements apart, f32 (is_complex 0) or c64 (is_complex 1); out c64 [batch][m], dense;
+ * x and out must not overlap.  batch = 0 succeeds and launches nothing.
+ * Both dispatch families are Bluestein's identity j k = (j^2 + k^2 - (k - j)^2) / 2 over three tables formed on the host in double and
+ * rounded to f32 once (nxsig_czt_tables returns them as doubles):
+ *     A[j] = a^(-j) w^(j^2 / 2), j < n         applied to the samples
+ *     F    = DFT_L(v) / L,  v[j mod L] = w^(-j^2 / 2) for j in (-n, m), zero elsewhere;  L a power of two >= n + m - 1
+ *     W[k] = w^(k^2 / 2), k < m                applied to the first m points of IDFT_L(DFT_L(x A) F) (the inverse without its 1 / L)
+ * czt.wave (n + m - 1 <= 2048: L = 1024 when n + m - 1 fits, else 2048; one wave per row, both transforms and the three products in
+ * registers and LDS, the row read once and the result written once) and czt.generic (everything else, and everything under
+ * NXSIG_CZT_WAVE=0 or NXSIG_DISABLE_WAVE: L the next power of two, nxsig_fft's row transforms around the three products, the padded rows
+ * in two temporaries the context keeps).  Both are single-precision transforms: a row is within 1e-5 max|X| of the definition
+ * evaluated in double; the two families need not agree to the bit.  No atomics; a row's bits do not depend on the batch.  The tables
+ * are cached per context by content; a repeated call forms nothing again.
+ * Spirals: |w| != 1 or |a| != 1 is accepted while the spread max|t| / min|t| of each of A, v and W stays within 32 (the gate is
+ * measured: csrc/czt_plan.hpp); beyond it the call is NXSIG_ERR_UNSUPPORTED, "czt: the contour leaves single
+ * precision".
+ * Non-finite rule: a row that holds an Inf / NaN among its n samples has no finite output element; which of NaN / Inf comes out is not
+ * specified.  The rule is carried out on bin 0 of the forward transform, the sum of the chirped samples: when it is not finite the
+ * whole spectrum of the row is replaced by NaN.  No other row of the batch is affected; rows never share a transform.
+ * Limits: n, m >= 1, w_den >= 1, w_abs and a_abs positive and finite, w_step and a_turns finite, batch_stride >= length.  n + m - 1 over
+ * 2^30, w_den over 2^61, lengths the row transforms of nxsig_fft refuse and rows whose byte counts overflow are NXSIG_ERR_UNSUPPORTED.
+ * Not built: f64 / c128 rows (there is no double tier), device tensors along another axis than the last, sharded entry points, NIF
+ * and Elixir functions.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+/* L of the family the shape takes by default (1024 or 2048 while n + m - 1 <= 2048, else the next power of two); negative status
+ * for n < 1, m < 1 or n + m - 1 > 2^30.  Host only, no context */
+int64_t nxsig_czt_conv_length(int64_t n, int64_t m);
+/* the three tables as interleaved complex doubles: A f64[2 n], F f64[2 L], W f64[2 m]; L a power of two >= n + m - 1; *spread (or
+ * NULL) receives the contour's spread, also when it is refused.  Host only, no context */
+int nxsig_czt_tables(int64_t n, int64_t m, int64_t L, double w_abs, double w_step, int64_t w_den, double a_abs, double a_turns,
+                     double* A, double* F, double* W, double* spread);
+int nxsig_czt(nxsig_ctx* ctx, const void* x, int32_t is_complex, int64_t length, int64_t batch, int64_t batch_stride, int64_t m,
+              double w_abs, double w_step, int64_t w_den, double a_abs, double a_turns, void* out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2739,3 +2739,58 @@ int nxsig_lombscargle(nxsig_ctx* ctx, const void* y, int32_t dtype, int64_t n, i
 }
 
 }  // extern "C"
+
+/* ---------------------------------------------------------------- Transforms.czt / zoom_fft */
+extern "C" {
+
+int64_t nxsig_czt_conv_length(int64_t n, int64_t m) {
+  if (n < 1 || m < 1) return set_error(NXSIG_ERR_INVALID_ARG, "czt_conv_length: n and m must be >= 1");
+  if (n > ((int64_t)1 << 30) || m > ((int64_t)1 << 30) || czt_need(n, m) > ((int64_t)1 << 30))
+    return set_error(NXSIG_ERR_UNSUPPORTED, "czt_conv_length: n + m - 1 must be at most 2^30");
+  return czt_conv_length(n, m, false);
+}
+
+int nxsig_czt_tables(int64_t n, int64_t m, int64_t L, double w_abs, double w_step, int64_t w_den, double a_abs, double a_turns,
+                     double* A, double* F, double* W, double* spread) {
+  NXSIG_API_BEGIN
+  if (!A || !F || !W) return set_error(NXSIG_ERR_INVALID_ARG, "czt_tables: null pointer argument");
+  const CztContour k{w_abs, w_step, w_den, a_abs, a_turns};
+  bool unsupported = false;
+  if (const char* what = czt_check(0, n, 1, n, m, k, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("czt_tables: ") + what);
+  if (!czt_is_pow2(L) || L < czt_need(n, m) || L > ((int64_t)1 << 30))
+    return set_error(NXSIG_ERR_INVALID_ARG, "czt_tables: L must be a power of two >= n + m - 1");
+  if (const char* what = czt_tables(n, m, L, k, A, F, W, spread)) return set_error(NXSIG_ERR_UNSUPPORTED, std::string("czt: ") + what);
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
+int nxsig_czt(nxsig_ctx* ctx, const void* x, int32_t is_complex, int64_t length, int64_t batch, int64_t batch_stride, int64_t m,
+              double w_abs, double w_step, int64_t w_den, double a_abs, double a_turns, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !out) return set_error(NXSIG_ERR_INVALID_ARG, "czt: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  const CztContour k{w_abs, w_step, w_den, a_abs, a_turns};
+  bool unsupported = false;
+  if (const char* what = czt_check(is_complex, length, batch, batch_stride, m, k, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("czt: ") + what);
+  if (!(czt_spread(length, m, k) <= kCztSpreadGate)) return set_error(NXSIG_ERR_UNSUPPORTED, "czt: the contour leaves single precision");
+  const size_t es = is_complex ? sizeof(float2) : sizeof(float);
+  const size_t x_bytes = batch ? ((size_t)(batch - 1) * batch_stride + length) * es : 0, out_bytes = (size_t)batch * m * sizeof(float2);
+  if (czt_overlap(x, x_bytes, out, out_bytes)) return set_error(NXSIG_ERR_INVALID_ARG, "czt: x and out must not overlap");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, x_bytes, kScratchNdStageA}}, {{out, out_bytes, kScratchNdStageOut}}))) return rc;
+  CztLaunch a;
+  a.x = io.in[0]; a.is_complex = is_complex != 0; a.length = length; a.x_stride = batch_stride; a.batch = batch; a.m = m; a.contour = k;
+  a.out = io.out[0];
+  if ((rc = launch_czt(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+}  // extern "C"

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(LOMBSCARGLE_TILE)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(LOMBSCARGLE_TILE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -205,10 +205,10 @@ struct Ctx {
   // DMA of chunk k + 1 into one slot while host threads copy chunk k out of the other into the caller's (pageable) buffer
   // (Staged::out_copy, api.cpp); created on the first host-tensor call of at least kPinMin bytes, freed with the context
   void* pin[4] = {nullptr, nullptr, nullptr, nullptr};   // [0, 1] device -> host, [2, 3] host -> device
-  size_t pin_bytes = 0;
-  hipStream_t xfer_stream = nullptr;
-  hipEvent_t xfer_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t xfer_ready = nullptr;
+  size_t pin_bytes = 0; hipStream_t xfer_stream = nullptr;
+  hipEvent_t xfer_ev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t xfer_ready = nullptr;
+  // czt.generic's two temporaries (kernels_czt.hip), its own: grown on demand like a scratch slot, kept from call to call, freed with the context
+  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra;
   std::string last_dispatch;                // kernel families of the last compute call on this context (nxsig_ctx_last_dispatch)
   Tuning tuning;                            // dispatch / geometry switches (environment at creation, nxsig_ctx_set_tuning later)
 };
@@ -653,4 +653,23 @@ struct LsLaunch {
   void* out;                 // device, dense [batch][num_freqs]: f32 / f64, c64 / c128 under kLsAmplitude
 };
 int launch_lombscargle(Ctx* c, const LsLaunch& a);
+}  // namespace nxsig
+
+#include "czt_plan.hpp"
+
+namespace nxsig {
+// kernels_czt.hip: Transforms.czt / zoom_fft over device rows (include/nxsig.h states the definition, DESIGN.md section 3.20 the design;
+// the argument checks are the caller's).  czt.wave uses no temporary; czt.generic keeps two of its own (Ctx::czt_rows: the chirped
+// zero-padded rows, later their spectra times F; Ctx::czt_spectra: the two transforms' results).  The three tables go through ctx_table once per
+// context and parameter set (a memo keeps the pointers: a repeated call makes no table request).  Everything is enqueued on c->stream
+// and nothing waits once the tables are cached
+struct CztLaunch {
+  const void* x;           // device f32 / c64 [batch][length], rows x_stride elements apart
+  bool is_complex;
+  int64_t length, x_stride, batch;
+  int64_t m;               // output points
+  CztContour contour;
+  void* out;               // device, dense c64 [batch][m]
+};
+int launch_czt(Ctx* c, const CztLaunch& a);
 }  // namespace nxsig

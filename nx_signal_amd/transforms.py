@@ -82,3 +82,5 @@ def ifft_nd(tensor, ctx=None, **opts):
 
 # dct / idct live in a module of their own (_dct.py) and are part of this one's interface
 from ._dct import dct, idct  # noqa: E402,F401
+# ... and so do czt / zoom_fft / czt_points (_czt.py)
+from ._czt import czt, czt_points, zoom_fft  # noqa: E402,F401

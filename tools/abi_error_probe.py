@@ -11,6 +11,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --dct [--real] [--write tests/golden/abi_error_table_dct.json]
     python tools/abi_error_probe.py --lfilter [--real] [--write tests/golden/abi_error_table_lfilter.json]
     python tools/abi_error_probe.py --lombscargle [--real] [--write tests/golden/abi_error_table_lombscargle.json]
+    python tools/abi_error_probe.py --czt [--real] [--write tests/golden/abi_error_table_czt.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -28,7 +29,7 @@ nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TAB
 (tests/test_hilbert_host.py, tests/test_gpu_hilbert.py), DCT_TABLE_ENTRIES (--dct) for nxsig_dct_f32 (tests/test_dct_host.py,
 tests/test_gpu_dct.py), LFILTER_TABLE_ENTRIES (--lfilter) for nxsig_lfilter_f32 and nxsig_filtfilt_f32 (tests/test_lfilter_host.py,
 tests/test_gpu_lfilter.py), LOMBSCARGLE_TABLE_ENTRIES (--lombscargle) for nxsig_lombscargle (tests/test_lombscargle_host.py,
-tests/test_gpu_lombscargle.py)."""
+tests/test_gpu_lombscargle.py), CZT_TABLE_ENTRIES (--czt) for nxsig_czt (tests/test_czt_host.py, tests/test_gpu_czt.py)."""
 import argparse
 import ctypes as C
 import json
@@ -52,6 +53,7 @@ GOLDEN_HILBERT = os.path.join(ROOT, "tests", "golden", "abi_error_table_hilbert.
 GOLDEN_DCT = os.path.join(ROOT, "tests", "golden", "abi_error_table_dct.json")
 GOLDEN_LFILTER = os.path.join(ROOT, "tests", "golden", "abi_error_table_lfilter.json")
 GOLDEN_LOMBSCARGLE = os.path.join(ROOT, "tests", "golden", "abi_error_table_lombscargle.json")
+GOLDEN_CZT = os.path.join(ROOT, "tests", "golden", "abi_error_table_czt.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -436,6 +438,22 @@ LOMBSCARGLE_TABLE_ENTRIES = [
       ("zero weights", {"weights": np.zeros(IL)})]),
 ]
 
+# Transforms.czt: 2 rows of 24 real samples, 13 points of a zoom (w = exp(-2 pi i 0.4 / 13), a = exp(2 pi i 0.05)).  batch = 0 is valid
+# and launches nothing, so it runs with ctx = NULL alone, where it shows that the argument checks let it through to the context
+CZT_TABLE_ENTRIES = [
+    ("nxsig_czt",
+     [("x", "in", _f32(B, HL)), ("is_complex", "v", 0), ("length", "v", HL), ("batch", "v", B), ("batch_stride", "v", HL), ("m", "v", 13),
+      ("w_abs", "v", 1.0), ("w_step", "v", 0.4), ("w_den", "v", 13), ("a_abs", "v", 1.0), ("a_turns", "v", 0.05),
+      ("out", "out", np.zeros((B, 13), np.complex64)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}, NULL_ONLY), ("batch=-1", {"batch": -1}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": HL - 1}),
+      ("m=0", {"m": 0}), ("m=-1", {"m": -1}), ("is_complex=2", {"is_complex": 2}), ("w_den=0", {"w_den": 0}), ("w_den=2^62", {"w_den": 1 << 62}),
+      ("w_abs=0", {"w_abs": 0.0}), ("w_abs=-1", {"w_abs": -1.0}), ("w_abs=inf", {"w_abs": float("inf")}), ("w_abs=nan", {"w_abs": float("nan")}),
+      ("a_abs=0", {"a_abs": 0.0}), ("a_abs=inf", {"a_abs": float("inf")}), ("w_step=nan", {"w_step": float("nan")}),
+      ("a_turns=inf", {"a_turns": float("inf")}), ("n+m-1=2^30+1", {"m": (1 << 30) - HL + 2}), ("m=2^31", {"m": 1 << 31}),
+      ("spiral beyond the gate", {"w_abs": 1.02}), ("start beyond the gate", {"a_abs": 1.2}),
+      ("rows too large", {"length": 1 << 29, "batch_stride": 1 << 59, "batch": 16}), ("result too large", {"batch": 1 << 40})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -555,9 +573,10 @@ def main():
     ap.add_argument("--dct", action="store_true", help="the entry point of DCT_TABLE_ENTRIES (Transforms.dct / idct)")
     ap.add_argument("--lfilter", action="store_true", help="the entry points of LFILTER_TABLE_ENTRIES (Filters.lfilter / filtfilt)")
     ap.add_argument("--lombscargle", action="store_true", help="the entry point of LOMBSCARGLE_TABLE_ENTRIES (Spectral.lombscargle)")
+    ap.add_argument("--czt", action="store_true", help="the entry point of CZT_TABLE_ENTRIES (Transforms.czt / zoom_fft)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, CZT_TABLE_ENTRIES if a.czt else LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
