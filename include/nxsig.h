@@ -711,8 +711,11 @@ int nxsig_timer_laps(nxsig_ctx* ctx, float* intervals_ms, int32_t capacity, int3
  * Non-finite rule: a row (for csd: the pair x_r, y_r) with an Inf / NaN inside the samples its M frames cover gives NaN in EVERY bin
  * of every result of that row — Pxx of a row whose y holds the NaN included; a non-finite sample in the dropped tail, in the gap
  * between rows or in another row reaches nothing.
- * Deterministic: partial sums per (row, run of frames) are stored and added in ascending run order, no atomics; a row's bits do not
- * depend on the other rows of the call.
+ * Deterministic: partial sums per (row, run of frames) are stored and added in ascending run order, no atomics.  The same call gives
+ * the same bits every time, and rows of equal content within one call get equal bits.  Across batch sizes welch.generic / csd.generic
+ * keep a row's bits (their runs are 64 frames whatever the batch); welch.pair / csd.pair size their runs from rows x frames of the
+ * whole call and sum a run in f32, so there a row of another batch size agrees within tolerance, not bit for bit — unless its
+ * frames fit one run or the runs are the shortest ones (four units) in both calls.
  * Dispatch: welch.pair / csd.pair (fft_length 1024 and 2048: wave-private transforms, the spectrum never reaches memory),
  * welch.generic / csd.generic for every other length and under NXSIG_DISABLE_WELCH_WAVE.  The tiers agree within tolerance, not bit
  * for bit.

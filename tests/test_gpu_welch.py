@@ -152,7 +152,9 @@ def test_one_long_row_is_split_over_many_runs(ctx):
 @pytest.mark.parametrize("tier", ["generic", "pair"])
 def test_rows_past_the_grid_limit(ctx, tier):
     """65 537 rows: 251 distinct rows repeated — the small call is held to the oracle, every row of the large one to the small call's bits
-    (with one frame, or a row's own frame count below a run, the run geometry of a row does not depend on the batch)"""
+    (with one frame, or a row's own frame count below a run, the run geometry of a row does not depend on the batch; where it does —
+    welch.pair / csd.pair with runs longer than four units — the bits change with the batch and the contract is tolerance:
+    tests/test_gpu_call_size.py test_welch_and_csd_runs_longer_than_four_units)"""
     n, k, length, overlap = (64, 64, 96, 32) if tier == "generic" else (1024, 1024, 1024, 512)
     base, w = noise(65537, (251, length)), hann(n)
     o = dict(overlap_length=overlap, fft_length=k)
