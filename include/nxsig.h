@@ -1045,6 +1045,54 @@ int nxsig_czt_tables(int64_t n, int64_t m, int64_t L, double w_abs, double w_ste
 int nxsig_czt(nxsig_ctx* ctx, const void* x, int32_t is_complex, int64_t length, int64_t batch, int64_t batch_stride, int64_t m,
               double w_abs, double w_step, int64_t w_den, double a_abs, double a_turns, void* out, int32_t mem);
 
+/*
+ * Filters.fir_bank / Transforms.cwt — a bank of S FIR filters of different lengths over real f32 rows, and the continuous wavelet
+ * transform that is one instance of it: scipy.signal.cwt, morlet2 and ricker as SciPy <= 1.14 had them (1.15 removed them, so the
+ * definition is written down here).  The reference has neither; DESIGN.md section 3.21.
+ * THE DEFINITION: for a row x[0 .. L) (L = length) and a filter h of N taps
+ *     full[n] = sum_k x[k] h[n - k],          out[s][n] = full[n + (N - 1) / 2],  0 <= n < L   ("same" alignment, integer division)
+ * which for N <= L is numpy.convolve(x, h, "same").  nxsig_fir_bank takes the filters as they are.  nxsig_cwt builds, per width a,
+ *     N   = min(ceil(10 a), L)                (SciPy passed the unrounded 10 a to arange: the same count)
+ *     h_a = conj(wavelet(N, a))[::-1]
+ *     morlet2(M, s, w): t = (arange(M) - (M - 1) / 2) / s,  sqrt(1 / s) pi^(-1/4) exp(i w t) exp(-t^2 / 2)             complex
+ *     ricker(M, a):     v = arange(M) - (M - 1) / 2,        2 / (sqrt(3 a) pi^(1/4)) (1 - v^2 / a^2) exp(-v^2 / (2 a^2))  real
+ * evaluated on the host in double and rounded to f32 once (nxsig_cwt_wavelet returns the doubles), and runs the same launcher.
+ * x [batch][length] rows batch_stride >= length elements apart, any 4-byte address; taps a HOST array, the S filters concatenated, f32
+ * (taps_complex 0) or c64 (1); tap_counts HOST int64[S]; out dense [batch][S][length], c64 for NXSIG_CWT_COMPLEX, f32 for
+ * NXSIG_CWT_REAL (the real part), NXSIG_CWT_MAGNITUDE (sqrtf(re re + im im), the expression of nxsig_hilbert's envelope) and
+ * NXSIG_CWT_POWER (re re + im im).  x and out must not overlap.
+ * The bank is split by support and one launch group runs per non-empty class; nxsig_last_dispatch names the classes that ran:
+ *     cwt.wave     N <= 513 at K = 1024 points, 514 <= N <= 1025 at K = 2048: overlap-save inside one wave.  A block of K samples is
+ *                  loaded and transformed ONCE; per filter of the class the spectrum is multiplied by H_s / K, inverted and the
+ *                  block's valid run of out[row][s] stored through the sink.  Block step K - Nmax + 1, one per class.  H_s is the
+ *                  K-point spectrum of the taps, formed in double and rounded once, cached per context (a repeated call forms nothing)
+ *     cwt.generic  N > 1025, and everything under NXSIG_CWT_WAVE=0 or NXSIG_DISABLE_WAVE: the rows zero-padded to the next power of
+ *                  two >= L + Nmax - 1 and transformed once by nxsig_fft's row transforms; per filter a product, the transform back and
+ *                  a slice-and-sink kernel; three temporaries the context keeps
+ * Both are single-precision: per (row, filter) the result is within 1e-5 max|out| of the definition in double, except where the output
+ * cancels against a large offset of the row (then 1e-5 max|x| sum|h_s|).  The classes need not agree to the bit.  No atomics.
+ * Non-finite rule (nxsig_fir's): a row that holds an Inf / NaN has no finite output element at any filter; every other row of the
+ * batch keeps its bits.  A kernel that loads such a sample raises the row's flag; a last pass writes NaN over flagged rows.
+ * Limits, each refused with its own message ahead of the context: batch in [1, 65535], num_filters in [1, 4096], every tap count >= 1,
+ * length + max taps - 1 <= 2^24 (NXSIG_ERR_UNSUPPORTED), widths positive and finite, taps finite, batch_stride >= length.
+ * Not built: f64 or complex rows, "full" / "valid" alignment (ragged), a 4096-point wave class, sharded entry points, NIF and Elixir
+ * functions.  A device call returns without waiting.
+ */
+#define NXSIG_CWT_COMPLEX 0
+#define NXSIG_CWT_REAL 1
+#define NXSIG_CWT_MAGNITUDE 2
+#define NXSIG_CWT_POWER 3
+#define NXSIG_CWT_MORLET2 0
+#define NXSIG_CWT_RICKER 1
+/* N = min(ceil(10 width), length); negative status for a width that is not positive and finite or length < 1.  Host only, no context */
+int64_t nxsig_cwt_support(double width, int64_t length);
+/* conj(wavelet(N, width))[::-1] as N interleaved complex doubles (w: morlet2's omega, ignored by ricker).  Host only, no context */
+int nxsig_cwt_wavelet(int32_t wavelet, double width, double w, int64_t N, double* out_f64);
+int nxsig_fir_bank(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int64_t batch_stride, const void* taps, int32_t taps_complex,
+                   const int64_t* tap_counts, int64_t num_filters, int32_t kind, void* out, int32_t mem);
+int nxsig_cwt(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int64_t batch_stride, int32_t wavelet, const double* widths,
+              int64_t num_widths, double w, int32_t kind, void* out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,7 @@ UNITS = [
     ("kernels_lfilter.hip", []),  # Filters.lfilter / filtfilt: a transfer function (b, a) in double, sosfilt's scan on a dense companion matrix
     ("kernels_lombscargle.hip", []),  # Spectral.lombscargle: periodograms of unevenly sampled rows, one double sincos per (t, w) shared by a block of rows
     ("kernels_czt.hip", []),  # Transforms.czt / zoom_fft: Bluestein's three table products around the forward and inverse cores of one wave
+    ("kernels_cwt.hip", []),  # Transforms.cwt / Filters.fir_bank: one forward transform of a block shared by every filter of a bank, sinks fused
 ]
 
 

@@ -2794,3 +2794,96 @@ int nxsig_czt(nxsig_ctx* ctx, const void* x, int32_t is_complex, int64_t length,
 }
 
 }  // extern "C"
+
+/* ---------------------------------------------------------------- Filters.fir_bank / Transforms.cwt */
+extern "C" {
+
+int64_t nxsig_cwt_support(double width, int64_t length) {
+  if (!std::isfinite(width) || !(width > 0.0)) return set_error(NXSIG_ERR_INVALID_ARG, "cwt_support: width must be positive and finite");
+  if (length < 1) return set_error(NXSIG_ERR_INVALID_ARG, "cwt_support: length must be >= 1");
+  return cwt_support(width, length);
+}
+
+int nxsig_cwt_wavelet(int32_t wavelet, double width, double w, int64_t N, double* out_f64) {
+  NXSIG_API_BEGIN
+  if (!out_f64) return set_error(NXSIG_ERR_INVALID_ARG, "cwt_wavelet: null pointer argument");
+  if (const char* what = cwt_widths_check(wavelet, &width, 1, w)) return set_error(NXSIG_ERR_INVALID_ARG, std::string("cwt_wavelet: ") + what);
+  if (N < 1) return set_error(NXSIG_ERR_INVALID_ARG, "cwt_wavelet: N must be >= 1");
+  if (N > kCwtMaxExtent) return set_error(NXSIG_ERR_UNSUPPORTED, "cwt_wavelet: N must be at most 2^24");
+  cwt_wavelet(wavelet, width, w, N, out_f64);
+  return NXSIG_OK;
+  NXSIG_API_END
+}
+
+}  // extern "C"
+
+// the part the two entry points share, once the bank is a list of interleaved complex doubles and every argument but the context is checked
+static int cwt_run(const char* name, nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int64_t batch_stride,
+                   const std::vector<double>& taps, const int64_t* tap_counts, int64_t num_filters, int32_t kind, void* out, int32_t mem) {
+  const size_t x_bytes = ((size_t)(batch - 1) * batch_stride + length) * sizeof(float);
+  const size_t out_bytes = (size_t)batch * num_filters * length * (kind == kCwComplex ? sizeof(float2) : sizeof(float));
+  if (czt_overlap(x, x_bytes, out, out_bytes)) return set_error(NXSIG_ERR_INVALID_ARG, std::string(name) + ": x and out must not overlap");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  HostIo io(c, mem);
+  int rc;
+  if ((rc = io.open({{x, x_bytes, kScratchNdStageA}}, {{out, out_bytes, kScratchNdStageOut}}))) return rc;
+  CwtLaunch a;
+  a.x = static_cast<const float*>(io.in[0]); a.length = length; a.x_stride = batch_stride; a.batch = batch;
+  a.taps_host = taps.data(); a.tap_counts = tap_counts; a.num_filters = num_filters; a.kind = kind; a.out = io.out[0];
+  if ((rc = launch_cwt(c, a))) return rc;
+  return io.close();
+}
+
+extern "C" {
+
+int nxsig_fir_bank(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int64_t batch_stride, const void* taps, int32_t taps_complex,
+                   const int64_t* tap_counts, int64_t num_filters, int32_t kind, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !taps || !tap_counts || !out) return set_error(NXSIG_ERR_INVALID_ARG, "fir_bank: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = cwt_rows_check(length, batch, batch_stride, kind, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("fir_bank: ") + what);
+  int64_t total = 0, longest = 0;
+  if (const char* what = cwt_bank_check(length, taps_complex, tap_counts, num_filters, &total, &longest, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("fir_bank: ") + what);
+  std::vector<double> h((size_t)2 * total, 0.0);
+  const float* tf = static_cast<const float*>(taps);
+  for (int64_t i = 0; i < total; ++i) {
+    h[2 * i] = taps_complex ? tf[2 * i] : tf[i];
+    if (taps_complex) h[2 * i + 1] = tf[2 * i + 1];
+  }
+  if (!cwt_all_finite(h.data(), 2 * total)) return set_error(NXSIG_ERR_INVALID_ARG, "fir_bank: the taps must be finite");
+  return cwt_run("fir_bank", ctx, x, length, batch, batch_stride, h, tap_counts, num_filters, kind, out, mem);
+  NXSIG_API_END
+}
+
+int nxsig_cwt(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int64_t batch_stride, int32_t wavelet, const double* widths,
+              int64_t num_widths, double w, int32_t kind, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  if (!x || !widths || !out) return set_error(NXSIG_ERR_INVALID_ARG, "cwt: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = cwt_rows_check(length, batch, batch_stride, kind, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("cwt: ") + what);
+  if (const char* what = cwt_widths_check(wavelet, widths, num_widths, w)) return set_error(NXSIG_ERR_INVALID_ARG, std::string("cwt: ") + what);
+  std::vector<int64_t> counts((size_t)num_widths);
+  for (int64_t s = 0; s < num_widths; ++s) counts[s] = cwt_support(widths[s], length);
+  int64_t total = 0, longest = 0;
+  if (const char* what = cwt_bank_check(length, 1, counts.data(), num_widths, &total, &longest, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("cwt: ") + what);
+  // the wavelets in double, rounded to f32 once: the bank nxsig_fir_bank would be handed
+  std::vector<double> h((size_t)2 * total);
+  int64_t at = 0;
+  for (int64_t s = 0; s < num_widths; ++s) { cwt_wavelet(wavelet, widths[s], w, counts[s], h.data() + 2 * at); at += counts[s]; }
+  for (double& v : h) v = (double)(float)v;
+  if (!cwt_all_finite(h.data(), 2 * total)) return set_error(NXSIG_ERR_INVALID_ARG, "cwt: the taps must be finite");
+  return cwt_run("cwt", ctx, x, length, batch, batch_stride, h, counts.data(), num_widths, kind, out, mem);
+  NXSIG_API_END
+}
+
+}  // extern "C"

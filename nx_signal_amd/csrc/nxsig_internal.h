@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(LOMBSCARGLE_TILE)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(LOMBSCARGLE_TILE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -208,7 +208,7 @@ struct Ctx {
   size_t pin_bytes = 0; hipStream_t xfer_stream = nullptr;
   hipEvent_t xfer_ev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t xfer_ready = nullptr;
   // czt.generic's two temporaries (kernels_czt.hip), its own: grown on demand like a scratch slot, kept from call to call, freed with the context
-  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra;
+  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra; OwnedBuffer cwt_flags, cwt_rows, cwt_spectra, cwt_conv;   // ... and cwt's own (kernels_cwt.hip), kept the same way: the per-row non-finite flags (zero between calls), cwt.generic's three temporaries
   std::string last_dispatch;                // kernel families of the last compute call on this context (nxsig_ctx_last_dispatch)
   Tuning tuning;                            // dispatch / geometry switches (environment at creation, nxsig_ctx_set_tuning later)
 };
@@ -672,4 +672,24 @@ struct CztLaunch {
   void* out;               // device, dense c64 [batch][m]
 };
 int launch_czt(Ctx* c, const CztLaunch& a);
+}  // namespace nxsig
+
+#include "cwt_plan.hpp"
+
+namespace nxsig {
+// kernels_cwt.hip: Filters.fir_bank / Transforms.cwt over device rows (include/nxsig.h states the definition, DESIGN.md section 3.21
+// the design; the argument checks are the caller's).  The bank is split by support and one launch group runs per non-empty class.  The
+// filters' spectra go through ctx_table once per context, class and bank (a memo keeps the pointers: a repeated call makes no table
+// request).  Temporaries are the family's own (Ctx::cwt_flags and, for cwt.generic, cwt_rows / cwt_spectra / cwt_conv).  Everything is
+// enqueued on c->stream and nothing waits once the tables are cached
+struct CwtLaunch {
+  const float* x;             // device f32 [batch][length], rows x_stride elements apart
+  int64_t length, x_stride, batch;
+  const double* taps_host;    // the filters concatenated, interleaved complex doubles
+  const int64_t* tap_counts;  // host [num_filters]
+  int64_t num_filters;
+  int32_t kind;               // CwtKind
+  void* out;                  // device, dense [batch][num_filters][length]: c64 (kCwComplex) or f32
+};
+int launch_cwt(Ctx* c, const CwtLaunch& a);
 }  // namespace nxsig

@@ -319,3 +319,5 @@ from ._savgol import savgol_coeffs, savgol_filter  # noqa: E402,F401
 from ._hilbert import hilbert  # noqa: E402,F401
 # ... and the transfer-function filters lfilter / lfilter_zi / filtfilt / lfiltic (_lfilter.py)
 from ._lfilter import filtfilt, lfilter, lfilter_zi, lfiltic  # noqa: E402,F401
+# ... and the filter bank fir_bank (_cwt.py)
+from ._cwt import fir_bank  # noqa: E402,F401

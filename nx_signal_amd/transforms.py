@@ -84,3 +84,5 @@ def ifft_nd(tensor, ctx=None, **opts):
 from ._dct import dct, idct  # noqa: E402,F401
 # ... and so do czt / zoom_fft / czt_points (_czt.py)
 from ._czt import czt, czt_points, zoom_fft  # noqa: E402,F401
+# ... and so do cwt / morlet2 / ricker (_cwt.py)
+from ._cwt import cwt, morlet2, ricker  # noqa: E402,F401

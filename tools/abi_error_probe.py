@@ -12,6 +12,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --lfilter [--real] [--write tests/golden/abi_error_table_lfilter.json]
     python tools/abi_error_probe.py --lombscargle [--real] [--write tests/golden/abi_error_table_lombscargle.json]
     python tools/abi_error_probe.py --czt [--real] [--write tests/golden/abi_error_table_czt.json]
+    python tools/abi_error_probe.py --cwt [--real] [--write tests/golden/abi_error_table_cwt.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -29,7 +30,8 @@ nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TAB
 (tests/test_hilbert_host.py, tests/test_gpu_hilbert.py), DCT_TABLE_ENTRIES (--dct) for nxsig_dct_f32 (tests/test_dct_host.py,
 tests/test_gpu_dct.py), LFILTER_TABLE_ENTRIES (--lfilter) for nxsig_lfilter_f32 and nxsig_filtfilt_f32 (tests/test_lfilter_host.py,
 tests/test_gpu_lfilter.py), LOMBSCARGLE_TABLE_ENTRIES (--lombscargle) for nxsig_lombscargle (tests/test_lombscargle_host.py,
-tests/test_gpu_lombscargle.py), CZT_TABLE_ENTRIES (--czt) for nxsig_czt (tests/test_czt_host.py, tests/test_gpu_czt.py)."""
+tests/test_gpu_lombscargle.py), CZT_TABLE_ENTRIES (--czt) for nxsig_czt (tests/test_czt_host.py, tests/test_gpu_czt.py), CWT_TABLE_ENTRIES (--cwt) for nxsig_fir_bank
+and nxsig_cwt (tests/test_cwt_host.py, tests/test_gpu_cwt.py)."""
 import argparse
 import ctypes as C
 import json
@@ -54,6 +56,7 @@ GOLDEN_DCT = os.path.join(ROOT, "tests", "golden", "abi_error_table_dct.json")
 GOLDEN_LFILTER = os.path.join(ROOT, "tests", "golden", "abi_error_table_lfilter.json")
 GOLDEN_LOMBSCARGLE = os.path.join(ROOT, "tests", "golden", "abi_error_table_lombscargle.json")
 GOLDEN_CZT = os.path.join(ROOT, "tests", "golden", "abi_error_table_czt.json")
+GOLDEN_CWT = os.path.join(ROOT, "tests", "golden", "abi_error_table_cwt.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -454,6 +457,41 @@ CZT_TABLE_ENTRIES = [
       ("rows too large", {"length": 1 << 29, "batch_stride": 1 << 59, "batch": 16}), ("result too large", {"batch": 1 << 40})]),
 ]
 
+# Filters.fir_bank / Transforms.cwt: 2 rows of 24 real samples; a bank of three real filters of 3, 4 and 1 taps, and three morlet2 widths
+# (N = 5, 12 and 24, the last capped by the row).  Both refuse batch = 0
+_CW_TAPS = np.array([0.25, 0.5, 0.25, 1.0, -1.0, 0.5, -0.5, 2.0], np.float32)
+_CW_COUNTS = np.array([3, 4, 1], np.int64)
+_CW_WIDTHS = np.array([0.5, 1.2, 4.0], np.float64)
+
+
+def _cw_broken(arr, at, value):
+    out = arr.copy()
+    out[at] = value
+    return out
+
+
+CWT_TABLE_ENTRIES = [
+    ("nxsig_fir_bank",
+     [("x", "in", _f32(B, HL)), ("length", "v", HL), ("batch", "v", B), ("batch_stride", "v", HL), ("taps", "host", _CW_TAPS),
+      ("taps_complex", "v", 0), ("tap_counts", "host", _CW_COUNTS), ("num_filters", "v", 3), ("kind", "v", 0),
+      ("out", "out", np.zeros((B, 3, HL), np.complex64)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}), ("batch=-1", {"batch": -1}), ("batch=65536", {"batch": 65536}), ("length=0", {"length": 0}),
+      ("batch_stride=length-1", {"batch_stride": HL - 1}), ("kind=4", {"kind": 4}), ("kind=-1", {"kind": -1}), ("taps_complex=2", {"taps_complex": 2}),
+      ("num_filters=0", {"num_filters": 0}), ("num_filters=4097", {"num_filters": 4097}), ("tap count 0", {"tap_counts": _cw_broken(_CW_COUNTS, 1, 0)}),
+      ("tap count -1", {"tap_counts": _cw_broken(_CW_COUNTS, 2, -1)}), ("length+taps-1=2^24+1", {"tap_counts": _cw_broken(_CW_COUNTS, 0, (1 << 24) - HL + 2)}),
+      ("tap count 2^40", {"tap_counts": _cw_broken(_CW_COUNTS, 0, 1 << 40)}), ("length=2^24+1", {"length": (1 << 24) + 1, "batch_stride": (1 << 24) + 1}),
+      ("taps nan", {"taps": _cw_broken(_CW_TAPS, 4, np.nan)}), ("taps inf", {"taps": _cw_broken(_CW_TAPS, 7, np.inf)})]),
+    ("nxsig_cwt",
+     [("x", "in", _f32(B, HL)), ("length", "v", HL), ("batch", "v", B), ("batch_stride", "v", HL), ("wavelet", "v", 0),
+      ("widths", "host", _CW_WIDTHS), ("num_widths", "v", 3), ("w", "v", 5.0), ("kind", "v", 0),
+      ("out", "out", np.zeros((B, 3, HL), np.complex64)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}), ("batch=65536", {"batch": 65536}), ("length=0", {"length": 0}), ("batch_stride=length-1", {"batch_stride": HL - 1}),
+      ("kind=4", {"kind": 4}), ("wavelet=2", {"wavelet": 2}), ("wavelet=-1", {"wavelet": -1}), ("num_widths=0", {"num_widths": 0}),
+      ("num_widths=4097", {"num_widths": 4097}), ("width 0", {"widths": _cw_broken(_CW_WIDTHS, 0, 0.0)}), ("width -1", {"widths": _cw_broken(_CW_WIDTHS, 1, -1.0)}),
+      ("width nan", {"widths": _cw_broken(_CW_WIDTHS, 2, np.nan)}), ("width inf", {"widths": _cw_broken(_CW_WIDTHS, 2, np.inf)}), ("w=nan", {"w": float("nan")}),
+      ("length=2^24", {"length": 1 << 24, "batch_stride": 1 << 24})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -574,9 +612,10 @@ def main():
     ap.add_argument("--lfilter", action="store_true", help="the entry points of LFILTER_TABLE_ENTRIES (Filters.lfilter / filtfilt)")
     ap.add_argument("--lombscargle", action="store_true", help="the entry point of LOMBSCARGLE_TABLE_ENTRIES (Spectral.lombscargle)")
     ap.add_argument("--czt", action="store_true", help="the entry point of CZT_TABLE_ENTRIES (Transforms.czt / zoom_fft)")
+    ap.add_argument("--cwt", action="store_true", help="the entry points of CWT_TABLE_ENTRIES (Filters.fir_bank / Transforms.cwt)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, CZT_TABLE_ENTRIES if a.czt else LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, CWT_TABLE_ENTRIES if a.cwt else CZT_TABLE_ENTRIES if a.czt else LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
