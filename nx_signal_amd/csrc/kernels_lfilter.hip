@@ -1,430 +1,118 @@
 // Filters.lfilter / filtfilt: a transfer function (b, a) of order n <= 16 in transposed direct form II over real f32 rows, scipy.signal's
-// definition; include/nxsig.h states it, DESIGN.md section 3.18 the design.  Coefficients, states and the recurrence are double; a sample
-// is widened on load and an output rounded to f32 once.
+// definition; include/nxsig.h states it, DESIGN.md section 3.18 the design.  Coefficients, states and the recurrence are double.
 //
-//   lfilter.scan     the scheme of sosfilt.scan (kernels_iir.hip) on the n states of the direct form, z[m + 1] = A z[m] + B x[m] with A a
-//                    dense companion matrix.  A row is cut into chunks of C samples, one per lane, and tiles of 64 chunks, one per
-//                    single-wave workgroup.
-//                      pass 1   every chunk runs the filter from a zero state; a scan over the 64 lanes with A^C, A^2C, ... A^32C turns
-//                               the end states into P_i = the state at the end of chunk i of a tile that started at zero; P goes to memory
-//                      carry    one wave per row: lane j walks R consecutive tiles with A^T from zero, a scan over the lanes with
-//                               A^(T R 2^k) joins the runs (the row's start state, zi or zero, enters at lane 0), a second walk writes
-//                               every tile's true start state
-//                      pass 2   a scan of the tile's start state gives lane i its A^(i C) s_tile; with P_(i-1) that is the chunk's true
-//                               start state; the chunk runs again and writes y
-//                    Every product with a power of A is a dense NP x NP one.  The tables are built on the host (lfilter_plan.hpp), which
-//                    also decides whether a filter may use them: a direct form with clustered poles has powers too badly conditioned
-//                    for this algebra although the plain recurrence is fine (the conditioning guard).  Every sum has one fixed order and
-//                    one writer; chunk and tile depend on the order only.  Samples travel through LDS in pieces of 32 per chunk so that
-//                    global loads and stores are 16 bytes per lane.
+//   lfilter.scan     the n states of the direct form are the linear system z[m + 1] = A z[m] + B x[m] with A a dense companion matrix:
+//                    the recurrence scan of recurrence_scan.hpp, whose kernels and driver this file instantiates with the direct form's
+//                    step and with dense NP x NP products.  The tables are built on the host (lfilter_plan.hpp), which also decides
+//                    whether a filter may use them: a direct form with clustered poles has powers too badly conditioned for this
+//                    algebra although the plain recurrence is fine (the conditioning guard).  Chunk and tile depend on the order only.
 //   lfilter.generic  one lane per row, the plain recurrence: rows of at most one chunk, every filter the guard keeps off the scan, and
 //                    NXSIG_DISABLE_LFILTER_SCAN
-// direction 1 runs the same kernels over the row read backwards.  b and a are filled up with zeros to the order 1 / 2 / 4 / 8 / 16 a
-// kernel is instantiated for; a padded state stays an exact zero.
-#include <algorithm>
-#include <cstring>
-
+// b and a are filled up with zeros to the order 1 / 2 / 4 / 8 / 16 a kernel is instantiated for; a padded state stays an exact zero.
 #include "nxsig_internal.h"
+#include "recurrence_scan.hpp"
 
 namespace nxsig {
 namespace {
 
-constexpr int kLanes = kIirLanes;
-constexpr int kSub = kIirSub;
-constexpr int kWords = kSub / 4 + 1;   // 16-byte words that cover a piece wherever it starts
-constexpr int kPitch = 4 * kWords + 1; // LDS floats per chunk: odd, so the lanes' reads fall on different banks
-
-typedef float gf4 __attribute__((ext_vector_type(4)));
-
-template <int NP> struct Coefs { double b[NP + 1], a[NP + 1]; };   // divided by a[0]; a[0] == 1 is not read
-
-struct Geom {
-  int64_t n, x_stride, y_stride, out_off, out_len, tiles, R;
-  int32_t C, dir, batch, zi_rows, zi_times_first;
+// what the family tells the driver of recurrence_scan.hpp
+struct LfFamily {
+  using Launch = LfLaunch;
+  static constexpr const char* kTooManyTiles = "lfilter: 2^31 or more tiles in one call";
+  static constexpr const char* kTooManyBlocks = "filtfilt: 2^31 or more tiles in one call";
+  static int states(const Launch& a) { return a.cf.n; }   // a gain has no state
+  static int32_t chunk(const Launch& a) { return lf_chunk(a.cf.n); }
+  static int64_t tiles(const Launch& a) { return lf_tiles(a.n, a.cf.n); }
+  static void note(bool scan) {
+    if (scan) dispatch_note("lfilter.scan");
+    else dispatch_note("lfilter.generic");
+  }
+  static int launch(Ctx* c, const Launch& a) { return launch_lfilter(c, a); }
 };
 
-// one sample: y = b0 x + z0;  z[i] = z[i + 1] + b[i + 1] x - a[i + 1] y;  z[NP - 1] = b[NP] x - a[NP] y
-template <int NP> __device__ __forceinline__ double step(const Coefs<NP>& cf, double (&z)[NP], double x) {
-  const double y = __builtin_fma(cf.b[0], x, z[0]);
-#pragma unroll
-  for (int i = 0; i < NP - 1; ++i) z[i] = __builtin_fma(cf.b[i + 1], x, __builtin_fma(-cf.a[i + 1], y, z[i + 1]));
-  z[NP - 1] = __builtin_fma(cf.b[NP], x, -cf.a[NP] * y);
-  return y;
-}
+template <int N> struct Lf : LfFamily {
+  static constexpr int NP = N;
+  struct Coefs { double b[NP + 1], a[NP + 1]; };   // divided by a[0]; a[0] == 1 is not read
 
-// v += M w for a dense M, ascending columns
-template <int NP> __device__ __forceinline__ void matvec_add(double (&v)[NP], const double* __restrict__ M, const double (&w)[NP]) {
-#pragma unroll
-  for (int r = 0; r < NP; ++r) {
-    double acc = v[r];
-#pragma unroll
-    for (int c = 0; c < NP; ++c) acc = __builtin_fma(M[r * NP + c], w[c], acc);
-    v[r] = acc;
-  }
-}
-
-// inclusive scan over the lanes of the wave: v_i <- sum over j <= i of B^(i - j) v_j, with M[k] = B^(2^k)
-template <int NP> __device__ __forceinline__ void scan_wave(double (&v)[NP], const double* __restrict__ M, int lane) {
-#pragma unroll 1
-  for (int k = 0; k < kIirLevels; ++k) {
-    double w[NP];
-#pragma unroll
-    for (int r = 0; r < NP; ++r) w[r] = __shfl_up(v[r], 1u << k, kLanes);
-    if (lane >= (1 << k)) matvec_add<NP>(v, M + (size_t)k * NP * NP, w);
-  }
-}
-
-// physical start of the piece of kSub samples whose logical start is l0 (negative when a backward piece hangs over the row's start)
-__device__ __forceinline__ int64_t piece_start(const Geom& g, int64_t l0) { return g.dir ? g.n - l0 - kSub : l0; }
-
-template <int NP, bool PASS2>
-__global__ __launch_bounds__(kLanes) void k_lf_pass(const float* __restrict__ x, float* __restrict__ y, Coefs<NP> cf,
-                                                    const double* __restrict__ M, double* __restrict__ P,
-                                                    const double* __restrict__ tile_start, double* __restrict__ zf, Geom g) {
-  __shared__ float lds[kLanes * kPitch];
-  const int lane = threadIdx.x;
-  const int64_t row = blockIdx.x / g.tiles, tile = blockIdx.x - row * g.tiles;
-  const float* xrow = x + row * g.x_stride;
-  const int64_t xbase = (int64_t)(reinterpret_cast<uintptr_t>(xrow) >> 2);
-  const int64_t l_chunk = (tile * kLanes + lane) * g.C;
-  const int cnt = g.n - l_chunk >= g.C ? g.C : (g.n - l_chunk > 0 ? (int)(g.n - l_chunk) : 0);
-  double* Pt = P + ((row * g.tiles + tile) * NP) * kLanes;
-
-  double s[NP];
-  if (PASS2) {
-    const double* ts = tile_start + (row * g.tiles + tile) * NP;
-#pragma unroll
-    for (int r = 0; r < NP; ++r) s[r] = lane == 0 ? ts[r] : 0.0;
-    scan_wave<NP>(s, M, lane);
-    if (lane > 0) {
-#pragma unroll
-      for (int r = 0; r < NP; ++r) s[r] += Pt[r * kLanes + lane - 1];
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < NP; ++r) s[r] = 0.0;
+  static Coefs fill(const Launch& a) {
+    Coefs cf;
+    for (int k = 0; k <= NP; ++k) { cf.b[k] = a.cf.b[k]; cf.a[k] = a.cf.a[k]; }
+    return cf;
   }
 
-  for (int b = 0; b < g.C / kSub; ++b) {
-    __syncthreads();   // the previous piece's readers are done
-    for (int u = lane; u < kLanes * kWords; u += kLanes) {
-      const int i = u / kWords, w = u - i * kWords;
-      const int64_t p0 = piece_start(g, (tile * kLanes + i) * g.C + b * kSub);
-      const int64_t p = p0 - ((xbase + p0) & 3) + 4 * w;
-      float e[4];
-      if (p >= 0 && p + 4 <= g.n) {
-        const gf4 v = *reinterpret_cast<const gf4*>(xrow + p);
-        e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
-      } else {
+  // one sample: y = b0 x + z0;  z[i] = z[i + 1] + b[i + 1] x - a[i + 1] y;  z[NP - 1] = b[NP] x - a[NP] y
+  static __device__ __forceinline__ double step(const Coefs& cf, double (&z)[NP], double x) {
+    const double y = __builtin_fma(cf.b[0], x, z[0]);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = (p + k >= 0 && p + k < g.n) ? xrow[p + k] : 0.0f;
-      }
+    for (int i = 0; i < NP - 1; ++i) z[i] = __builtin_fma(cf.b[i + 1], x, __builtin_fma(-cf.a[i + 1], y, z[i + 1]));
+    z[NP - 1] = __builtin_fma(cf.b[NP], x, -cf.a[NP] * y);
+    return y;
+  }
+
+  // v += M w for a dense M, ascending columns
+  static __device__ __forceinline__ void matvec_add(double (&v)[NP], const double* __restrict__ M, const double (&w)[NP]) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) lds[i * kPitch + 4 * w + k] = e[k];
-    }
-    __syncthreads();
-    {
-      const int64_t p0 = piece_start(g, l_chunk + b * kSub);
-      float* mine = lds + lane * kPitch + (int)((xbase + p0) & 3);
-      const int live = cnt - b * kSub;   // samples of this piece that exist
-#pragma unroll 4
-      for (int j = 0; j < kSub; ++j) {
-        if (j < live) {
-          const int slot = g.dir ? kSub - 1 - j : j;
-          const double yv = step<NP>(cf, s, (double)mine[slot]);
-          if (PASS2) mine[slot] = (float)yv;
-        }
-      }
-    }
-    if (PASS2) {
-      __syncthreads();
-      float* yrow = y + row * g.y_stride;
-      const int64_t ybase = (int64_t)(reinterpret_cast<uintptr_t>(yrow) >> 2);
-      for (int u = lane; u < kLanes * kWords; u += kLanes) {
-        const int i = u / kWords, w = u - i * kWords;
-        const int64_t p0 = piece_start(g, (tile * kLanes + i) * g.C + b * kSub);
-        const int lead_x = (int)((xbase + p0) & 3);
-        const int64_t q0 = p0 - g.out_off;
-        const int e0 = 4 * w - (int)((ybase + q0) & 3);   // element of the piece the word starts at
-        const float* src = lds + i * kPitch + lead_x;
-        bool ok[4], all = true;
+    for (int r = 0; r < NP; ++r) {
+      double acc = v[r];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int e = e0 + k;
-          ok[k] = e >= 0 && e < kSub && p0 + e >= 0 && p0 + e < g.n && q0 + e >= 0 && q0 + e < g.out_len;
-          all = all && ok[k];
-        }
-        if (all) {
-          gf4 v;
-          v.x = src[e0]; v.y = src[e0 + 1]; v.z = src[e0 + 2]; v.w = src[e0 + 3];
-          *reinterpret_cast<gf4*>(yrow + q0 + e0) = v;
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (ok[k]) yrow[q0 + e0 + k] = src[e0 + k];
-        }
-      }
+      for (int c = 0; c < NP; ++c) acc = __builtin_fma(M[r * NP + c], w[c], acc);
+      v[r] = acc;
     }
   }
 
-  if (PASS2) {
-    if (zf && cnt > 0 && l_chunk + cnt == g.n) {
-#pragma unroll
-      for (int r = 0; r < NP; ++r) zf[row * NP + r] = s[r];
+  // The tables of a filter are built once per context and (R, b, a): the memo keeps the device pointers and the guard's verdict beside
+  // the key's content, so a later call neither forms the powers again nor asks for a table.  Dropped together with the table cache
+  // (DeviceGuard, api.cpp).  *scan_ok false: the conditioning guard keeps the filter off the scan (no table was uploaded)
+  static int tables(Ctx* c, const Launch& a, int64_t R, const void** mcd, const void** mtd, bool* scan_ok) {
+    const LfCoefs& cf = a.cf;
+    const int n = cf.n;
+    std::vector<uint64_t> want((size_t)4 + 2 * (n + 1));
+    want[2] = ((uint64_t)R << 8) | (uint64_t)n;
+    std::memcpy(want.data() + 4, cf.b, (size_t)(n + 1) * sizeof(double));
+    std::memcpy(want.data() + 4 + (n + 1), cf.a, (size_t)(n + 1) * sizeof(double));
+    const uint64_t key = fnv1a(0x11f17e00ull ^ ((uint64_t)NP << 40) ^ (uint64_t)R, want.data() + 4, (size_t)2 * (n + 1) * sizeof(double));
+    auto hit = c->memo.find(key);
+    if (hit != c->memo.end() && hit->second.size() == want.size() && hit->second[2] == want[2] && std::equal(want.begin() + 4, want.end(), hit->second.begin() + 4)) {
+      *mcd = reinterpret_cast<const void*>((uintptr_t)hit->second[0]);
+      *mtd = reinterpret_cast<const void*>((uintptr_t)hit->second[1]);
+      *scan_ok = hit->second[3] != 0;
+      return NXSIG_OK;
     }
-  } else {
-    scan_wave<NP>(s, M, lane);
-#pragma unroll
-    for (int r = 0; r < NP; ++r) Pt[r * kLanes + lane] = s[r];
-  }
-}
-
-// the start state of a row: zero, zi, or zi * (the row's first logical sample)
-template <int NP>
-__device__ __forceinline__ void row_start(double (&s0)[NP], const float* __restrict__ x, const double* __restrict__ zi, int64_t row, const Geom& g) {
-  if (zi) {
-    const double* zr = zi + (g.zi_rows == 1 ? 0 : row) * NP;
-    const double scale = g.zi_times_first ? (double)x[row * g.x_stride + (g.dir ? g.n - 1 : 0)] : 1.0;
-#pragma unroll
-    for (int r = 0; r < NP; ++r) s0[r] = zr[r] * scale;
-  } else {
-#pragma unroll
-    for (int r = 0; r < NP; ++r) s0[r] = 0.0;
-  }
-}
-
-// M: [0 .. 5] A^(T R 2^k), [6] A^T
-template <int NP>
-__global__ __launch_bounds__(kLanes) void k_lf_carry(const float* __restrict__ x, const double* __restrict__ P, const double* __restrict__ M,
-                                                     const double* __restrict__ zi, double* __restrict__ tile_start, Geom g) {
-  const int lane = threadIdx.x;
-  const int64_t row = blockIdx.x;
-  const double* MT = M + (size_t)kIirLevels * NP * NP;
-  const int64_t t0 = lane * g.R < g.tiles ? lane * g.R : g.tiles;
-  const int64_t t1 = t0 + g.R < g.tiles ? t0 + g.R : g.tiles;
-  // the end state of tile t run from zero: P of its last lane
-  auto tile_end = [&](int64_t t, double (&z)[NP]) {
-    const double* Pt = P + ((row * g.tiles + t) * NP) * kLanes;
-#pragma unroll
-    for (int r = 0; r < NP; ++r) z[r] = Pt[r * kLanes + kLanes - 1];
-  };
-  double s0[NP], acc[NP], z[NP];
-  row_start<NP>(s0, x, zi, row, g);
-#pragma unroll
-  for (int r = 0; r < NP; ++r) acc[r] = 0.0;
-  for (int64_t t = t0; t < t1; ++t) {
-    tile_end(t, z);
-    matvec_add<NP>(z, MT, acc);
-#pragma unroll
-    for (int r = 0; r < NP; ++r) acc[r] = z[r];
-  }
-  if (lane == 0) matvec_add<NP>(acc, M, s0);   // lane 0 walks R tiles (R <= tiles): the row's start state travels A^(T R)
-  scan_wave<NP>(acc, M, lane);
-  double s[NP];
-#pragma unroll
-  for (int r = 0; r < NP; ++r) {
-    const double below = __shfl_up(acc[r], 1u, kLanes);
-    s[r] = lane == 0 ? s0[r] : below;
-  }
-  for (int64_t t = t0; t < t1; ++t) {
-    double* ts = tile_start + (row * g.tiles + t) * NP;
-#pragma unroll
-    for (int r = 0; r < NP; ++r) ts[r] = s[r];
-    tile_end(t, z);
-    matvec_add<NP>(z, MT, s);
-#pragma unroll
-    for (int r = 0; r < NP; ++r) s[r] = z[r];
-  }
-}
-
-template <int NP>
-__global__ __launch_bounds__(kLanes) void k_lf_generic(const float* __restrict__ x, float* __restrict__ y, Coefs<NP> cf,
-                                                       const double* __restrict__ zi, double* __restrict__ zf, Geom g) {
-  const int64_t row = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-  if (row >= g.batch) return;
-  double s[NP];
-  row_start<NP>(s, x, zi, row, g);
-  const float* xrow = x + row * g.x_stride;
-  float* yrow = y + row * g.y_stride;
-  for (int64_t i = 0; i < g.n; ++i) {
-    const int64_t p = g.dir ? g.n - 1 - i : i;
-    const double yv = step<NP>(cf, s, (double)xrow[p]);
-    const int64_t q = p - g.out_off;
-    if (q >= 0 && q < g.out_len) yrow[q] = (float)yv;
-  }
-  if (zf) {
-#pragma unroll
-    for (int r = 0; r < NP; ++r) zf[row * NP + r] = s[r];
-  }
-}
-
-// filtfilt's extension: ext[row][j], j in [0, n + 2 e); the odd form 2 x_end - x is rounded to f32 once, as scipy forms it on f32 rows
-__global__ __launch_bounds__(256) void k_lf_extend(const float* __restrict__ x, float* __restrict__ ext, int64_t n, int64_t x_stride, int64_t e,
-                                                   int32_t padtype, int64_t blocks_per_row) {
-  const int64_t row = blockIdx.x / blocks_per_row;
-  const int64_t j = (blockIdx.x - row * blocks_per_row) * 256 + threadIdx.x;
-  const int64_t m = n + 2 * e;
-  if (j >= m) return;
-  const float* xr = x + row * x_stride;
-  float v;
-  if (j >= e && j < e + n) v = xr[j - e];
-  else {
-    const bool left = j < e;
-    const float end = left ? xr[0] : xr[n - 1];
-    const float in = left ? xr[e - j] : xr[n - 2 - (j - (e + n))];
-    v = padtype == 1 ? (float)(2.0 * (double)end - (double)in) : (padtype == 2 ? in : end);
-  }
-  ext[row * m + j] = v;
-}
-
-// The tables of a filter are built once per context and (R, b, a): the memo keeps the device pointers and the guard's verdict beside
-// the key's content, so a later call neither forms the powers again nor asks for a table.  Dropped together with the table cache
-// (DeviceGuard, api.cpp).  *scan_ok false: the filter stays off the scan (no table was uploaded)
-template <int NP> int tables(Ctx* c, const LfCoefs& cf, int64_t R, const void** mcd, const void** mtd, bool* scan_ok) {
-  const int n = cf.n;
-  std::vector<uint64_t> want((size_t)4 + 2 * (n + 1));
-  want[2] = ((uint64_t)R << 8) | (uint64_t)n;
-  std::memcpy(want.data() + 4, cf.b, (size_t)(n + 1) * sizeof(double));
-  std::memcpy(want.data() + 4 + (n + 1), cf.a, (size_t)(n + 1) * sizeof(double));
-  const uint64_t key = fnv1a(0x11f17e00ull ^ ((uint64_t)NP << 40) ^ (uint64_t)R, want.data() + 4, (size_t)2 * (n + 1) * sizeof(double));
-  auto hit = c->memo.find(key);
-  if (hit != c->memo.end() && hit->second.size() == want.size() && hit->second[2] == want[2] && std::equal(want.begin() + 4, want.end(), hit->second.begin() + 4)) {
-    *mcd = reinterpret_cast<const void*>((uintptr_t)hit->second[0]);
-    *mtd = reinterpret_cast<const void*>((uintptr_t)hit->second[1]);
-    *scan_ok = hit->second[3] != 0;
+    const LfTables t = lf_tables(cf, R);
+    *mcd = *mtd = nullptr;
+    *scan_ok = t.scan_ok;
+    if (t.scan_ok) {
+      int rc;
+      if ((rc = ctx_table(c, 0x11f17e43ull ^ ((uint64_t)NP << 32), t.mc.data(), t.mc.size() * sizeof(double), mcd))) return rc;
+      if ((rc = ctx_table(c, 0x11f17f43ull ^ ((uint64_t)NP << 32), t.mt.data(), t.mt.size() * sizeof(double), mtd))) return rc;
+    }
+    want[0] = (uint64_t)(uintptr_t)*mcd;
+    want[1] = (uint64_t)(uintptr_t)*mtd;
+    want[3] = t.scan_ok ? 1 : 0;
+    c->memo[key] = want;
     return NXSIG_OK;
   }
-  const LfTables t = lf_tables(cf, R);
-  *mcd = *mtd = nullptr;
-  *scan_ok = t.scan_ok;
-  if (t.scan_ok) {
-    int rc;
-    if ((rc = ctx_table(c, 0x11f17e43ull ^ ((uint64_t)NP << 32), t.mc.data(), t.mc.size() * sizeof(double), mcd))) return rc;
-    if ((rc = ctx_table(c, 0x11f17f43ull ^ ((uint64_t)NP << 32), t.mt.data(), t.mt.size() * sizeof(double), mtd))) return rc;
-  }
-  want[0] = (uint64_t)(uintptr_t)*mcd;
-  want[1] = (uint64_t)(uintptr_t)*mtd;
-  want[3] = t.scan_ok ? 1 : 0;
-  c->memo[key] = want;
-  return NXSIG_OK;
-}
 
-template <int NP> int run(Ctx* c, const LfLaunch& a, bool scan) {
-  const int n = a.cf.n;
-  Coefs<NP> cf;
-  for (int k = 0; k <= NP; ++k) { cf.b[k] = a.cf.b[k]; cf.a[k] = a.cf.a[k]; }
-  Geom g;
-  g.n = a.n; g.x_stride = a.x_stride; g.y_stride = a.y_stride; g.out_off = a.out_off; g.out_len = a.out_len;
-  g.C = lf_chunk(n); g.dir = a.direction; g.batch = a.batch; g.zi_rows = a.zi_rows; g.zi_times_first = a.zi_times_first ? 1 : 0;
-  g.tiles = lf_tiles(a.n, n);
-  g.R = iir_tiles_per_lane(g.tiles);
-  int rc;
-  const void *mcd = nullptr, *mtd = nullptr;
-  if (scan) {
-    if (g.tiles >= ((int64_t)1 << 31) / a.batch) return set_error(NXSIG_ERR_UNSUPPORTED, "lfilter: 2^31 or more tiles in one call");
-    if ((rc = tables<NP>(c, a.cf, g.R, &mcd, &mtd, &scan))) return rc;   // the conditioning guard may take the filter off the scan
+  // filtfilt's zi is a function of (b, a): one cached table per filter
+  static int zi_table(Ctx* c, const std::vector<double>& padded, const void** d) {
+    return ctx_table(c, 0x11f17a49ull ^ ((uint64_t)NP << 32), padded.data(), padded.size() * sizeof(double), d);
   }
-
-  // one allocation: chunk states P, tile start states, zi rows, zf rows
-  const size_t p_elems = scan ? (size_t)a.batch * g.tiles * NP * kLanes : 0;
-  const size_t ts_elems = scan ? (size_t)a.batch * g.tiles * NP : 0;
-  const bool has_zi = a.zi_host && n > 0;
-  const bool zi_table = has_zi && a.zi_times_first;   // filtfilt's zi is a function of (b, a): one cached table per filter
-  const size_t zi_elems = has_zi && !zi_table ? (size_t)a.zi_rows * NP : 0;
-  const size_t zf_elems = a.zf_host ? (size_t)a.batch * NP : 0;
-  void* base = nullptr;
-  if ((rc = ctx_scratch(c, kScratchLongStftFrames, (p_elems + ts_elems + zi_elems + zf_elems + 1) * sizeof(double), &base))) return rc;
-  double* P = static_cast<double*>(base);
-  double* ts = P + p_elems;
-  double* zi_scratch = ts + ts_elems;
-  double* zf = a.zf_host ? zi_scratch + zi_elems : nullptr;
-
-  // zi padded to NP states per row; a row with a non-finite entry is NaN throughout, so that output 0 is non-finite already
-  const double* zi = nullptr;
-  if (has_zi) {
-    std::vector<double> padded((size_t)a.zi_rows * NP, 0.0);
-    for (int32_t r = 0; r < a.zi_rows; ++r) {
-      bool finite = true;
-      for (int k = 0; k < n; ++k) finite = finite && std::isfinite(a.zi_host[(size_t)r * n + k]);
-      for (int k = 0; k < NP; ++k) padded[(size_t)r * NP + k] = finite ? (k < n ? a.zi_host[(size_t)r * n + k] : 0.0) : NAN;
-    }
-    if (zi_table) {
-      const void* d = nullptr;
-      if ((rc = ctx_table(c, 0x11f17a49ull ^ ((uint64_t)NP << 32), padded.data(), padded.size() * sizeof(double), &d))) return rc;
-      zi = static_cast<const double*>(d);
-    } else {   // a caller's zi changes from call to call (zf fed back as zi): through the scratch slot, never a cached table
-      NXSIG_HIP_TRY(hipMemcpyAsync(zi_scratch, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-      NXSIG_HIP_TRY(hipStreamSynchronize(c->stream));   // `padded` goes away
-      zi = zi_scratch;
-    }
-  }
-
-  if (!scan) {
-    dispatch_note("lfilter.generic");
-    hipLaunchKernelGGL(k_lf_generic<NP>, dim3((unsigned)(((int64_t)a.batch + kLanes - 1) / kLanes)), dim3(kLanes), 0, c->stream, a.x, a.y, cf, zi, zf, g);
-    NXSIG_HIP_TRY(hipGetLastError());
-  } else {
-    const unsigned blocks = (unsigned)(g.tiles * a.batch);
-    dispatch_note("lfilter.scan");
-    hipLaunchKernelGGL((k_lf_pass<NP, false>), dim3(blocks), dim3(kLanes), 0, c->stream, a.x, static_cast<float*>(nullptr), cf,
-                       static_cast<const double*>(mcd), P, static_cast<const double*>(nullptr), static_cast<double*>(nullptr), g);
-    NXSIG_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_lf_carry<NP>, dim3((unsigned)a.batch), dim3(kLanes), 0, c->stream, a.x, P, static_cast<const double*>(mtd), zi, ts, g);
-    NXSIG_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((k_lf_pass<NP, true>), dim3(blocks), dim3(kLanes), 0, c->stream, a.x, a.y, cf, static_cast<const double*>(mcd), P,
-                       static_cast<const double*>(ts), zf, g);
-    NXSIG_HIP_TRY(hipGetLastError());
-  }
-  if (a.zf_host) {
-    std::vector<double> back((size_t)a.batch * NP);
-    NXSIG_HIP_TRY(hipMemcpyAsync(back.data(), zf, back.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    NXSIG_HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int32_t r = 0; r < a.batch; ++r)
-      for (int k = 0; k < n; ++k) a.zf_host[(size_t)r * n + k] = back[(size_t)r * NP + k];
-  }
-  return NXSIG_OK;
-}
+};
 
 }  // namespace
 
 int launch_lfilter(Ctx* c, const LfLaunch& a) {
   // a row of one chunk has nothing to run side by side: the plain recurrence (a rule of the row length and the order only)
   const bool scan = !tune(c, kT_DISABLE_LFILTER_SCAN, 0) && a.n > lf_chunk(a.cf.n);
-  switch (lf_padded_order(a.cf.n)) {
-    case 1: return run<1>(c, a, scan);
-    case 2: return run<2>(c, a, scan);
-    case 4: return run<4>(c, a, scan);
-    case 8: return run<8>(c, a, scan);
-    default: return run<16>(c, a, scan);
-  }
+  return rscan::run_padded<Lf>(c, a, lf_padded_order(a.cf.n), scan);
 }
 
 int launch_filtfilt(Ctx* c, const float* x, int64_t n, int64_t x_stride, int32_t batch, const LfCoefs& cf, int32_t padtype, int64_t edge, float* y) {
-  const int64_t m = n + 2 * edge;
-  void* base = nullptr;
-  // the extended rows (when there is an edge) and the forward result, both f32 [batch][m]
-  int rc = ctx_scratch(c, kScratchFirLong, (size_t)batch * m * sizeof(float) * (edge > 0 ? 2 : 1), &base);
-  if (rc) return rc;
-  float* fwd = static_cast<float*>(base);
-  const float* in = x;
-  int64_t in_stride = x_stride;
-  if (edge > 0) {
-    float* ext = fwd + (size_t)batch * m;
-    const int64_t bpr = (m + 255) / 256;
-    if (bpr >= ((int64_t)1 << 31) / batch) return set_error(NXSIG_ERR_UNSUPPORTED, "filtfilt: 2^31 or more tiles in one call");
-    hipLaunchKernelGGL(k_lf_extend, dim3((unsigned)(bpr * batch)), dim3(256), 0, c->stream, x, ext, n, x_stride, edge, padtype, bpr);
-    NXSIG_HIP_TRY(hipGetLastError());
-    in = ext; in_stride = m;
-  }
   double zi[kLfMaxOrder];
   if (!lf_zi(cf, zi)) return set_error(NXSIG_ERR_INVALID_ARG, "filtfilt: singular matrix");
-  LfLaunch a;
-  a.x = in; a.n = m; a.x_stride = in_stride; a.batch = batch; a.cf = cf;
-  a.zi_host = zi; a.zi_rows = 1; a.zi_times_first = true; a.zf_host = nullptr;
-  a.direction = 0; a.y = fwd; a.y_stride = m; a.out_off = 0; a.out_len = m;
-  if ((rc = launch_lfilter(c, a))) return rc;
-  a.x = fwd; a.x_stride = m; a.direction = 1; a.y = y; a.y_stride = n; a.out_off = edge; a.out_len = n;
-  return launch_lfilter(c, a);
+  LfLaunch a{};
+  a.cf = cf; a.zi_host = zi;
+  return rscan::forward_backward<LfFamily>(c, x, n, x_stride, batch, padtype, edge, y, a);
 }
 
 }  // namespace nxsig

@@ -131,12 +131,12 @@ enum ScratchSlot : int {
   kScratchConvNdA = 13,          // n-D fftconvolve: padded A, later the inverse transform's result (kernels_nd.hip)
   kScratchConvNdB = 14,          // n-D fftconvolve: padded B (kernels_nd.hip)
   kScratchConvNdC = 15,          // n-D fftconvolve: the product (kernels_nd.hip)
-  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip); welch / csd: row flags, partial sums, the generic tier's frames (kernels_welch.hip); sosfilt: chunk and tile states, zi, zf (kernels_iir.hip); lfilter: the same (kernels_lfilter.hip)
+  kScratchLongStftFrames = 16,   // frames of the long-transform stft (launch_stft_big, kernels_nd.hip); welch / csd: row flags, partial sums, the generic tier's frames (kernels_welch.hip); sosfilt and lfilter: chunk and tile states, zi, zf (recurrence_scan.hpp)
   kScratchNdStageA = 17,         // host staging of the n-D / filter / peak / waveform calls: first input; the mask of the masked istft (api.cpp)
   kScratchNdStageB = 18,         // the same: second input; peak finding's `valid` cell (api.cpp)
   kScratchNdStageOut = 19,       // the same: results, several packed at a 256-byte stride (api.cpp)
   kScratchIstftProduct = 20,     // z * H / z * mask of the filtered and masked istft's two-step fall-back (launch_istft, api.cpp); hilbert.generic: the means of the rows that fill the transform, the dense (centred or gathered) rows, later the complex signal ahead of the sink — every output of a centred row, the f32 outputs of the others (kernels_hilbert.hip); dct.fft: the input of its one row transform — the row means and the permuted, centred rows (type 2) or the Hermitian spectra (type 3) (kernels_dct.hip)
-  kScratchFirLong = 21,          // long FIR: full convolution row, partition outputs, delay-line spectra (api.cpp, kernels_wave_firlong.hip); sosfiltfilt: the extended rows and the forward result (kernels_iir.hip); filtfilt: the same (kernels_lfilter.hip)
+  kScratchFirLong = 21,          // long FIR: full convolution row, partition outputs, delay-line spectra (api.cpp, kernels_wave_firlong.hip); sosfiltfilt and filtfilt: the extended rows and the forward result (recurrence_scan.hpp)
   kScratchFirRowFlags = 22,      // per-row non-finite flags of the FIR kernels (fir_row_flags, kernels_generic.hip)
   kScratchIstftNfList = 23,      // units with a non-finite bin reported by the multi-frame inverse kernels (istft_nf_list, kernels_generic.hip)
   kScratchPackedSpectrum = 24,   // packed istft fall-back: the Hermitian rows written out (launch_istft, api.cpp)
@@ -490,23 +490,27 @@ int launch_welch(Ctx* c, const WelchLaunch& a);
 #include "welch_plan.hpp"
 
 namespace nxsig {
-// kernels_iir.hip: Filters.sosfilt / sosfiltfilt (include/nxsig.h states the definition, DESIGN.md section 3.13 the design).  One
-// run of the cascade over `batch` rows.  Logical sample i of a row is physical sample i (direction 0) or n - 1 - i (direction 1);
-// output sample p (physical) goes to y[row * y_stride + p - out_off] when 0 <= p - out_off < out_len.  Temporaries (chunk and tile
-// states, zi, zf) live in kScratchLongStftFrames.  Enqueued on c->stream; only a call that returns zf or brings a zi of the caller's waits
-struct IirLaunch {
+// recurrence_scan.hpp: what one run of a recursive filter over `batch` rows is told, whichever family it belongs to.  Logical sample i of
+// a row is physical sample i (direction 0) or n - 1 - i (direction 1); output sample p (physical) goes to y[row * y_stride + p - out_off]
+// when 0 <= p - out_off < out_len.  Temporaries (chunk and tile states, zi, zf) live in kScratchLongStftFrames.  Enqueued on c->stream;
+// only a call that returns zf or brings a zi of the caller's waits
+struct ScanLaunch {
   const float* x;          // device f32[batch][n], rows x_stride elements apart
   int64_t n, x_stride;
   int32_t batch;
-  const double* sos_host;  // f64[n_sections][6]
-  int32_t n_sections;      // 1 .. kIirMaxSections
-  const double* zi_host;   // f64[zi_rows][n_sections][2] or nullptr (zero state)
+  const double* zi_host;   // f64[zi_rows][states of the filter] or nullptr (zero state)
   int32_t zi_rows;         // 1 or batch
-  bool zi_times_first;     // the start state of a row is zi * (its first logical sample): sosfiltfilt
-  double* zf_host;         // f64[batch][n_sections][2] or nullptr
+  bool zi_times_first;     // the start state of a row is zi * (its first logical sample): the forward-backward filters
+  double* zf_host;         // f64[batch][states of the filter] or nullptr
   int32_t direction;
   float* y;                // device
   int64_t y_stride, out_off, out_len;
+};
+// kernels_iir.hip: Filters.sosfilt / sosfiltfilt (include/nxsig.h states the definition, DESIGN.md section 3.13 the design).  One
+// run of the cascade; a row has 2 n_sections states ([n_sections][2])
+struct IirLaunch : ScanLaunch {
+  const double* sos_host;  // f64[n_sections][6]
+  int32_t n_sections;      // 1 .. kIirMaxSections
 };
 int launch_sosfilt(Ctx* c, const IirLaunch& a);
 // sosfiltfilt: x rows -> extended rows (padtype 1 odd, 2 even, 3 constant; edge samples each side) in kScratchFirLong, forward,
@@ -611,22 +615,9 @@ int launch_dct(Ctx* c, const DctLaunch& a);
 
 namespace nxsig {
 // kernels_lfilter.hip: Filters.lfilter / filtfilt (include/nxsig.h states the definition, DESIGN.md section 3.18 the design; the argument
-// checks are the caller's).  One run of the filter over `batch` rows, with IirLaunch's conventions: logical sample i of a row is physical
-// sample i (direction 0) or n - 1 - i (direction 1); output sample p (physical) goes to y[row * y_stride + p - out_off] when
-// 0 <= p - out_off < out_len.  Temporaries (chunk and tile states, zi, zf) live in sosfilt's slot kScratchLongStftFrames.  Enqueued on
-// c->stream; only a call that returns zf or brings a zi of the caller's waits
-struct LfLaunch {
-  const float* x;          // device f32[batch][n], rows x_stride elements apart
-  int64_t n, x_stride;
-  int32_t batch;
+// checks are the caller's).  One run of the filter; a row has cf.n states, none when the filter is a gain
+struct LfLaunch : ScanLaunch {
   LfCoefs cf;              // b and a divided by a[0], zero-padded; cf.n the order 0 .. kLfMaxOrder
-  const double* zi_host;   // f64[zi_rows][order] or nullptr (zero state)
-  int32_t zi_rows;         // 1 or batch
-  bool zi_times_first;     // the start state of a row is zi * (its first logical sample): filtfilt
-  double* zf_host;         // f64[batch][order] or nullptr
-  int32_t direction;
-  float* y;                // device
-  int64_t y_stride, out_off, out_len;
 };
 int launch_lfilter(Ctx* c, const LfLaunch& a);
 // filtfilt: x rows -> extended rows (padtype 1 odd, 2 even, 3 constant; edge samples each side) in kScratchFirLong, forward, backward,

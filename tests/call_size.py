@@ -96,12 +96,12 @@ CITE = {
     "lfilter.lanes": ("iir_plan.hpp:15", "constexpr int32_t kIirLanes = 64;"),
     "lfilter.chunk": ("lfilter_plan.hpp:23", "inline int32_t lf_chunk(int32_t n)"),
     "lfilter.tile": ("lfilter_plan.hpp:24", "inline int32_t lf_tile(int32_t n) { return lf_chunk(n) * kIirLanes; }"),
-    "lfilter.generic_row": ("kernels_lfilter.hip:243", "const int64_t row = (int64_t)blockIdx.x * kLanes + threadIdx.x;"),
-    "lfilter.generic_grid": ("kernels_lfilter.hip:364", "dim3((unsigned)(((int64_t)a.batch + kLanes - 1) / kLanes))"),
-    "lfilter.scan_grid": ("kernels_lfilter.hip:367", "const unsigned blocks = (unsigned)(g.tiles * a.batch);"),
-    "lfilter.carry_grid": ("kernels_lfilter.hip:372", "hipLaunchKernelGGL(k_lf_carry<NP>, dim3((unsigned)a.batch)"),
-    "lfilter.p_elems": ("kernels_lfilter.hip:329", "const size_t p_elems = scan ? (size_t)a.batch * g.tiles * NP * kLanes : 0;"),
-    "lfilter.tile_start": ("kernels_lfilter.hip:230", "double* ts = tile_start + (row * g.tiles + t) * NP;"),
+    "lfilter.generic_row": ("recurrence_scan.hpp:235", "const int64_t row = (int64_t)blockIdx.x * kLanes + threadIdx.x;"),
+    "lfilter.generic_grid": ("recurrence_scan.hpp:326", "dim3((unsigned)(((int64_t)a.batch + kLanes - 1) / kLanes))"),
+    "lfilter.scan_grid": ("recurrence_scan.hpp:329", "const unsigned blocks = (unsigned)(g.tiles * a.batch);"),
+    "lfilter.carry_grid": ("recurrence_scan.hpp:333", "hipLaunchKernelGGL(k_scan_carry<F>, dim3((unsigned)a.batch)"),
+    "lfilter.p_elems": ("recurrence_scan.hpp:291", "const size_t p_elems = scan ? (size_t)a.batch * g.tiles * NP * kLanes : 0;"),
+    "lfilter.tile_start": ("recurrence_scan.hpp:221", "double* ts = tile_start + (row * g.tiles + t) * NP;"),
 }
 
 
@@ -373,7 +373,7 @@ class FindPeaks:
 # ----------------------------------------------------------------------------------------------------------------------------- lfilter
 @dataclass(frozen=True)
 class Lfilter:
-    """kernels_lfilter.hip run<NP>: scan passes on tiles * batch workgroups and one carry workgroup per row; the plain recurrence on
+    """recurrence_scan.hpp run<F> for kernels_lfilter.hip: scan passes on tiles * batch workgroups and one carry workgroup per row; the plain recurrence on
     ceil(batch / 64) workgroups of 64 rows"""
     order: int
     n: int

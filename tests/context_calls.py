@@ -486,7 +486,7 @@ def _newer_families():
     sos = _golden("iir_vectors.json")
     sos2, sos4 = np.array(sos["butter4_lp4k"]["sos"], np.float64), np.array(sos["cheby1_8_lp100"]["sos"], np.float64)
     assert sos2.shape == (2, 6) and sos4.shape == (4, 6)
-    iir16 = {frames16: "kernels_iir.hip:306"}
+    iir16 = {frames16: "recurrence_scan.hpp:298"}
     E.append(_rows_entry("sosfilt-scan", 2, 2049, lambda S, ctx, a, dev: S.filters.sosfilt(dev(a["x"]), sos2, ctx=ctx), "sosfilt.scan", iir16, ("iir-scan",),
                          {stage_a: "api.cpp:2420", stage_out: "api.cpp:2421"}, twin="x", switch=("DISABLE_SOSFILT_SCAN", 1)))
     E.append(_rows_entry("sosfilt-one-chunk-generic", 2, 32, lambda S, ctx, a, dev: S.filters.sosfilt(dev(a["x"]), sos2, ctx=ctx), "sosfilt.generic", iir16, (),
@@ -495,14 +495,14 @@ def _newer_families():
                          ("iir-scan",), {stage_a: "api.cpp:2420", stage_out: "api.cpp:2421"}, twin="x",
                          more=lambda rng, rows: {"zi": 0.1 * rng.standard_normal((4, rows, 2))}))
     E.append(_rows_entry("sosfiltfilt-odd", 2, 4097, lambda S, ctx, a, dev: S.filters.sosfiltfilt(dev(a["x"]), sos4, ctx=ctx, padtype="odd"), "sosfilt.scan",
-                         {**iir16, long21: "kernels_iir.hip:400"}, ("iir-scan", "iir-zi"), {stage_a: "api.cpp:2449", stage_out: "api.cpp:2450"}, twin="x"))
+                         {**iir16, long21: "recurrence_scan.hpp:367"}, ("iir-scan", "iir-zi"), {stage_a: "api.cpp:2449", stage_out: "api.cpp:2450"}, twin="x"))
 
     # ---- lfilter / filtfilt: the same regions of the same two slots.  Order 2: chunks of 32, tiles of 2048; order 6: 64 and 4096 (NP = 2 / 8)
     ba = _golden("lfilter_vectors.json")
     b2, a2 = (np.array(ba["butter2_lp02"][k], np.float64) for k in "ba")
     b6, a6 = (np.array(ba["ellip6"][k], np.float64) for k in "ba")
     assert ba["butter2_lp02"]["on_scan"] and ba["ellip6"]["on_scan"] and len(a2) == 3 and len(a6) == 7
-    lf16 = {frames16: "kernels_lfilter.hip:336"}
+    lf16 = {frames16: "recurrence_scan.hpp:298"}
     E.append(_rows_entry("lfilter-scan", 2, 2049, lambda S, ctx, a, dev: S.filters.lfilter(dev(a["x"]), b2, a2, ctx=ctx), "lfilter.scan", lf16, ("lfilter-scan",),
                          {stage_a: "api.cpp:2503", stage_out: "api.cpp:2504"}, twin="x", switch=("DISABLE_LFILTER_SCAN", 1)))
     E.append(_rows_entry("lfilter-one-chunk-generic", 2, 32, lambda S, ctx, a, dev: S.filters.lfilter(dev(a["x"]), b2, a2, ctx=ctx), "lfilter.generic", lf16, (),
@@ -511,7 +511,7 @@ def _newer_families():
                          ("lfilter-scan",), {stage_a: "api.cpp:2503", stage_out: "api.cpp:2504"}, twin="x",
                          more=lambda rng, rows: {"zi": 0.1 * rng.standard_normal((rows, 6))}))
     E.append(_rows_entry("filtfilt-odd", 2, 2049, lambda S, ctx, a, dev: S.filters.filtfilt(dev(a["x"]), b2, a2, ctx=ctx, padtype="odd"), "lfilter.scan",
-                         {**lf16, long21: "kernels_lfilter.hip:406"}, ("lfilter-scan", "lfilter-zi"), {stage_a: "api.cpp:2534", stage_out: "api.cpp:2535"},
+                         {**lf16, long21: "recurrence_scan.hpp:367"}, ("lfilter-scan", "lfilter-zi"), {stage_a: "api.cpp:2534", stage_out: "api.cpp:2535"},
                          twin="x"))
 
     # ---- find_peaks: the layouts of slots 29 / 30 differ from argrelextrema's.  Prominence and width, so that the walks run; the generic

@@ -53,7 +53,8 @@ def test_every_line_that_takes_a_scratch_slot_is_cited():
     """the next family that moves into an old slot fails here until it has an entry of its own: every `ctx_scratch(<ctx>, kScratch...`
     call under csrc is cited by a claim, or excused with a reason (a site the Python mirror cannot reach on one context)"""
     sites = CC.scratch_sites()
-    assert len(sites) >= 52 and len({s for s, _ in sites}) == len(sites), len(sites)   # 52 when this test was written
+    # 50 today: 52 when this test was written, less the two pairs of sites of sosfilt and lfilter, which became one pair (recurrence_scan.hpp)
+    assert len(sites) >= 50 and len({s for s, _ in sites}) == len(sites), len(sites)
     assert {slot for _, slot in sites} <= set(CC.scratch_slots())
     cited = {}
     for e in CC.ENTRIES:

@@ -201,9 +201,13 @@ def test_the_switch_the_sources_and_the_documents_are_in_place():
     src = read("nx_signal_amd", "csrc", "kernels_iir.hip")
     assert "tune(c, kT_DISABLE_SOSFILT_SCAN, 0)" in src
     assert '("kernels_iir.hip", [])' in read("nx_signal_amd", "build.py")
-    # no atomics, no single-precision arithmetic on the recurrence, nothing included but the internal header
-    assert "atomic" not in src.lower() and re.findall(r'#include "([^"]+)"', src) == ["nxsig_internal.h"]
-    assert "fmaf" not in src and 'dispatch_note("sosfilt.scan")' in src and 'dispatch_note("sosfilt.generic")' in src
+    # no atomics, no single-precision arithmetic on the recurrence (the shared kernels of recurrence_scan.hpp included), nothing included
+    # but the internal header and those kernels
+    shared = read("nx_signal_amd", "csrc", "recurrence_scan.hpp")
+    assert "atomic" not in src.lower() and re.findall(r'#include "([^"]+)"', src) == ["nxsig_internal.h", "recurrence_scan.hpp"]
+    assert "atomic" not in shared.lower() and re.findall(r'#include "([^"]+)"', shared) == ["nxsig_internal.h"]
+    assert "fmaf" not in src and "fmaf" not in shared
+    assert 'dispatch_note("sosfilt.scan")' in src and 'dispatch_note("sosfilt.generic")' in src
     assert "NXSIG_DISABLE_SOSFILT_SCAN" in read("INTEGRATION.md")
     design = read("DESIGN.md")
     assert "3.13" in design and "NxSignalAMD.Filters.sosfilt" in design and "lfilter" in design

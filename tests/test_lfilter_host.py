@@ -284,9 +284,13 @@ def test_the_switch_the_sources_and_the_documents_are_in_place():
     src = read("nx_signal_amd", "csrc", "kernels_lfilter.hip")
     assert "tune(c, kT_DISABLE_LFILTER_SCAN, 0)" in src
     assert '("kernels_lfilter.hip", [])' in read("nx_signal_amd", "build.py")
-    # no atomics, no single-precision arithmetic on the recurrence, nothing included but the internal header
-    assert "atomic" not in src.lower() and re.findall(r'#include "([^"]+)"', src) == ["nxsig_internal.h"]
-    assert "fmaf" not in src and 'dispatch_note("lfilter.scan")' in src and 'dispatch_note("lfilter.generic")' in src
+    # no atomics, no single-precision arithmetic on the recurrence (the shared kernels of recurrence_scan.hpp included), nothing included
+    # but the internal header and those kernels
+    shared = read("nx_signal_amd", "csrc", "recurrence_scan.hpp")
+    assert "atomic" not in src.lower() and re.findall(r'#include "([^"]+)"', src) == ["nxsig_internal.h", "recurrence_scan.hpp"]
+    assert "atomic" not in shared.lower() and re.findall(r'#include "([^"]+)"', shared) == ["nxsig_internal.h"]
+    assert "fmaf" not in src and "fmaf" not in shared
+    assert 'dispatch_note("lfilter.scan")' in src and 'dispatch_note("lfilter.generic")' in src
     plan = read("nx_signal_amd", "csrc", "lfilter_plan.hpp")
     assert "hip" not in plan.replace("free of HIP", "").lower() and '#include "iir_plan.hpp"' in plan and "kLfGuardMax" in plan
     assert "NXSIG_DISABLE_LFILTER_SCAN" in read("INTEGRATION.md")
