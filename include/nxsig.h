@@ -1093,6 +1093,69 @@ int nxsig_fir_bank(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch,
 int nxsig_cwt(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int64_t batch_stride, int32_t wavelet, const double* widths,
               int64_t num_widths, double w, int32_t kind, void* out, int32_t mem);
 
+/*
+ * Convolution.correlate_rows / convolve_rows — scipy.signal.correlate / convolve of SciPy 1.15.3 on row PAIRS: row r of one device (or
+ * host) tensor with row r of another, both real f32 or both c64.  The reference has no pairwise call; DESIGN.md section 3.22.
+ * THE DEFINITION: for rows x[0 .. n1) and y[0 .. n2)
+ *     correlate   full[k] = sum_l x[l] conj(y[l - k + n2 - 1]),   k = 0 .. n1 + n2 - 2   (the lag of full[k] is k - (n2 - 1))
+ *     convolve    full[k] = sum_l x[l] y[k - l].
+ * mode (nxsig_conv_mode) selects a window of full: FULL all of it; SAME the n1 elements from (n2 - 1) / 2 (centred on full); VALID the
+ * max(n1, n2) - min(n1, n2) + 1 elements from min(n1, n2) - 1, n2 > n1 included.  nxsig_conv_length(n1, n2, mode) is the window's
+ * length n_out; the result is SciPy's per pair for every op and mode.
+ * a [batch][n1] rows a_stride >= n1 elements apart; b [batch][n2] rows b_stride >= n2 apart, or b_stride = 0: ONE row b for every
+ * pair (a shared template).  is_complex 0: f32 operands and result; 1: c64 operands and result.  a and b may be the same memory
+ * (autocorrelation); out (and out_lags) must not overlap an operand or each other.  batch = 0 succeeds and launches nothing.
+ * weighting NXSIG_XCORR_PHAT (correlate only) replaces the cross spectrum R[k] = X[k] conj(Y[k]) by
+ *     G[k] = R[k] / max(|R[k]|, phat_floor max_j |R[j]|),   G[k] = 0 where that denominator is 0 (a pair whose cross spectrum is zero),
+ * phat_floor in [0, 1).  G is not linear in the operands, so its inverse depends on the transform length: the contract fixes
+ *     P = nxsig_xcorr_fft_length(n1, n2) = max(1024, the next power of two >= n1 + n2 - 1)      for BOTH dispatch families,
+ * X = DFT_P(x), Y = DFT_P(y) of the zero-padded rows, and the weighted result is the mode's window of IDFT_P(G) (with its 1 / P).
+ * sink NXSIG_XCORR_PEAK (correlate only) writes per pair, instead of the row, out_lags[r] = scipy.signal.correlation_lags(n1, n2,
+ * mode)[i] and out[r] = window[i] at i = the first maximum in lag order (np.argmax) of the window's values (real pairs) or of their
+ * moduli (c64 pairs: the f32 rounding of sqrt(re^2 + im^2) evaluated in double); out is then [batch], the [batch][n_out] rows are
+ * never written.  SciPy's "same" lags are not always the lags of the "same" values (odd n1 with even n2 differ by one); the sink
+ * reports correlation_lags' entry as it stands.
+ * Dispatch families:
+ *   xcorr.wave     n1 + n2 - 1 <= 1024, and real pairs up to 2048: one wave per pair on the wave-private transform cores, in czt.wave's
+ *                  layout, LDS budget and rows-per-wave geometry.  A real pair is packed as z = x + i y into ONE forward transform,
+ *                  X and Y recovered from Z[k] and Z[P - k] (fetched through the wave's LDS strip); each row is first scaled by the power
+ *                  of two that brings its largest magnitude into [0.5, 1) and the scale is undone at the sink — exact, and needed: the
+ *                  packed transform's error is relative to the larger row (rows of 1e4 against 1e-4 lose everything without it).  A c64
+ *                  pair takes two forward transforms; at 2048 points that does not fit the register file, so c64 pairs with
+ *                  n1 + n2 - 1 > 1024 run on xcorr.generic.  The operands are read once and the result written once
+ *   xcorr.generic  everything else and everything under NXSIG_XCORR_WAVE=0 / NXSIG_DISABLE_WAVE: a pad kernel writes dense zero-padded
+ *                  c64 rows [rows][P] of both operands (a shared template once), nxsig_fft's row transforms forward on both, the
+ *                  product (PHAT after a per-row maximum), the inverse transform, a sink kernel.  Its four temporaries are its own,
+ *                  kept by the context; the batch runs in slabs of pairs so that they stay within 256 MiB together (one pair when a
+ *                  single pair is larger); NXSIG_XCORR_SLAB_ROWS (0 = automatic) forces the slab
+ * Both are single-precision transforms: an element is within 1e-5 ||x||_2 ||y||_2 of the definition in double (the Cauchy-Schwarz
+ * bound of any element), and a row of noise within 1e-5 of its maximum; the families need not agree to the bit.  No atomics; a
+ * pair's bits depend neither on the batch nor on its neighbours in a wave or slab.
+ * Non-finite rule: a pair in which either row holds an Inf / NaN has no finite output element; under the peak sink its value is NaN
+ * and its lag 0.  Carried out on bin 0 of the forward transforms (the sum of the samples): when it is not finite the pair's cross
+ * spectrum is replaced by NaN.  No other pair changes.  A pair of finite samples whose products overflow single precision (c64 rows near
+ * 1e19) comes out Inf / NaN as any f32 arithmetic would; when its whole window is NaN the peak sink writes NaN and lag 0 as well.  The
+ * PHAT weighting is formed on the cross spectrum scaled under 1 by a power of two, so it neither overflows nor vanishes where R is finite.
+ * Limits: n1, n2 >= 1, a_stride >= n1, b_stride = 0 or >= n2, phat_floor in [0, 1); PHAT and the peak sink with convolve are refused.
+ * n1 + n2 - 1 over 2^30, lengths the row transforms of nxsig_fft refuse and rows whose byte counts overflow are NXSIG_ERR_UNSUPPORTED.
+ * Not built: f64 / c128 pairs (there is no double tier), mixed real / complex pairs, n-D correlation, device tensors along another axis
+ * than the last, max_lag windows, "coeff" normalisation, sharded entry points, NIF and Elixir functions.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+#define NXSIG_XCORR_CONVOLVE 0
+#define NXSIG_XCORR_CORRELATE 1
+#define NXSIG_XCORR_PLAIN 0
+#define NXSIG_XCORR_PHAT 1
+#define NXSIG_XCORR_ROWS 0
+#define NXSIG_XCORR_PEAK 1
+/* out_lags: s32 [batch] under NXSIG_XCORR_PEAK, else NULL (ignored) */
+/* P of the contract: max(1024, the next power of two >= n1 + n2 - 1); negative status for n1 < 1, n2 < 1 or n1 + n2 - 1 > 2^30.
+ * Host only, no context */
+int64_t nxsig_xcorr_fft_length(int64_t n1, int64_t n2);
+int nxsig_xcorr(nxsig_ctx* ctx, const void* a, int64_t n1, int64_t a_stride, const void* b, int64_t n2, int64_t b_stride, int64_t batch,
+                int32_t is_complex, int32_t op, int32_t mode, int32_t weighting, double phat_floor, int32_t sink, void* out,
+                int32_t* out_lags, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,8 @@ SIGNATURES = {
     "nxsig_cwt_wavelet": (C.c_int, [_i32, _f64, _f64, _i64, C.POINTER(_f64)]),
     "nxsig_fir_bank": (C.c_int, [_ctx_iir, _p, _i64, _i64, _i64, _p, _i32, C.POINTER(_i64), _i64, _i32, _p, _i32]),
     "nxsig_cwt": (C.c_int, [_ctx_iir, _p, _i64, _i64, _i64, _i32, C.POINTER(_f64), _i64, _f64, _i32, _p, _i32]),
+    "nxsig_xcorr_fft_length": (_i64, [_i64, _i64]),   # host only: no tensor operand, no context
+    "nxsig_xcorr": (C.c_int, [_ctx_iir, _p, _i64, _i64, _p, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f64, _i32, _p, _p, _i32]),
     "nxsig_sawtooth": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _i32]),
     "nxsig_square": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _p, _i32]),
     "nxsig_gaussian_pulse": (C.c_int, [_p, _p, _i32, _i64, _f64, _f64, _f64, _p, _p, _p, _i32]),

@@ -63,6 +63,7 @@ UNITS = [
     ("kernels_lombscargle.hip", []),  # Spectral.lombscargle: periodograms of unevenly sampled rows, one double sincos per (t, w) shared by a block of rows
     ("kernels_czt.hip", []),  # Transforms.czt / zoom_fft: Bluestein's three table products around the forward and inverse cores of one wave
     ("kernels_cwt.hip", []),  # Transforms.cwt / Filters.fir_bank: one forward transform of a block shared by every filter of a bank, sinks fused
+    ("kernels_xcorr.hip", []),  # Convolution.correlate_rows / convolve_rows: row pairs, two real rows packed into one forward core, PHAT and peak sinks fused
 ]
 
 

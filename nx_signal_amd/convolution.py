@@ -165,3 +165,7 @@ def fftconvolve(in1, in2, ctx=None, **opts):
             return full[start:start + new]
         x, h32 = Operand(h32), x.host  # convolution commutes; keep the longer operand as the stream
     return _fir(lib.nxsig_fir_f32, x, h32, mode, ctx)
+
+
+# correlate_rows / convolve_rows / correlation_lags live in a module of their own (_xcorr.py) and are part of this one's interface
+from ._xcorr import convolve_rows, correlate_rows, correlation_lags  # noqa: E402,F401

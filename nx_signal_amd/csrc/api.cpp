@@ -2887,3 +2887,49 @@ int nxsig_cwt(nxsig_ctx* ctx, const void* x, int64_t length, int64_t batch, int6
 }
 
 }  // extern "C"
+
+/* ---------------------------------------------------------------- Convolution.correlate_rows / convolve_rows */
+extern "C" {
+
+int64_t nxsig_xcorr_fft_length(int64_t n1, int64_t n2) {
+  if (n1 < 1 || n2 < 1) return set_error(NXSIG_ERR_INVALID_ARG, "xcorr_fft_length: lengths must be >= 1");
+  if (n1 > ((int64_t)1 << 30) || n2 > ((int64_t)1 << 30) || xcorr_need(n1, n2) > ((int64_t)1 << 30))
+    return set_error(NXSIG_ERR_UNSUPPORTED, "xcorr_fft_length: n1 + n2 - 1 must be at most 2^30");
+  return xcorr_fft_length(n1, n2);
+}
+
+int nxsig_xcorr(nxsig_ctx* ctx, const void* a, int64_t n1, int64_t a_stride, const void* b, int64_t n2, int64_t b_stride, int64_t batch,
+                int32_t is_complex, int32_t op, int32_t mode, int32_t weighting, double phat_floor, int32_t sink, void* out,
+                int32_t* out_lags, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!a || !b || !out || (sink == kXcPeak && !out_lags)) return set_error(NXSIG_ERR_INVALID_ARG, "xcorr: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = xcorr_check(n1, a_stride, n2, b_stride, batch, is_complex, op, mode, weighting, phat_floor, sink, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("xcorr: ") + what);
+  const size_t es = is_complex ? sizeof(float2) : sizeof(float);
+  const bool peak = sink == kXcPeak;
+  const size_t a_bytes = batch ? ((size_t)(batch - 1) * a_stride + n1) * es : 0, b_bytes = batch ? ((size_t)(batch - 1) * b_stride + n2) * es : 0;
+  const size_t out_bytes = (size_t)batch * (peak ? 1 : xcorr_out_length(n1, n2, mode)) * es, lag_bytes = peak ? (size_t)batch * sizeof(int32_t) : 0;
+  if (czt_overlap(a, a_bytes, out, out_bytes) || czt_overlap(b, b_bytes, out, out_bytes) || czt_overlap(a, a_bytes, out_lags, lag_bytes) ||
+      czt_overlap(b, b_bytes, out_lags, lag_bytes) || czt_overlap(out, out_bytes, out_lags, lag_bytes))
+    return set_error(NXSIG_ERR_INVALID_ARG, "xcorr: the result must not overlap an operand");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if (peak) rc = io.open({{a, a_bytes, kScratchNdStageA}, {b, b_bytes, kScratchNdStageB}}, {{out, out_bytes, kScratchNdStageOut}, {out_lags, lag_bytes, kScratchNdStageOut}});
+  else rc = io.open({{a, a_bytes, kScratchNdStageA}, {b, b_bytes, kScratchNdStageB}}, {{out, out_bytes, kScratchNdStageOut}});
+  if (rc) return rc;
+  XcorrLaunch l;
+  l.a = io.in[0]; l.b = io.in[1]; l.is_complex = is_complex != 0; l.n1 = n1; l.a_stride = a_stride; l.n2 = n2; l.b_stride = b_stride; l.batch = batch;
+  l.op = op; l.mode = mode; l.weighting = weighting; l.sink = sink; l.phat_floor = (float)phat_floor;
+  l.out = io.out[0]; l.out_lags = peak ? static_cast<int32_t*>(io.out[1]) : nullptr;
+  if ((rc = launch_xcorr(c, l))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+}  // extern "C"

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(LOMBSCARGLE_TILE)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(XCORR_WAVE) X(XCORR_SLAB_ROWS) X(LOMBSCARGLE_TILE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -208,7 +208,7 @@ struct Ctx {
   size_t pin_bytes = 0; hipStream_t xfer_stream = nullptr;
   hipEvent_t xfer_ev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t xfer_ready = nullptr;
   // czt.generic's two temporaries (kernels_czt.hip), its own: grown on demand like a scratch slot, kept from call to call, freed with the context
-  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra; OwnedBuffer cwt_flags, cwt_rows, cwt_spectra, cwt_conv;   // ... and cwt's own (kernels_cwt.hip), kept the same way: the per-row non-finite flags (zero between calls), cwt.generic's three temporaries
+  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra; OwnedBuffer cwt_flags, cwt_rows, cwt_spectra, cwt_conv; OwnedBuffer xcorr_a, xcorr_b, xcorr_sa, xcorr_sb;   // ... and cwt's own (kernels_cwt.hip), kept the same way: the per-row non-finite flags (zero between calls), cwt.generic's three temporaries; xcorr.generic's four temporaries (kernels_xcorr.hip), kept the same way: the padded rows of either operand and their spectra, one slab of pairs each
   std::string last_dispatch;                // kernel families of the last compute call on this context (nxsig_ctx_last_dispatch)
   Tuning tuning;                            // dispatch / geometry switches (environment at creation, nxsig_ctx_set_tuning later)
 };
@@ -683,4 +683,24 @@ struct CwtLaunch {
   void* out;                  // device, dense [batch][num_filters][length]: c64 (kCwComplex) or f32
 };
 int launch_cwt(Ctx* c, const CwtLaunch& a);
+}  // namespace nxsig
+
+#include "xcorr_plan.hpp"
+
+namespace nxsig {
+// kernels_xcorr.hip: Convolution.correlate_rows / convolve_rows over device rows (include/nxsig.h states the definition, DESIGN.md
+// section 3.22 the design; the argument checks are the caller's).  xcorr.wave uses no temporary and no table beyond the wave twiddles;
+// xcorr.generic keeps four temporaries of its own (Ctx::xcorr_a / xcorr_b: the zero-padded rows, later the cross spectrum;
+// Ctx::xcorr_sa / xcorr_sb: the spectra, later the circular result) and walks the batch in slabs.  Everything is enqueued on c->stream
+struct XcorrLaunch {
+  const void* a;           // device f32 / c64 [batch][n1], rows a_stride elements apart
+  const void* b;           // device f32 / c64 [batch][n2], rows b_stride elements apart; b_stride 0: one row for every pair
+  bool is_complex;
+  int64_t n1, a_stride, n2, b_stride, batch;
+  int32_t op, mode, weighting, sink;
+  float phat_floor;
+  void* out;               // device, dense: [batch][n_out] (rows) or [batch] (peak), f32 or c64 as the operands
+  int32_t* out_lags;       // device s32 [batch] (peak), else unused
+};
+int launch_xcorr(Ctx* c, const XcorrLaunch& a);
 }  // namespace nxsig

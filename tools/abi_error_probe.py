@@ -13,6 +13,7 @@ argument broken at a time; the return code, nxsig_last_error() and what landed i
     python tools/abi_error_probe.py --lombscargle [--real] [--write tests/golden/abi_error_table_lombscargle.json]
     python tools/abi_error_probe.py --czt [--real] [--write tests/golden/abi_error_table_czt.json]
     python tools/abi_error_probe.py --cwt [--real] [--write tests/golden/abi_error_table_cwt.json]
+    python tools/abi_error_probe.py --xcorr [--real] [--write tests/golden/abi_error_table_xcorr.json]
 
 Without --real every call gets ctx = NULL (needs no GPU): entry points that look at the context first answer "null context", the ones
 that validate first answer with the argument's own message.  With --real a context on device 0 is used: every broken case returns
@@ -31,7 +32,8 @@ nxsig_sosfiltfilt_f32 (tests/test_iir_host.py, tests/test_gpu_iir.py), PEAKS_TAB
 tests/test_gpu_dct.py), LFILTER_TABLE_ENTRIES (--lfilter) for nxsig_lfilter_f32 and nxsig_filtfilt_f32 (tests/test_lfilter_host.py,
 tests/test_gpu_lfilter.py), LOMBSCARGLE_TABLE_ENTRIES (--lombscargle) for nxsig_lombscargle (tests/test_lombscargle_host.py,
 tests/test_gpu_lombscargle.py), CZT_TABLE_ENTRIES (--czt) for nxsig_czt (tests/test_czt_host.py, tests/test_gpu_czt.py), CWT_TABLE_ENTRIES (--cwt) for nxsig_fir_bank
-and nxsig_cwt (tests/test_cwt_host.py, tests/test_gpu_cwt.py)."""
+and nxsig_cwt (tests/test_cwt_host.py, tests/test_gpu_cwt.py), XCORR_TABLE_ENTRIES (--xcorr) for nxsig_xcorr (tests/test_xcorr_host.py,
+tests/test_gpu_xcorr.py)."""
 import argparse
 import ctypes as C
 import json
@@ -57,6 +59,7 @@ GOLDEN_LFILTER = os.path.join(ROOT, "tests", "golden", "abi_error_table_lfilter.
 GOLDEN_LOMBSCARGLE = os.path.join(ROOT, "tests", "golden", "abi_error_table_lombscargle.json")
 GOLDEN_CZT = os.path.join(ROOT, "tests", "golden", "abi_error_table_czt.json")
 GOLDEN_CWT = os.path.join(ROOT, "tests", "golden", "abi_error_table_cwt.json")
+GOLDEN_XCORR = os.path.join(ROOT, "tests", "golden", "abi_error_table_xcorr.json")
 NF_SENTINEL = -7   # *num_frames_out before every call: a case that leaves it alone reports this value
 NULL_ONLY = "null-ctx only"   # a broken value this entry point accepts: with a real context it would launch, so it runs with ctx = NULL alone
 
@@ -492,6 +495,24 @@ CWT_TABLE_ENTRIES = [
       ("length=2^24", {"length": 1 << 24, "batch_stride": 1 << 24})]),
 ]
 
+# Convolution.correlate_rows: 2 pairs of 24 against 9 real samples, PHAT-weighted, under the peak sink (so that out_lags is a required
+# pointer).  batch = 0 is valid and launches nothing, so it runs with ctx = NULL alone, where it shows that the argument checks let it
+# through to the context
+XL = 9
+XCORR_TABLE_ENTRIES = [
+    ("nxsig_xcorr",
+     [("a", "in", _f32(B, HL)), ("n1", "v", HL), ("a_stride", "v", HL), ("b", "in", _f32(B, XL)), ("n2", "v", XL), ("b_stride", "v", XL), ("batch", "v", B),
+      ("is_complex", "v", 0), ("op", "v", 1), ("mode", "v", 0), ("weighting", "v", 1), ("phat_floor", "v", 0.001), ("sink", "v", 1),
+      ("out", "out", np.zeros(B, np.float32)), ("out_lags", "out", np.zeros(B, np.int32)), ("mem", "mem", None)],
+     [("batch=0", {"batch": 0}, NULL_ONLY), ("batch=-1", {"batch": -1}), ("n1=0", {"n1": 0}), ("n2=0", {"n2": 0}), ("n2=-1", {"n2": -1}),
+      ("a_stride=n1-1", {"a_stride": HL - 1}), ("b_stride=n2-1", {"b_stride": XL - 1}), ("b_stride=-1", {"b_stride": -1}),
+      ("is_complex=2", {"is_complex": 2}), ("op=2", {"op": 2}), ("op=-1", {"op": -1}), ("mode=3", {"mode": 3}), ("weighting=2", {"weighting": 2}),
+      ("sink=2", {"sink": 2}), ("phat with convolve", {"op": 0, "sink": 0}), ("peak with convolve", {"op": 0, "weighting": 0}),
+      ("phat_floor=1", {"phat_floor": 1.0}), ("phat_floor=-0.1", {"phat_floor": -0.1}), ("phat_floor=nan", {"phat_floor": float("nan")}),
+      ("n1+n2-1=2^30+1", {"n2": (1 << 30) - HL + 2, "b_stride": 0}), ("n1=2^31", {"n1": 1 << 31, "a_stride": 1 << 31}),
+      ("rows too large", {"a_stride": 1 << 59, "batch": 16}), ("result too large", {"batch": 1 << 40})]),
+]
+
 
 def _cases(args, listed):
     out = [("valid", {})]
@@ -613,9 +634,10 @@ def main():
     ap.add_argument("--lombscargle", action="store_true", help="the entry point of LOMBSCARGLE_TABLE_ENTRIES (Spectral.lombscargle)")
     ap.add_argument("--czt", action="store_true", help="the entry point of CZT_TABLE_ENTRIES (Transforms.czt / zoom_fft)")
     ap.add_argument("--cwt", action="store_true", help="the entry points of CWT_TABLE_ENTRIES (Filters.fir_bank / Transforms.cwt)")
+    ap.add_argument("--xcorr", action="store_true", help="the entry point of XCORR_TABLE_ENTRIES (Convolution.correlate_rows / convolve_rows)")
     a = ap.parse_args()
     key = "real_ctx" if a.real else "null_ctx"
-    table = probe(a.lib, a.real, CWT_TABLE_ENTRIES if a.cwt else CZT_TABLE_ENTRIES if a.czt else LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
+    table = probe(a.lib, a.real, XCORR_TABLE_ENTRIES if a.xcorr else CWT_TABLE_ENTRIES if a.cwt else CZT_TABLE_ENTRIES if a.czt else LOMBSCARGLE_TABLE_ENTRIES if a.lombscargle else LFILTER_TABLE_ENTRIES if a.lfilter else DCT_TABLE_ENTRIES if a.dct else HILBERT_TABLE_ENTRIES if a.hilbert else SAVGOL_TABLE_ENTRIES if a.savgol else PEAKS_TABLE_ENTRIES if a.peaks else IIR_TABLE_ENTRIES if a.iir else WELCH_TABLE_ENTRIES if a.welch else OWN_TABLE_ENTRIES if a.own else None)
     if not a.write:
         print(json.dumps({key: table}, indent=1))
         return
