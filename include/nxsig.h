@@ -1156,6 +1156,38 @@ int nxsig_xcorr(nxsig_ctx* ctx, const void* a, int64_t n1, int64_t a_stride, con
                 int32_t is_complex, int32_t op, int32_t mode, int32_t weighting, double phat_floor, int32_t sink, void* out,
                 int32_t* out_lags, int32_t mem);
 
+/* ---- Transforms.mdct / imdct (an extension: the lapped cosine transform of AAC, Vorbis, AC-3 and CELT) ----
+ * THE DEFINITION.  Frame length N = 2 M, M even and >= 2 (N a multiple of 4), hop M, window w of N real f32 samples (a HOST array
+ * whatever `mem` says), rows real f32.
+ *   forward  X[m, k] = g sum_{n=0}^{N-1} w[n] x[m M + n] cos(pi / M (n + 1/2 + M/2) (k + 1/2)),  k = 0 .. M - 1;
+ *            g = 1 under NXSIG_MDCT_NORM_NONE, sqrt(2 / M) under NXSIG_MDCT_NORM_ORTHO
+ *   inverse  y[m M + n] += g w[n] sum_k X[m, k] cos(the same argument);  g = 2 / M under NONE, sqrt(2 / M) under ORTHO.
+ *            With w[n]^2 + w[n + M]^2 = 1 (Princen-Bradley), imdct(mdct(x)) = x on every sample that two frames cover
+ *   frames   pad_edges = 0: F = (L - N) / M + 1 (a ragged tail is dropped, as in stft / welch), L >= N.
+ *            pad_edges = 1: the row is taken as M zeros, the row, then zeros up to (F + 1) M samples, F = ceil(L / M) + 1; nothing is
+ *            padded in memory, and every sample lies under two frames
+ *   inverse length  pad_edges = 0: out_length = (F + 1) M.  pad_edges = 1: the out_length samples after the first M, 1 <= out_length
+ *            <= F M (the Python mirror's default is (F - 1) M), so imdct(mdct(x, pad_edges), pad_edges, out_length = L) is x
+ *   fold     with the windowed frame f = w x in quarters a, b, c, d of M / 2 samples, X[m, .] is the DCT-IV
+ *            (sum u[n] cos(pi / M (n + 1/2)(k + 1/2))) of u = [-rev(c) - d, a - rev(b)]: one complex transform of M / 2 points
+ *            between two twiddle products, which is what both tiers compute
+ * Non-finite rule: an Inf / NaN sample makes exactly the frames that cover it non-finite, every coefficient of them; an Inf / NaN
+ * coefficient of frame m makes exactly the output samples [m M, m M + N) non-finite.  Neighbours keep their values.
+ * Dispatch: "mdct.wave" / "imdct.wave" for M = 256, 512, 1024, "mdct.generic" / "imdct.generic" (followed by the row transforms'
+ * families) for every other M and under NXSIG_MDCT_WAVE=0 or NXSIG_DISABLE_WAVE.  x rows lie batch_stride >= length elements apart and
+ * may start at any 4-byte address; out is dense f32 [batch][F][M]; X is dense f32 [batch][frames][M], the inverse's out dense
+ * f32 [batch][out_length].  Not built: f64 and complex rows, windows on the device, sharded entry points, NIF and Elixir functions.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+#define NXSIG_MDCT_NORM_NONE 0
+#define NXSIG_MDCT_NORM_ORTHO 1
+/* F of the contract; negative status when the arguments are refused.  Host only, no context */
+int64_t nxsig_mdct_frames(int64_t length, int64_t frame_length, int32_t pad_edges);
+int nxsig_mdct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch, int64_t batch_stride, const float* window, int64_t frame_length,
+                   int32_t pad_edges, int32_t norm, float* out, int32_t mem);
+int nxsig_imdct_f32(nxsig_ctx* ctx, const float* X, int64_t frames, int64_t batch, const float* window, int64_t frame_length, int32_t pad_edges,
+                    int32_t norm, float* out, int64_t out_length, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

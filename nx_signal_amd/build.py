@@ -64,6 +64,9 @@ UNITS = [
     ("kernels_czt.hip", []),  # Transforms.czt / zoom_fft: Bluestein's three table products around the forward and inverse cores of one wave
     ("kernels_cwt.hip", []),  # Transforms.cwt / Filters.fir_bank: one forward transform of a block shared by every filter of a bank, sinks fused
     ("kernels_xcorr.hip", []),  # Convolution.correlate_rows / convolve_rows: row pairs, two real rows packed into one forward core, PHAT and peak sinks fused
+    # Transforms.mdct / imdct: fold, carry and overlap-add in registers around a wave-private half-length transform (plain FP32 only:
+    # this unit is compiled without the packed-FP32 instructions)
+    ("kernels_mdct.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
 ]
 
 

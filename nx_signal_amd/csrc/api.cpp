@@ -2932,4 +2932,64 @@ int nxsig_xcorr(nxsig_ctx* ctx, const void* a, int64_t n1, int64_t a_stride, con
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Transforms.mdct / imdct */
+int64_t nxsig_mdct_frames(int64_t length, int64_t frame_length, int32_t pad_edges) {
+  bool unsupported = false;
+  if (const char* what = mdct_check(length, 1, length, frame_length, pad_edges, kMdNormNone, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("mdct_frames: ") + what);
+  return mdct_frames(length, frame_length, pad_edges != 0);
+}
+
+int nxsig_mdct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch, int64_t batch_stride, const float* window, int64_t frame_length,
+                   int32_t pad_edges, int32_t norm, float* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !window || !out) return set_error(NXSIG_ERR_INVALID_ARG, "mdct: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = mdct_check(length, batch, batch_stride, frame_length, pad_edges, norm, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("mdct: ") + what);
+  const int64_t frames = mdct_frames(length, frame_length, pad_edges != 0);
+  const size_t x_bytes = batch ? ((size_t)(batch - 1) * batch_stride + length) * sizeof(float) : 0;
+  const size_t out_bytes = (size_t)batch * frames * (frame_length / 2) * sizeof(float);
+  if (czt_overlap(x, x_bytes, out, out_bytes)) return set_error(NXSIG_ERR_INVALID_ARG, "mdct: x and out must not overlap");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, x_bytes, kScratchNdStageA}}, {{out, out_bytes, kScratchNdStageOut}}))) return rc;
+  MdctLaunch a;
+  a.inverse = false; a.in = static_cast<const float*>(io.in[0]); a.length = length; a.in_stride = batch_stride; a.batch = batch; a.frames = frames;
+  a.window_host = window; a.N = frame_length; a.pad = pad_edges; a.norm = norm; a.out = static_cast<float*>(io.out[0]);
+  if ((rc = launch_mdct(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
+int nxsig_imdct_f32(nxsig_ctx* ctx, const float* X, int64_t frames, int64_t batch, const float* window, int64_t frame_length, int32_t pad_edges,
+                    int32_t norm, float* out, int64_t out_length, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!X || !window || !out) return set_error(NXSIG_ERR_INVALID_ARG, "imdct: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = imdct_check(frames, batch, frame_length, pad_edges, norm, out_length, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("imdct: ") + what);
+  const size_t x_bytes = (size_t)batch * frames * (frame_length / 2) * sizeof(float), out_bytes = (size_t)batch * out_length * sizeof(float);
+  if (czt_overlap(X, x_bytes, out, out_bytes)) return set_error(NXSIG_ERR_INVALID_ARG, "imdct: X and out must not overlap");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{X, x_bytes, kScratchNdStageA}}, {{out, out_bytes, kScratchNdStageOut}}))) return rc;
+  MdctLaunch a;
+  a.inverse = true; a.in = static_cast<const float*>(io.in[0]); a.length = out_length; a.in_stride = 0; a.batch = batch; a.frames = frames;
+  a.window_host = window; a.N = frame_length; a.pad = pad_edges; a.norm = norm; a.out = static_cast<float*>(io.out[0]);
+  if ((rc = launch_mdct(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"

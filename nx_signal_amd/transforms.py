@@ -86,3 +86,5 @@ from ._dct import dct, idct  # noqa: E402,F401
 from ._czt import czt, czt_points, zoom_fft  # noqa: E402,F401
 # ... and so do cwt / morlet2 / ricker (_cwt.py)
 from ._cwt import cwt, morlet2, ricker  # noqa: E402,F401
+# ... and so do mdct / imdct / mdct_window (_mdct.py)
+from ._mdct import imdct, mdct, mdct_window  # noqa: E402,F401
