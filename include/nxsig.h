@@ -1188,6 +1188,35 @@ int nxsig_mdct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch
 int nxsig_imdct_f32(nxsig_ctx* ctx, const float* X, int64_t frames, int64_t batch, const float* window, int64_t frame_length, int32_t pad_edges,
                     int32_t norm, float* out, int64_t out_length, int32_t mem);
 
+/* ---- Transforms.phase_vocoder (an extension: librosa.phase_vocoder / torchaudio.functional.phase_vocoder, the step between stft and
+ * istft that changes a spectrogram's time base) ----
+ * THE DEFINITION.  z is c64 [batch][M][K], dense and time-major (what stft and stft_onesided return), M >= 1, K >= 1; `rate` a finite
+ * double > 0 (2 plays twice as fast).  The bins are independent, so any K is served: a full spectrum stays Hermitian, K / 2 + 1
+ * one-sided bins work.  The PACKED layout of stft_packed is excluded by contract: its bin 0 carries two values.
+ *   frames   n_out = ceil(M / rate), the quotient taken in double: len(numpy.arange(0, M, rate))
+ *   steps    s_t = t rate as one double product, i_t = floor(s_t), alpha_t = s_t - i_t.  Frames M and M + 1 count as zeros and are
+ *            never read
+ *   unit     u(z) = z / |z|, and u(0) = 1 for a zero of either sign.  (numpy has angle(-0 + 0i) = pi: a deviation that stft cannot
+ *            reach, whose cleaning rule writes +0.0)
+ *   phasor   U[0, k] = u(z[0, k]),  U[t + 1, k] = U[t, k] u(z[i_t + 1, k]) conj(u(z[i_t, k])), all in double
+ *   result   out[t, k] = f32(((1 - alpha_t) |z[i_t, k]| + alpha_t |z[i_t + 1, k]|) U[t, k]): magnitude and product in double, each
+ *            component rounded once.  out is dense c64 [batch][n_out][K]
+ * Equivalence: librosa and torchaudio accumulate phase_acc += phi_adv + wrap(angle(z[i + 1]) - angle(z[i]) - phi_adv) with the expected
+ * advance phi_adv = 2 pi hop k / n_fft.  The wrap changes its argument by a multiple of 2 pi, so modulo 2 pi the sum is
+ * angle(z[i + 1]) - angle(z[i]) whatever phi_adv is, and exp(i phase_acc) is the product of unit rotors above: the result is theirs
+ * for EVERY hop_length / phase_advance, which is why those arguments do not exist.  No atan2, no sincos, and no phase that grows
+ * with the row (their double phase_acc has lost 3e-7 after 15 000 frames; the product of unit numbers in double has not).
+ * Non-finite rule: bin k of a row is non-finite at every t from the first t whose pair (i_t, i_t + 1) holds an Inf / NaN in that bin;
+ * other bins and rows keep their values.
+ * Dispatch: "pvoc.walk" when a row's n_out output frames are one chunk (n_out <= 1024 by default), else "pvoc.scan" (chunk products,
+ * their exclusive prefix per bin, the chunks' frames: three launches, z read twice; NXSIG_PVOC_CHUNK=n forces chunks of n frames).
+ * Not built: f64 / c128 spectra, sharded entry points, NIF and Elixir functions, a fused istft sink.
+ * Every argument check comes ahead of the context; a device call returns without waiting; z and out must not overlap.
+ */
+/* n_out of the contract; negative status when the arguments are refused.  Host only, no context */
+int64_t nxsig_pvoc_frames(int64_t frames, double rate);
+int nxsig_phase_vocoder_c64(nxsig_ctx* ctx, const void* z, int64_t batch, int64_t frames, int64_t bins, double rate, void* out, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,8 @@ UNITS = [
     # Transforms.mdct / imdct: fold, carry and overlap-add in registers around a wave-private half-length transform (plain FP32 only:
     # this unit is compiled without the packed-FP32 instructions)
     ("kernels_mdct.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
+    # Transforms.phase_vocoder: a double rotor product per bin, lanes own bins and waves walk time; a three-launch scan over chunks
+    ("kernels_pvoc.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
 ]
 
 

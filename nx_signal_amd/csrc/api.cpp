@@ -2992,4 +2992,35 @@ int nxsig_imdct_f32(nxsig_ctx* ctx, const float* X, int64_t frames, int64_t batc
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Transforms.phase_vocoder */
+int64_t nxsig_pvoc_frames(int64_t frames, double rate) {
+  bool unsupported = false;
+  if (const char* what = pvoc_check_rate(frames, rate, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("pvoc_frames: ") + what);
+  return pvoc_frames(frames, rate);
+}
+
+int nxsig_phase_vocoder_c64(nxsig_ctx* ctx, const void* z, int64_t batch, int64_t frames, int64_t bins, double rate, void* out, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!z || !out) return set_error(NXSIG_ERR_INVALID_ARG, "phase_vocoder: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = pvoc_check(batch, frames, bins, rate, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("phase_vocoder: ") + what);
+  const size_t z_bytes = (size_t)batch * frames * bins * sizeof(float2), out_bytes = (size_t)batch * pvoc_frames(frames, rate) * bins * sizeof(float2);
+  if (czt_overlap(z, z_bytes, out, out_bytes)) return set_error(NXSIG_ERR_INVALID_ARG, "phase_vocoder: z and out must not overlap");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{z, z_bytes, kScratchNdStageA}}, {{out, out_bytes, kScratchNdStageOut}}))) return rc;
+  PvocLaunch a;
+  a.z = io.in[0]; a.batch = batch; a.frames = frames; a.bins = bins; a.rate = rate; a.out = io.out[0];
+  if ((rc = launch_pvoc(c, a))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"

@@ -88,3 +88,5 @@ from ._czt import czt, czt_points, zoom_fft  # noqa: E402,F401
 from ._cwt import cwt, morlet2, ricker  # noqa: E402,F401
 # ... and so do mdct / imdct / mdct_window (_mdct.py)
 from ._mdct import imdct, mdct, mdct_window  # noqa: E402,F401
+# ... and so do phase_vocoder / time_stretch (_pvoc.py)
+from ._pvoc import phase_vocoder, time_stretch  # noqa: E402,F401
