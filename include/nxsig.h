@@ -1217,6 +1217,38 @@ int nxsig_imdct_f32(nxsig_ctx* ctx, const float* X, int64_t frames, int64_t batc
 int64_t nxsig_pvoc_frames(int64_t frames, double rate);
 int nxsig_phase_vocoder_c64(nxsig_ctx* ctx, const void* z, int64_t batch, int64_t frames, int64_t bins, double rate, void* out, int32_t mem);
 
+/* ---- Spectral.lpc (an extension: librosa.lpc, Burg's method of linear prediction, on every frame of every row; DESIGN.md section
+ * 3.25) ----
+ * THE DEFINITION.  A frame x[0 ... L-1], an order p with 1 <= p <= L - 1, all arithmetic in double:
+ *   f = x[1:], b = x[:-1], a = [1]
+ *   for m in 0 ... p-1:
+ *       k_m = -2 sum(f b) / (sum(f f) + sum(b b) + tiny)       tiny = DBL_MIN, so an all-zero frame gives k = 0
+ *       a   = [a, 0] + k_m reversed([a, 0])                    the Levinson step-up
+ *       f, b = (f + k_m b)[1:], (b + k_m f)[:-1]               both from the OLD f and b
+ *   e = (sum(x x) / L) prod(1 - k_m^2)
+ * Results per frame, rounded to f32 once: a[0 ... p] the prediction polynomial (what librosa.lpc returns), k[0 ... p-1] the reflection
+ * coefficients, e the prediction error power.  The denominator is summed afresh at every stage; librosa updates it by a recurrence
+ * and computes in the type of y, so for f32 rows this is librosa's result up to librosa's own single-precision rounding.
+ * Framing (librosa.util.frame): a row of n samples gives F = 1 + (n - frame_length) / hop frames (integer division) that start at
+ * multiples of hop; no padding; hop may exceed frame_length; frame_length = n is one frame, the whole row.  Rows lie batch_stride >= n
+ * elements apart.  a is dense f32 [batch][F][order + 1], k dense f32 [batch][F][order] or NULL, e dense f32 [batch][F] or NULL.
+ * Non-finite rule: an Inf / NaN sample makes every output of exactly the frames that contain it non-finite (a[0] too: 1 + k 0); every
+ * other frame keeps its bits.
+ * Dispatch: "lpc.wave" for frame_length <= 2048 (one wave owns a frame, its error sequences in double registers for all p stages),
+ * "lpc.rows" for longer frames and under NXSIG_LPC_WAVE=0 or NXSIG_DISABLE_WAVE (one launch per stage, the error sequences in a
+ * temporary the family keeps in the context, walked in slabs of frames that keep it within 256 MiB; one longer frame takes 32 bytes
+ * per sample).  A rule of frame_length and the switch alone, never of the batch.  Within 1e-5 of the definition on either tier, not the
+ * same bits.
+ * Refused: order < 1, order >= frame_length, hop < 1, frame_length > n, batch_stride < n (INVALID_ARG); orders above 128 ("orders up to
+ * 128 are built") and frames beyond 2^28 samples (UNSUPPORTED).  Not built: f64 and complex rows, the autocorrelation and covariance
+ * methods, windows, LSF / cepstrum conversion, sharded entry points, NIF and Elixir functions.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+/* F of the contract; negative status when the arguments are refused.  Host only, no context */
+int64_t nxsig_lpc_frames(int64_t n, int64_t frame_length, int64_t hop);
+int nxsig_lpc_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int64_t batch_stride, int64_t frame_length, int64_t hop,
+                  int64_t order, float* a, float* k, float* e, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

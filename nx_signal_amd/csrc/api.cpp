@@ -3023,4 +3023,42 @@ int nxsig_phase_vocoder_c64(nxsig_ctx* ctx, const void* z, int64_t batch, int64_
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Spectral.lpc */
+int64_t nxsig_lpc_frames(int64_t n, int64_t frame_length, int64_t hop) {
+  bool unsupported = false;
+  if (const char* what = lpc_check_framing(n, frame_length, hop, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("lpc_frames: ") + what);
+  return lpc_frames(n, frame_length, hop);
+}
+
+int nxsig_lpc_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int64_t batch_stride, int64_t frame_length, int64_t hop,
+                  int64_t order, float* a, float* k, float* e, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !a) return set_error(NXSIG_ERR_INVALID_ARG, "lpc: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = lpc_check(batch, n, batch_stride, frame_length, hop, order, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("lpc: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  const size_t frames = (size_t)batch * lpc_frames(n, frame_length, hop), fb = sizeof(float);
+  const HostIo::In in{x, rows_bytes((int32_t)batch, batch_stride, n, fb), kScratchNdStageA};
+  const HostIo::Out oa{a, frames * (order + 1) * fb, kScratchNdStageOut}, ok{k, frames * order * fb, kScratchNdStageOut}, oe{e, frames * fb, kScratchNdStageOut};
+  HostIo io(c, mem);   // k and e are optional: only the results asked for are staged, in the order a, k, e
+  if (k && e) rc = io.open({in}, {oa, ok, oe});
+  else if (k) rc = io.open({in}, {oa, ok});
+  else if (e) rc = io.open({in}, {oa, oe});
+  else rc = io.open({in}, {oa});
+  if (rc) return rc;
+  LpcLaunch l;
+  l.x = io.in[0]; l.batch = batch; l.n = n; l.x_stride = batch_stride; l.frame_length = frame_length; l.hop = hop; l.order = order;
+  l.a = io.out[0]; l.k = k ? io.out[1] : nullptr; l.e = e ? io.out[k ? 2 : 1] : nullptr;
+  if ((rc = launch_lpc(c, l))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"

@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(XCORR_WAVE) X(XCORR_SLAB_ROWS) X(MDCT_WAVE) X(PVOC_CHUNK) X(LOMBSCARGLE_TILE)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(XCORR_WAVE) X(XCORR_SLAB_ROWS) X(MDCT_WAVE) X(PVOC_CHUNK) X(LPC_WAVE) X(LOMBSCARGLE_TILE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -208,7 +208,7 @@ struct Ctx {
   size_t pin_bytes = 0; hipStream_t xfer_stream = nullptr;
   hipEvent_t xfer_ev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t xfer_ready = nullptr;
   // czt.generic's two temporaries (kernels_czt.hip), its own: grown on demand like a scratch slot, kept from call to call, freed with the context
-  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra; OwnedBuffer cwt_flags, cwt_rows, cwt_spectra, cwt_conv; OwnedBuffer xcorr_a, xcorr_b, xcorr_sa, xcorr_sb; OwnedBuffer mdct_points, mdct_spectra; OwnedBuffer pvoc_carry;   // ... and cwt's own (kernels_cwt.hip), kept the same way: the per-row non-finite flags (zero between calls), cwt.generic's three temporaries; xcorr.generic's four temporaries (kernels_xcorr.hip), kept the same way: the padded rows of either operand and their spectra, one slab of pairs each; mdct.generic / imdct.generic's two temporaries (kernels_mdct.hip), kept the same way: the frames' complex points and their transforms; pvoc.scan's chunk aggregates / carries (kernels_pvoc.hip), kept the same way
+  struct OwnedBuffer { void* ptr = nullptr; size_t bytes = 0; OwnedBuffer() = default; OwnedBuffer(const OwnedBuffer&) = delete; OwnedBuffer& operator=(const OwnedBuffer&) = delete; ~OwnedBuffer() { if (ptr) (void)hipFree(ptr); } } czt_rows, czt_spectra; OwnedBuffer cwt_flags, cwt_rows, cwt_spectra, cwt_conv; OwnedBuffer xcorr_a, xcorr_b, xcorr_sa, xcorr_sb; OwnedBuffer mdct_points, mdct_spectra; OwnedBuffer pvoc_carry; OwnedBuffer lpc_tmp;   // ... and cwt's own (kernels_cwt.hip), kept the same way: the per-row non-finite flags (zero between calls), cwt.generic's three temporaries; xcorr.generic's four temporaries (kernels_xcorr.hip), kept the same way: the padded rows of either operand and their spectra, one slab of pairs each; mdct.generic / imdct.generic's two temporaries (kernels_mdct.hip), kept the same way: the frames' complex points and their transforms; pvoc.scan's chunk aggregates / carries (kernels_pvoc.hip), kept the same way; lpc.rows' error sequences and partial sums of one slab of frames (kernels_lpc.hip), kept the same way
   std::string last_dispatch;                // kernel families of the last compute call on this context (nxsig_ctx_last_dispatch)
   Tuning tuning;                            // dispatch / geometry switches (environment at creation, nxsig_ctx_set_tuning later)
 };
@@ -738,4 +738,20 @@ struct PvocLaunch {
   void* out;                // device c64 [batch][pvoc_frames(frames, rate)][bins], dense
 };
 int launch_pvoc(Ctx* c, const PvocLaunch& a);
+}  // namespace nxsig
+
+#include "lpc_plan.hpp"
+
+namespace nxsig {
+// kernels_lpc.hip: Spectral.lpc over device rows (include/nxsig.h states the definition, DESIGN.md section 3.25 the design; the argument
+// checks are the caller's).  lpc.wave uses no temporary; lpc.rows keeps the error sequences of a slab of frames in one of its own
+// (Ctx::lpc_tmp).  Everything is enqueued on c->stream
+struct LpcLaunch {
+  const void* x;            // device f32 rows of n samples, x_stride elements apart
+  int64_t batch, n, x_stride, frame_length, hop, order;
+  void* a;                  // device f32 [batch][lpc_frames(n, frame_length, hop)][order + 1], dense
+  void* k;                  // device f32 [batch][frames][order], or null
+  void* e;                  // device f32 [batch][frames], or null
+};
+int launch_lpc(Ctx* c, const LpcLaunch& a);
 }  // namespace nxsig

@@ -133,3 +133,5 @@ def coherence(x, y, window, ctx=None, **opts):
 
 # lombscargle lives in a module of its own (_lombscargle.py)
 from ._lombscargle import lombscargle  # noqa: E402,F401
+# ... and so does lpc (_lpc.py)
+from ._lpc import lpc  # noqa: E402,F401
