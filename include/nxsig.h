@@ -1249,6 +1249,50 @@ int64_t nxsig_lpc_frames(int64_t n, int64_t frame_length, int64_t hop);
 int nxsig_lpc_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int64_t batch_stride, int64_t frame_length, int64_t hop,
                   int64_t order, float* a, float* k, float* e, int32_t mem);
 
+/* ---- Spectral.yin (an extension: the YIN fundamental-frequency estimate on every frame of every row, following librosa.yin;
+ * DESIGN.md section 3.26) ----
+ * THE DEFINITION.  A frame x[0 ... L-1], W = L / 2 (integer division), integer lags 1 <= pmin < pmax <= L - W - 1, T = pmax, a sampling
+ * rate sr > 0, a threshold thr > 0; all arithmetic in double (f32 samples convert exactly):
+ *   d(tau) = sum_{j = 1 .. W} (x[j] - x[j + tau])^2              tau = 0 ... T     a sum of squares of differences, never E + E - 2 r:
+ *                                                                                  d(0) = 0, a periodic frame gives exact zeros, d >= 0
+ *   c(tau) = d(tau) / ((1 / tau) sum_{u = 1 .. tau} d(u) + tiny)  tau = pmin ... pmax, tiny = DBL_MIN: an all-zero frame gives c = 0
+ *   with c indexed i = tau - pmin, m = pmax - pmin + 1 values:
+ *   trough(i) = c[i] < c[i-1] and c[i] <= c[i+1]                 0 < i < m - 1
+ *   trough(0) = c[0] < c[1];  trough(m-1) = c[m-1] < c[m-2]
+ *   i* = the first i with trough(i) and c[i] < thr; if there is none, the first index of min(c)
+ *   a = c[i*+1] + c[i*-1] - 2 c[i*],  b = (c[i*+1] - c[i*-1]) / 2
+ *   shift = -b / a  if 0 < i* < m - 1 and |b| < |a|,  else 0
+ *   f0 = sr / (pmin + i* + shift)         v = c[i*]
+ * Results per frame, rounded to f32 once, after the search has run on the double values: f0, v (the normalised difference at the chosen
+ * lag: small = voiced) and the m values of c.  This FOLLOWS librosa.yin (0.10), the sums starting at j = 1 and win_length =
+ * frame_length / 2 included; it does not equal it, for two reasons: every sum here is direct and in double, where librosa uses a
+ * single-precision FFT autocorrelation (d as E(0) + E(tau) - 2 r(tau), which cancels to 3 - 4 digits on a voiced frame); and librosa
+ * zeroes |acf| and |energy| below 1e-6, which is not reproduced.
+ * Framing: center = 0 is librosa.util.frame, F = 1 + (n - frame_length) / hop frames (integer division) that start at multiples of
+ * hop.  center = 1 extends the row by frame_length / 2 zeros on both sides first (pad_mode = "constant"), F = 1 + (n + 2
+ * (frame_length / 2) - frame_length) / hop; the padded row is never written, a sample outside the row loads as 0.  hop may exceed
+ * frame_length.  Rows lie batch_stride >= n elements apart.  f0 and v are dense f32 [batch][F], cmnd dense f32 [batch][F][m]; f0 may be
+ * NULL when cmnd is given (at least one of the two is required), v and cmnd may be NULL.
+ * Non-finite rule: a frame whose used samples x[1 ... W + pmax] hold an Inf / NaN gets f0 = v = NaN and an all-NaN row of c (a flag
+ * taken while the frame is staged decides, not the search); every other frame keeps its bits.  Sample 0 of a frame and the samples
+ * past W + pmax are never read into a sum.
+ * Deterministic: a frame's bits depend on (frame_length, pmin, pmax, thr, sr) and its samples alone, never on the batch, the grid or
+ * the neighbouring frames; partial sums are combined in a fixed order, no atomics.
+ * Dispatch: "yin.tile", one launch (the frame's used samples staged in LDS in double; a thread owns 1, 2, 4 or 8 consecutive lags, 64
+ * or 256 threads serve a frame; NXSIG_YIN_LAGS = 1 / 2 / 4 / 8 forces the lags per thread where 256 threads of it cover pmax + 1 lags:
+ * the same d, the prefix sum associated differently, so within the same 1e-5 and not the same bits).  No temporary.
+ * Refused: frame_length < 4, hop < 1, frame_length > n without center, batch_stride < n, min_period < 1, max_period <= min_period,
+ * max_period > frame_length - frame_length / 2 - 1, sr or threshold not finite and positive, center not 0 or 1 (INVALID_ARG); frames
+ * longer than 4096 samples ("frames of up to 4096 samples are built", UNSUPPORTED).  Not built: f64 and complex rows, pad_mode other
+ * than constant, frames beyond 4096 samples, pYIN's HMM, sharded entry points, NIF and Elixir functions.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+/* F of the contract; negative status when the arguments are refused.  Host only, no context */
+int64_t nxsig_yin_frames(int64_t n, int64_t frame_length, int64_t hop, int32_t center);
+int nxsig_yin_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int64_t batch_stride, int64_t frame_length, int64_t hop,
+                  int32_t center, int64_t min_period, int64_t max_period, double sr, double threshold, float* f0, float* v, float* cmnd,
+                  int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

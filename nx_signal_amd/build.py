@@ -70,6 +70,7 @@ UNITS = [
     # Transforms.phase_vocoder: a double rotor product per bin, lanes own bins and waves walk time; a three-launch scan over chunks
     ("kernels_pvoc.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     ("kernels_lpc.hip", []),  # Spectral.lpc: Burg's recursion per frame, the error sequences of a frame in one wave's double registers; a launch per stage for long frames
+    ("kernels_yin.hip", []),  # Spectral.yin: the difference function as a register-tiled sliding product over an LDS-staged frame in double, prefix scan and search in the same launch
 ]
 
 

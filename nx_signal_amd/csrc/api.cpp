@@ -2691,6 +2691,50 @@ int nxsig_dct_f32(nxsig_ctx* ctx, const float* x, int64_t length, int64_t batch,
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Spectral.yin */
+int64_t nxsig_yin_frames(int64_t n, int64_t frame_length, int64_t hop, int32_t center) {
+  bool unsupported = false;
+  if (const char* what = yin_check_framing(n, frame_length, hop, center, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("yin_frames: ") + what);
+  return yin_frames(n, frame_length, hop, center);
+}
+
+int nxsig_yin_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int64_t batch_stride, int64_t frame_length, int64_t hop,
+                  int32_t center, int64_t min_period, int64_t max_period, double sr, double threshold, float* f0, float* v, float* cmnd,
+                  int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || (!f0 && !cmnd)) return set_error(NXSIG_ERR_INVALID_ARG, "yin: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  if (const char* what = yin_check(batch, n, batch_stride, frame_length, hop, center, min_period, max_period, sr, threshold, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("yin: ") + what);
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  const size_t frames = (size_t)batch * yin_frames(n, frame_length, hop, center), fb = sizeof(float);
+  const HostIo::In in{x, rows_bytes((int32_t)batch, batch_stride, n, fb), kScratchNdStageA};
+  const HostIo::Out of{f0, frames * fb, kScratchNdStageOut}, ov{v, frames * fb, kScratchNdStageOut},
+      oc{cmnd, frames * (size_t)(max_period - min_period + 1) * fb, kScratchNdStageOut};
+  HostIo io(c, mem);   // only the results asked for are staged, in the order f0, v, cmnd
+  if (f0 && v && cmnd) rc = io.open({in}, {of, ov, oc});
+  else if (f0 && v) rc = io.open({in}, {of, ov});
+  else if (f0 && cmnd) rc = io.open({in}, {of, oc});
+  else if (v && cmnd) rc = io.open({in}, {ov, oc});
+  else if (f0) rc = io.open({in}, {of});
+  else rc = io.open({in}, {oc});
+  if (rc) return rc;
+  int slot = 0;
+  YinLaunch l;
+  l.x = io.in[0]; l.batch = batch; l.n = n; l.x_stride = batch_stride; l.frame_length = frame_length; l.hop = hop; l.center = center;
+  l.min_period = min_period; l.max_period = max_period; l.sr = sr; l.threshold = threshold;
+  l.f0 = f0 ? io.out[slot++] : nullptr; l.v = v ? io.out[slot++] : nullptr; l.cmnd = cmnd ? io.out[slot++] : nullptr;
+  if ((rc = launch_yin(c, l))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"
 
 namespace nxsig {

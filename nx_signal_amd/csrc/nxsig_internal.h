@@ -96,7 +96,7 @@ int make_framing(int64_t L, int32_t N, int32_t hop, int32_t pad_mode, int64_t pa
   X(FIR32) X(FIR_PAD_TAPS) X(FIR_PHASE) X(FIR_HREG) X(FIR_UNITS_PER_WAVE) X(FIR_R2K) X(FIR_DLINE)                                                    \
   X(MEL_TILE) X(MEL_LDS_KB) X(FFT_TILED) X(FFT_TILE_ELEMS) X(FFT_TILE_NT) X(FFT_COLUMNS) X(FFT_TILED_MIN) X(CONV_POW2)          \
   X(DIRECT_FAST) X(POOL_MAX_MB) X(NO_PREFAULT) X(HOST_PIPE) X(DISABLE_FILTER_TILES) X(DISABLE_PEAK_TILES) X(DISABLE_RESAMPLE_LDS) \
-  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(XCORR_WAVE) X(XCORR_SLAB_ROWS) X(MDCT_WAVE) X(PVOC_CHUNK) X(LPC_WAVE) X(LOMBSCARGLE_TILE)
+  X(TABLE_CACHE_MAX) X(DISABLE_WELCH_WAVE) X(DISABLE_SOSFILT_SCAN) X(DISABLE_FIND_PEAKS_TABLES) X(DISABLE_SAVGOL_TILES) X(DISABLE_HILBERT_WAVE) X(DISABLE_DCT_DIRECT) X(DISABLE_LFILTER_SCAN) X(CZT_WAVE) X(CWT_WAVE) X(XCORR_WAVE) X(XCORR_SLAB_ROWS) X(MDCT_WAVE) X(PVOC_CHUNK) X(LPC_WAVE) X(YIN_LAGS) X(LOMBSCARGLE_TILE)
 enum TuneKey : int {
 #define NXSIG_X(n) kT_##n,
   NXSIG_TUNABLES(NXSIG_X)
@@ -754,4 +754,21 @@ struct LpcLaunch {
   void* e;                  // device f32 [batch][frames], or null
 };
 int launch_lpc(Ctx* c, const LpcLaunch& a);
+}  // namespace nxsig
+
+#include "yin_plan.hpp"
+
+namespace nxsig {
+// kernels_yin.hip: Spectral.yin over device rows (include/nxsig.h states the definition, DESIGN.md section 3.26 the design; the argument
+// checks are the caller's).  One launch, no temporary.  Everything is enqueued on c->stream
+struct YinLaunch {
+  const void* x;            // device f32 rows of n samples, x_stride elements apart
+  int64_t batch, n, x_stride, frame_length, hop, min_period, max_period;
+  int32_t center;
+  double sr, threshold;
+  void* f0;                 // device f32 [batch][yin_frames(n, frame_length, hop, center)], or null
+  void* v;                  // device f32 [batch][frames], or null
+  void* cmnd;               // device f32 [batch][frames][max_period - min_period + 1], or null
+};
+int launch_yin(Ctx* c, const YinLaunch& a);
 }  // namespace nxsig

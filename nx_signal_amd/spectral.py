@@ -135,3 +135,5 @@ def coherence(x, y, window, ctx=None, **opts):
 from ._lombscargle import lombscargle  # noqa: E402,F401
 # ... and so does lpc (_lpc.py)
 from ._lpc import lpc  # noqa: E402,F401
+# ... and yin (_yin.py)
+from ._yin import yin  # noqa: E402,F401
