@@ -1293,6 +1293,50 @@ int nxsig_yin_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int6
                   int32_t center, int64_t min_period, int64_t max_period, double sr, double threshold, float* f0, float* v, float* cmnd,
                   int32_t mem);
 
+/* ---- Spectral.cqt / vqt (an extension: constant-Q and variable-Q transforms of every row, following librosa.cqt / librosa.vqt;
+ * DESIGN.md section 3.27) ----
+ * THE DEFINITION.  A sampling rate sr, B bins per octave, fmin, n_bins, filter_scale, gamma >= 0 (cqt is vqt with gamma = 0), hop >= 1.
+ * With alpha = 2^(1/B) - 1 and f_k = fmin 2^(k/B), k = 0 ... n_bins - 1, all in double:
+ *   l_k  = filter_scale sr / (alpha f_k + gamma)                 a real number
+ *   lo_k = floor(-l_k / 2),  hi_k = floor(l_k / 2) - 1,  N_k = hi_k - lo_k + 1
+ *   w_k[j] = 1/2 - 1/2 cos(2 pi j / N_k),  j = 0 ... N_k - 1     the periodic Hann window
+ *   b_k[n] = w_k[n - lo_k] exp(2 pi i f_k n / sr),  n = lo_k ... hi_k
+ *   norm = 1 divides b_k by sum_n |b_k[n]|, norm = 2 by its Euclidean norm, no norm by nothing
+ *   g_k = sqrt(l_k) if scale, else l_k
+ *   C[k, t] = g_k sum_{n = lo_k .. hi_k} x~[t hop + n] conj(b_k[n]),  t = 0 ... F - 1,  F = 1 + length / hop (integer division)
+ * x~ is the row with zeros outside [0, length): frames are always centred at t hop.  f_k < sr / 2 and N_k >= 2 for every bin.  These
+ * are the filters, the normalisation and the scaling of librosa.cqt / librosa.vqt with window = "hann" and pad_mode = "constant",
+ * evaluated directly and not by librosa's recursive downsampling: this FOLLOWS librosa, it does not reproduce its approximation error.
+ * THE C ENTRY TAKES THE BANK AS DATA: per bin lo[k] (s64) and count[k] = N_k (s32, >= 2), and taps, the c64 values
+ * g_k conj(b_k[n]) of all bins concatenated in the order of k, n ascending, formed in double and rounded to f32 once (host arrays, all
+ * three, whatever `mem` says).  It computes C[k, t] = sum_{j < count[k]} x~[t hop + lo[k] + j] taps_k[j] for ANY such bank.
+ * Rows lie batch_stride >= length elements apart; out is dense [batch][n_bins][F], c64 for output_kind 0, f32 |C| for 1 and f32 |C|^2
+ * for 2, both formed from the double sums before the one rounding.
+ * Non-finite rule: an Inf / NaN sample makes exactly the (k, t) whose support [t hop + lo[k], t hop + lo[k] +
+ * count[k] - 1] holds it NaN (both parts of a complex output); every other output keeps the bits it has when that sample is replaced
+ * by 0.  Rows, and the gaps of strided rows, never reach each other.
+ * Deterministic: an output's bits depend on its row's samples, hop, the bank and the tier alone, never on the batch or the grid; sums
+ * are combined in a fixed order, no atomics.  The two tiers agree within the 1e-5 of the row maximum of |C|, not in bits.
+ * Dispatch: "cqt.mfma" (the default: a banded real-by-complex GEMM on the f32 matrix instruction v_mfma_f32_16x16x4_f32, bins sorted
+ * by length in tiles of 16, f32 sums within a panel of 512 samples, panels added in double in a fixed order) or "cqt.direct"
+ * (NXSIG_CQT_MFMA=0: one wave per bin and 8 frames, every product and sum in double).  Two temporaries of the family's own (the rows'
+ * non-finite bits and their prefix counts: 12 bytes per 64 samples).
+ * Refused: length < 1, hop < 1, batch < 0, batch_stride < length, n_bins < 1, a count < 2, an output_kind other than 0 / 1 / 2, a
+ * non-finite tap, x overlapping out (INVALID_ARG); more than 4096 bins, a bin of more than 2^24 taps, a bank of more than 2^22 taps
+ * (UNSUPPORTED).  Not built: f64 rows, other windows, center = False, pad_mode other than constant, icqt, chroma, hybrid / pseudo CQT,
+ * sharded entry points, NIF and Elixir functions.
+ * Every argument check comes ahead of the context; a device call returns without waiting.
+ */
+/* F of the contract; negative status when the arguments are refused.  Host only, no context */
+int64_t nxsig_cqt_frames(int64_t length, int64_t hop);
+/* The plan of cqt.mfma for a bank, host only, no context: summary[4] = bin tiles, sub-panels of 64 samples in the table, complex cells of
+ * the table, LDS bytes of a workgroup; tiles (or NULL) [tiles][4] = bins, the first n, sub-panels, the longest bin of each tile; cells (or
+ * NULL) [sum of count]: the cell of the table that each tap of the concatenated bank lands in.  Returns the taps of the bank, or a
+ * negative status */
+int64_t nxsig_cqt_plan(int64_t n_bins, const int64_t* lo, const int32_t* count, int64_t* summary, int64_t* tiles, int64_t* cells);
+int nxsig_cqt_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t length, int64_t batch_stride, int64_t hop, int64_t n_bins,
+                  const int64_t* lo, const int32_t* count, const void* taps, void* out, int32_t output_kind, int32_t mem);
+
 #ifdef __cplusplus
 }
 #endif

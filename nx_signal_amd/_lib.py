@@ -208,6 +208,9 @@ SIGNATURES = {
     "nxsig_lpc_f32": (C.c_int, [_ctx_iir, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i32]),
     "nxsig_yin_frames": (_i64, [_i64, _i64, _i64, _i32]),   # host only: no tensor operand, no context
     "nxsig_yin_f32": (C.c_int, [_ctx_iir, _p, _i64, _i64, _i64, _i64, _i64, _i32, _i64, _i64, _f64, _f64, _p, _p, _p, _i32]),
+    "nxsig_cqt_frames": (_i64, [_i64, _i64]),   # host only: no tensor operand, no context
+    "nxsig_cqt_plan": (_i64, [_i64, _p, _p, _p, _p, _p]),   # host only
+    "nxsig_cqt_f32": (C.c_int, [_ctx_iir, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _i32, _i32]),
     "nxsig_sawtooth": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _i32]),
     "nxsig_square": (C.c_int, [_p, _p, _i32, _i64, _f64, _p, _p, _i32]),
     "nxsig_gaussian_pulse": (C.c_int, [_p, _p, _i32, _i64, _f64, _f64, _f64, _p, _p, _p, _i32]),

@@ -71,6 +71,7 @@ UNITS = [
     ("kernels_pvoc.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     ("kernels_lpc.hip", []),  # Spectral.lpc: Burg's recursion per frame, the error sequences of a frame in one wave's double registers; a launch per stage for long frames
     ("kernels_yin.hip", []),  # Spectral.yin: the difference function as a register-tiled sliding product over an LDS-staged frame in double, prefix scan and search in the same launch
+    ("kernels_cqt.hip", []),  # Spectral.cqt / vqt: a banded real-by-complex GEMM on the f32 matrix instruction over LDS-staged frames, double across panels; a double-precision wave tier beside it
 ]
 
 

@@ -2735,6 +2735,69 @@ int nxsig_yin_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t n, int6
   NXSIG_API_END
 }
 
+/* ---------------------------------------------------------------- Spectral.cqt / vqt */
+int64_t nxsig_cqt_frames(int64_t length, int64_t hop) {
+  bool unsupported = false;
+  if (const char* what = cqt_check_framing(length, hop, &unsupported))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("cqt_frames: ") + what);
+  return cqt_frames(length, hop);
+}
+
+int64_t nxsig_cqt_plan(int64_t n_bins, const int64_t* lo, const int32_t* count, int64_t* summary, int64_t* tiles, int64_t* cells) {
+  NXSIG_API_BEGIN
+  if (!lo || !count || !summary) return set_error(NXSIG_ERR_INVALID_ARG, "cqt_plan: null pointer argument");
+  bool unsupported = false;
+  int64_t total = 0;
+  if (const char* what = cqt_check(0, 1, 1, 1, n_bins, lo, count, kCqComplex, &unsupported, &total))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("cqt_plan: ") + what);
+  CqtPlan p;
+  cqt_plan(n_bins, lo, count, &p);
+  summary[0] = (int64_t)p.tiles.size(); summary[1] = p.subs_total; summary[2] = p.subs_total * (kCqtSub / 4 * 64); summary[3] = (int64_t)kCqtLdsBytes;
+  std::vector<int64_t> off((size_t)n_bins);
+  int64_t at = 0;
+  for (int64_t k = 0; k < n_bins; ++k) { off[(size_t)k] = at; at += count[k]; }
+  for (size_t i = 0; i < p.tiles.size(); ++i) {
+    const CqtTile& t = p.tiles[i];
+    if (tiles) { tiles[4 * i] = t.bins; tiles[4 * i + 1] = t.n_lo; tiles[4 * i + 2] = t.subs; tiles[4 * i + 3] = p.order[(size_t)t.first]; }
+    for (int64_t m = 0; cells && m < t.bins; ++m) {
+      const int64_t k = p.order[(size_t)(t.first + m)];
+      for (int64_t j = 0; j < count[k]; ++j) cells[off[(size_t)k] + j] = cqt_cell(t, m, lo[k] + j);
+    }
+  }
+  return total;
+  NXSIG_API_END
+}
+
+int nxsig_cqt_f32(nxsig_ctx* ctx, const float* x, int64_t batch, int64_t length, int64_t batch_stride, int64_t hop, int64_t n_bins,
+                  const int64_t* lo, const int32_t* count, const void* taps, void* out, int32_t output_kind, int32_t mem) {
+  NXSIG_API_BEGIN
+  // the argument checks need no context and come ahead of it
+  if (!x || !lo || !count || !taps || !out) return set_error(NXSIG_ERR_INVALID_ARG, "cqt: null pointer argument");
+  int rc = check_mem(mem);
+  if (rc) return rc;
+  bool unsupported = false;
+  int64_t total = 0;
+  if (const char* what = cqt_check(batch, length, batch_stride, hop, n_bins, lo, count, output_kind, &unsupported, &total))
+    return set_error(unsupported ? NXSIG_ERR_UNSUPPORTED : NXSIG_ERR_INVALID_ARG, std::string("cqt: ") + what);
+  const float* tf = static_cast<const float*>(taps);
+  for (int64_t i = 0; i < 2 * total; ++i)
+    if (!std::isfinite(tf[i])) return set_error(NXSIG_ERR_INVALID_ARG, "cqt: the taps must be finite");
+  const size_t x_bytes = batch ? ((size_t)(batch - 1) * batch_stride + length) * sizeof(float) : 0;
+  const size_t out_bytes = (size_t)batch * n_bins * cqt_frames(length, hop) * (output_kind == kCqComplex ? sizeof(float2) : sizeof(float));
+  if (czt_overlap(x, x_bytes, out, out_bytes)) return set_error(NXSIG_ERR_INVALID_ARG, "cqt: x and out must not overlap");
+  NXSIG_CHECK_CTX(ctx)
+  DispatchScope dispatch_scope(c);
+  if (batch == 0) return NXSIG_OK;
+  HostIo io(c, mem);
+  if ((rc = io.open({{x, x_bytes, kScratchNdStageA}}, {{out, out_bytes, kScratchNdStageOut}}))) return rc;
+  CqtLaunch l;
+  l.x = io.in[0]; l.batch = batch; l.length = length; l.x_stride = batch_stride; l.hop = hop; l.n_bins = n_bins;
+  l.lo_host = lo; l.count_host = count; l.taps_host = taps; l.total = total; l.kind = output_kind; l.out = io.out[0];
+  if ((rc = launch_cqt(c, l))) return rc;
+  return io.close();
+  NXSIG_API_END
+}
+
 }  // extern "C"
 
 namespace nxsig {

@@ -137,3 +137,5 @@ from ._lombscargle import lombscargle  # noqa: E402,F401
 from ._lpc import lpc  # noqa: E402,F401
 # ... and yin (_yin.py)
 from ._yin import yin  # noqa: E402,F401
+# ... and cqt / vqt (_cqt.py)
+from ._cqt import cqt, cqt_frequencies, cqt_lengths, vqt  # noqa: E402,F401
